@@ -16,11 +16,16 @@ current frame — through ellc_align_enqueue / ellc_align_fetch: mask/compaction
 Gauss-Newton schedule with early exit disabled so the work is deterministic (32 GN iterations per alignment), followed —
 when N>1 — by the single gather of the resulting se(3) poses over RCCL. Inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field). Besides the contract's fields it carries the
-same workload in the per-pixel bit-exact arithmetic mode (`exact_arith`, repeated in `config`), a sustained block of >= 2000
-steps, BASELINE configs[4] at 16 alignments per GPU (`c4_dense`), the depth-map kernels against their algorithmic bytes
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field). A plain run does only what the headline needs:
+set-up, warm-up, the K timed steps and the contract's fields. With --full the line also carries the roofline of the dominant
+kernel, the same workload in the per-pixel bit-exact arithmetic mode (`exact_arith`, repeated in `config`), a sustained block of
+>= 2000 steps, BASELINE configs[4] at 16 alignments per GPU (`c4_dense`), the depth-map kernels against their algorithmic bytes
 (`depth`), the single alignment and tracked frame of configs[1] (with and without the loop-closure batch running beside it),
 and the CPU port timed on this box's host cores (`cpu_baseline`, with the pose error of the GPU result against it).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller (ellc_align_fetch) as
+DIR/pose.npy (B x 6 f32 se(3)), DIR/iters.npy (B x levels, iterations per level, f64) and DIR/weighted.npy (B f32), and with a
+gather DIR/gathered.npy (the last all-gathered result table, f32). The inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -55,11 +60,14 @@ def parse():
                     "launch sequence, up to this many (1: every batch is launched by itself, at most three in flight)")
     ap.add_argument("--early-exit", action="store_true", help="informational: the reference's early exit on (data-dependent iteration counts; "
                     "value then counts the iterations actually executed)")
-    ap.add_argument("--blocks", type=int, default=25, help="after the timed region: this many further blocks of --steps steps, for the spread (N=1)")
-    ap.add_argument("--sustained", type=int, default=2000, help="after the timed region: one block of this many steps (N=1; 0: none)")
-    ap.add_argument("--no-extras", action="store_true", help="only the contract's fields (no exact_arith / c4_dense / depth / tracking sub-records)")
+    ap.add_argument("--full", action="store_true", help="after the timed region: the roofline of the dominant kernel, the sub-records and the CPU "
+                    "baseline (off: a plain run prints the contract's fields only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--blocks", type=int, default=25, help="--full: after the timed region, this many further blocks of --steps steps, for the spread (N=1)")
+    ap.add_argument("--sustained", type=int, default=2000, help="--full: after the timed region, one block of this many steps (N=1; 0: none)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: the roofline only (no exact_arith / c4_dense / depth / tracking sub-records)")
     ap.add_argument("--trace-only", action="store_true", help="stop after the timed region (kernel traces of exactly the timed workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--gather-at-1", action="store_true", help="N=1 only: run the per-batch gather all the same (RCCL communicator of one rank through "
                     "the library's C entry points): what the exchange costs the loop, measured on one GPU")
     ap.add_argument("--backend", choices=["nccl", "gloo", "tcp"], default="nccl", help="N>1: transport of the gather of the poses. nccl = RCCL "
@@ -75,7 +83,10 @@ def parse():
     ap.add_argument("--cache-records", action="store_true", help="diagnostic only (NOT the contract's workload): cfg.cache_records on the main workload — the compact "
                     "lists are kept with the keyframe slots, so the timed steps contain no compaction at all: the ceiling of what hiding it can give")
     ap.add_argument("--lib", default=None, help="diagnostic A/B only: load this build of the library instead of csrc/libellc_hip.so")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def spawn_ranks(a):
@@ -228,7 +239,7 @@ class Workload:
         """nsteps steps, software-pipelined through the asynchronous API: up to G batches in flight, each on its own stream and
         slot group; every batch is fetched (and, N>1, gathered) before this returns."""
         ctx, G, B = self.ctx, self.G, self.B
-        pose = iters = None
+        pose = iters = wgt = None
         for s in range(min(G, nsteps)):
             ctx.align_enqueue(self.kf[s % G], self.fr[s % G], mode=self.mode)
         for s in range(nsteps):
@@ -237,12 +248,12 @@ class Workload:
                 ctx.align_enqueue(self.kf[(s + G) % G], self.fr[(s + G) % G], mode=self.mode)
             if on_fetch is not None:
                 on_fetch(pose, iters, wgt)
-        return pose, iters
+        return pose, iters, wgt
 
     def timed(self, nsteps):
         self.ctx.sync()
         t0 = time.perf_counter()
-        pose, iters = self.run(nsteps)
+        pose, iters, _ = self.run(nsteps)
         self.ctx.sync()
         return time.perf_counter() - t0, pose, iters
 
@@ -373,12 +384,14 @@ def main():
                                  port=int(os.environ.get("MASTER_PORT", "29500")) + 18)
     outstanding = []   # rows of each exchange in flight, oldest first
     gathered_rows = [0]
+    last_table = [None]   # the newest gathered table (Comm.finish returns a fresh array): what --dump-outputs writes
 
     def finish_one():
         rows = outstanding.pop(0)
         t = comm.finish(rows)
         assert t.shape == (rows, sharding.RECORD)
         gathered_rows[0] += rows
+        last_table[0] = t
 
     def start(table):
         if len(outstanding) == depth:
@@ -414,10 +427,12 @@ def main():
     ctl.barrier()
     sync()
     t0 = time.perf_counter()
-    pose, iters = run(a.steps)
+    pose, iters, wgt = run(a.steps)
     sync()
     ctl.barrier()
     dt_mine = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, pose, iters, wgt, last_table[0])
     dt = ctl.max(dt_mine)
     per_rank_ms = [1e3 * x / a.steps for x in ctl.all(dt_mine)]   # every rank's own time for its K steps (the contract's T is their maximum)
     if a.early_exit:   # every batch of a group repeats the same alignments: the last batch's count holds for all
@@ -483,7 +498,7 @@ def main():
         ctl.barrier()
         ctl.close()
 
-    if a.trace_only:
+    if a.trace_only or not a.full:   # a plain run: the contract's fields only
         if rank == 0:
             print(json.dumps(out), flush=True)
         wl.close()
@@ -615,6 +630,17 @@ def main():
     if wl is not None:
         wl.close()
     finish()
+
+
+def dump_outputs(d, pose, iters, wgt, gathered):
+    """What the last timed step returned to its caller (ellc_align_fetch), as float arrays: the step's B alignments are the
+    same on every run with the same arguments (seeded scenes, group (steps - 1) mod G)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"pose": np.asarray(pose, np.float32), "iters": np.asarray(iters, np.float64), "weighted": np.asarray(wgt, np.float32)}
+    if gathered is not None:
+        arrays["gathered"] = np.asarray(gathered, np.float32)
+    for name, x in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), x)
 
 
 def rehearse_launcher(a, world, rank, local_rank):

@@ -9,7 +9,7 @@ for v in "$@"; do
     python3 tools/profile_kernel.py --arith fast > $OUT/k640_${v}_$rep.json 2>> $OUT/err.log
     python3 tools/profile_kernel.py --arith fast --width 1280 --height 960 --levels 5 --dense --batch 16 --reps 10 > $OUT/kc4_${v}_$rep.json 2>> $OUT/err.log
   done
-  python3 bench.py $LIBARG --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_$v.json 2>> $OUT/err.log
+  python3 bench.py $LIBARG --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_$v.json 2>> $OUT/err.log
 done
 python3 - $OUT <<'PY'
 import json, sys, glob, os

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Side-by-side of the headline fields of two or more bench.py JSON lines: python tools/bench_diff.py a.json b.json ..."""
+"""Side-by-side of the headline fields of two or more `bench.py --full` JSON lines: python tools/bench_diff.py a.json b.json ..."""
 import json
 import sys
 

@@ -5,7 +5,7 @@ OUT=gpurun_out/$1; mkdir -p $OUT
 run() {  # name, queues, args
   local name=$1; shift; local q=$1; shift
   if [ -n "$q" ]; then export GPU_MAX_HW_QUEUES=$q; else unset GPU_MAX_HW_QUEUES; fi
-  python3 bench.py --steps 40 --warmup 8 --no-extras --no-cpu-baseline --blocks 5 --sustained 1000 "$@" > $OUT/$name.json 2>> $OUT/err.log
+  python3 bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --blocks 5 --sustained 1000 "$@" > $OUT/$name.json 2>> $OUT/err.log
   python3 - $OUT/$name.json $name <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

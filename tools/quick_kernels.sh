@@ -8,8 +8,8 @@ for A in fast exact; do
   python3 tools/profile_kernel.py --arith $A --width 1280 --height 960 --levels 5 --dense --batch 16 --reps 10 > $OUT/kc4_$A.json 2>> $OUT/err.log
 done
 python3 tools/profile_kernel.py --arith fast --level 1 > $OUT/k640_fast_l1.json 2>> $OUT/err.log
-python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_fast.json 2>> $OUT/err.log
-python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --arith exact > $OUT/bench_exact.json 2>> $OUT/err.log
+python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/bench_fast.json 2>> $OUT/err.log
+python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --arith exact > $OUT/bench_exact.json 2>> $OUT/err.log
 python3 - $OUT <<'PY'
 import json, sys, glob, os
 for f in sorted(glob.glob(os.path.join(sys.argv[1], "k*.json"))):
