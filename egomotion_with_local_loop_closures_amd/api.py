@@ -335,6 +335,25 @@ class Context:
         self._ck(self._l.ellc_debug_persist_counters(self.h, C.byref(a), C.byref(b), C.byref(r)), "ellc_debug_persist_counters")
         return a.value, b.value, r.value
 
+    def debug_schedule_sums(self, kf_slots, frame_slots, level, pose, mode=MODE_FCA):
+        """One launch of the level-bound schedule's kernel at `level` from the poses pose[b] (ellc_debug_schedule_sums). Returns
+        dict(H=[B][6][6] symmetric, b=[B][6] (f64, the blocks' sums), pose=[B][6] after the step, hinv=[B][6][6] (constant-weight
+        path), kernel=name, grid=(blocks per alignment, age rounds, xcd relabelling))."""
+        self._need_diag("ellc_debug_schedule_sums")
+        B = len(kf_slots)
+        pose = np.ascontiguousarray(np.broadcast_to(np.asarray(pose, np.float32).reshape(-1, 6), (B, 6)), np.float32)
+        _, kf, fr, _ = self._batch(kf_slots, frame_slots, None)
+        sums = np.zeros((B, 27), np.float64); newp = np.zeros((B, 6), np.float32); hinv = np.zeros((B, 36), np.float32)
+        name = C.create_string_buffer(64); grid = np.zeros(3, np.int32)
+        self._ck(self._l.ellc_debug_schedule_sums(self.h, B, _p(kf), _p(fr), level, mode, _p(pose), _p(sums), _p(newp), _p(hinv), name, 64,
+                                                  _p(grid)), "ellc_debug_schedule_sums")
+        H = np.zeros((B, 6, 6), np.float64)
+        iu = np.triu_indices(6)
+        H[:, iu[0], iu[1]] = sums[:, :21]
+        H[:, iu[1], iu[0]] = sums[:, :21]
+        return dict(H=H, b=sums[:, 21:].copy(), pose=newp, hinv=hinv.reshape(B, 6, 6), kernel=name.value.decode(),
+                    grid=tuple(int(v) for v in grid))
+
     def profile_gn_kernel(self, kf_slots, frame_slots, level, reps=20):
         self._need_diag("ellc_profile_gn_kernel")
         B, kf, fr, _ = self._batch(kf_slots, frame_slots, None)

@@ -161,8 +161,9 @@ struct ellc_ctx {
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // captured launch sequences of ellc_align, keyed by (B, unique keyframes, mode, flags: save_weights | persist | run | continuation, batch set)
-  std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;
+  // captured launch sequences of ellc_align, keyed by (B, unique keyframes, mode, flags: save_weights | continuation | track | pollable,
+  // launches of a first state-driven graph, cfg.grid_batch, dense, cur_need, batch set): launch_align_graph
+  std::map<std::tuple<int, int, int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
   long long counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ELLC_CTR_* (ellc_abi.h): ellc_ctx_counters
   int poll_timeout_us = 2000;   // resolve_batch polls this long before it falls back to the event
   bool poll_results = true;     // resolve_batch polls the pinned result records of small single-stream batches; ELLC_NO_POLL=1 (diag)

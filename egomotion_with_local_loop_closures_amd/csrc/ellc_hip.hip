@@ -514,32 +514,70 @@ static void set_age_split(ellc_ctx* c, FusedArgs& fa, int B) {
   fa.age_rounds = R;
 }
 
-static void launch_fused(ellc_ctx* c, dim3 grd, dim3 blk, const FusedArgs& fa, hipStream_t st) {
+static void set_track_fields(const ellc_ctx* c, FusedArgs& fa, bool continuation);
+static const char* launch_ica_fused(ellc_ctx* c, dim3 grd, dim3 blk, const FusedArgs& fa, hipStream_t st);
+
+// The one kernel launch of a level-bound schedule at fa.g.level (enqueue_schedule_fused, enqueue_schedule_ica_fused; the same
+// choice in ellc_profile_gn_kernel and ellc_debug_schedule_sums): which kernel runs for this context, batch and record set.
+// Returns the kernel's name (the diagnostic hooks report it).
+static const char* launch_level_bound(ellc_ctx* c, dim3 grd, dim3 blk, const FusedArgs& fa, hipStream_t st) {
   const AlignState* src_state = fa.g.state + (size_t)(fa.seq & 1) * fa.stride_state;
   const float* prev_part = fa.g.partials + (size_t)((fa.seq + 1) & 1) * fa.stride_part;
+  if (fa.ica) return launch_ica_fused(c, grd, blk, fa, st);   // constant weights: b sums only, H^-1 from the keyframe slot
   if (c->cur_dense) {   // dense maps: no compact lists (gn_fca_dense; launch_group decided)
     if (!c->fast) {   // the exact mode: a thread per pixel, the planes and the slot's 1 / Z plane in double (no 20-byte records)
       if (c->geom_h[0].divc_ok) hipLaunchKernelGGL(gn_fca_dense_x<true>, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
       else hipLaunchKernelGGL(gn_fca_dense_x<false>, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
-      return;
+      return c->geom_h[0].divc_ok ? "gn_fca_dense_x<divc>" : "gn_fca_dense_x";
     }
     // four adjacent pixels per thread where a row is a whole number of them (r06: one tap window per row for the four)
-    if (dense_quads_at(c, fa.g.level))
+    if (dense_quads_at(c, fa.g.level)) {
       hipLaunchKernelGGL(gn_fca_dense4, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
-    else
-      hipLaunchKernelGGL(gn_fca_dense, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
-    return;
+      return "gn_fca_dense4";
+    }
+    hipLaunchKernelGGL(gn_fca_dense, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
+    return "gn_fca_dense";
   }
   if (c->fast) {
     if (fa.g.save_w) hipLaunchKernelGGL((gn_fca_fused<false, true, true, 1>), grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
     else hipLaunchKernelGGL((gn_fca_fused<false, true, true, 0>), grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
+    return fa.g.save_w ? "gn_fca_fused<fast,pipe,savew>" : "gn_fca_fused<fast,pipe>";
   } else if (c->pipe) {
     if (c->geom_h[0].divc_ok) hipLaunchKernelGGL((gn_fca_fused<true, true>), grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
     else hipLaunchKernelGGL((gn_fca_fused<false, true>), grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
+    return c->geom_h[0].divc_ok ? "gn_fca_fused<exact,pipe,divc>" : "gn_fca_fused<exact,pipe>";
   } else {
     if (c->geom_h[0].divc_ok) hipLaunchKernelGGL((gn_fca_fused<true, false>), grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
     else hipLaunchKernelGGL((gn_fca_fused<false, false>), grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
+    return c->geom_h[0].divc_ok ? "gn_fca_fused<exact,divc>" : "gn_fca_fused<exact>";
   }
+}
+
+// The FusedArgs of a level-bound schedule (FCA, or ICA with ica = true) before its first launch: nothing pending.
+static FusedArgs level_bound_args(ellc_ctx* c, int B, int save_weights, bool ica) {
+  FusedArgs fa;
+  fa.continuation = 0;
+  set_track_fields(c, fa, false);
+  fa.seq = 0;
+  fa.prev_level = -1;
+  fa.prev_nblk = 0;
+  fa.early_exit = c->cfg.early_exit;
+  fa.stride_state = c->group_cap;
+  fa.stride_part = (size_t)c->group_cap * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
+  fa.g = make_gn_args(c, 0, B, (save_weights && !ica) ? 1 : 0, nullptr);
+  fa.res = c->result_dev_alias;
+  fa.ica = ica ? 1 : 0;
+  fa.xcd_map = (!ica && B % 8 == 0) ? 1 : 0;
+  for (int l = 0; l < ELLC_MAX_LEVELS; l++) { fa.nblk_lv[l] = 1; fa.max_it[l] = 0; }
+  fa.nblk_grid = 1;
+  fa.age_rounds = 0;
+  for (int i = 0; i < 5; i++) fa.age_cum[i] = 0;
+  return fa;
+}
+// ... and its launches at `level`: the grid (make_gn_args: the batch's grid size, cur_dense) and, FCA only, the age-balanced split
+static void level_bound_level(ellc_ctx* c, FusedArgs& fa, int level, int B) {
+  fa.g = make_gn_args(c, level, B, fa.g.save_w, nullptr);
+  if (!fa.ica) set_age_split(c, fa, B);
 }
 
 static void launch_finish(ellc_ctx* c, int B, const FusedArgs& fa, bool adaptive = false) {
@@ -785,29 +823,12 @@ static ellc_status enqueue_schedule_adaptive(ellc_ctx* c, int B, int save_weight
 // dominates; compacting the fine levels on a second stream beside the coarse iterations — fork/join cost more than the
 // overlap gave; a one-block-per-alignment kernel running all coarse iterations — one CU is VALU-bound on a level.)
 static ellc_status enqueue_schedule_fused(ellc_ctx* c, int B, int save_weights) {
-  FusedArgs fa;
-  fa.continuation = 0;
-  set_track_fields(c, fa, false);
-  fa.seq = 0;
-  fa.prev_level = -1;
-  fa.prev_nblk = 0;
-  fa.early_exit = c->cfg.early_exit;
-  fa.stride_state = c->group_cap;
-  fa.stride_part = (size_t)c->group_cap * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
-  fa.g = make_gn_args(c, 0, B, save_weights ? 1 : 0, nullptr);
-  fa.res = c->result_dev_alias;
-  fa.ica = 0;
-  fa.xcd_map = (B % 8 == 0) ? 1 : 0;
-  for (int l = 0; l < ELLC_MAX_LEVELS; l++) { fa.nblk_lv[l] = 1; fa.max_it[l] = 0; }
-  fa.nblk_grid = 1;
-  fa.age_rounds = 0;
-  for (int i = 0; i < 5; i++) fa.age_cum[i] = 0;
+  FusedArgs fa = level_bound_args(c, B, save_weights, false);
   for (int level = c->L - 1; level >= 0; level--) {
-    fa.g = make_gn_args(c, level, B, save_weights ? 1 : 0, nullptr);
-    set_age_split(c, fa, B);
+    level_bound_level(c, fa, level, B);
     const dim3 grd(fa.g.nblk, B), blk(ELLC_GN_THREADS);
     for (int it = 0; it < c->cfg.max_iter[level]; it++) {
-      launch_fused(c, grd, blk, fa, c->stream);
+      launch_level_bound(c, grd, blk, fa, c->stream);
       fa.prev_level = level;
       fa.prev_nblk = fa.g.nblk;
       fa.seq++;
@@ -821,30 +842,21 @@ static ellc_status enqueue_schedule_fused(ellc_ctx* c, int B, int save_weights) 
 
 // Constant-weight (ICA) schedule in the fused form: H^-1 per (keyframe, level) comes from the compaction (ica_hinv), every
 // launch solves the previous launch's b sums in its prologue: one launch per iteration plus the final solve.
+// (defined here, not in launch_level_bound: the kernels' order in the code object follows where they are first launched)
+static const char* launch_ica_fused(ellc_ctx* c, dim3 grd, dim3 blk, const FusedArgs& fa, hipStream_t st) {
+  const AlignState* src_state = fa.g.state + (size_t)(fa.seq & 1) * fa.stride_state;
+  const float* prev_part = fa.g.partials + (size_t)((fa.seq + 1) & 1) * fa.stride_part;
+  if (c->fast) hipLaunchKernelGGL(gn_ica_fused<true>, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa);
+  else hipLaunchKernelGGL(gn_ica_fused<false>, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa);
+  return c->fast ? "gn_ica_fused<fast>" : "gn_ica_fused<exact>";
+}
 static ellc_status enqueue_schedule_ica_fused(ellc_ctx* c, int B) {
-  FusedArgs fa;
-  fa.continuation = 0;
-  set_track_fields(c, fa, false);
-  fa.seq = 0;
-  fa.prev_level = -1;
-  fa.prev_nblk = 0;
-  fa.early_exit = c->cfg.early_exit;
-  fa.stride_state = c->group_cap;
-  fa.stride_part = (size_t)c->group_cap * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
-  fa.res = c->result_dev_alias;
-  fa.ica = 1;
-  fa.xcd_map = 0;
-  fa.age_rounds = 0;
-  for (int i = 0; i < 5; i++) fa.age_cum[i] = 0;
-  fa.g = make_gn_args(c, 0, B, 0, nullptr);
+  FusedArgs fa = level_bound_args(c, B, 0, true);
   for (int level = c->L - 1; level >= 0; level--) {
-    fa.g = make_gn_args(c, level, B, 0, nullptr);
+    level_bound_level(c, fa, level, B);
     const dim3 grd(fa.g.nblk, B), blk(ELLC_GN_THREADS);
     for (int it = 0; it < c->cfg.max_iter[level]; it++) {
-      const AlignState* src_state = fa.g.state + (size_t)(fa.seq & 1) * fa.stride_state;
-      const float* prev_part = fa.g.partials + (size_t)((fa.seq + 1) & 1) * fa.stride_part;
-      if (c->fast) hipLaunchKernelGGL(gn_ica_fused<true>, grd, blk, 0, c->stream, src_state, prev_part, fa.prev_nblk, fa);
-      else hipLaunchKernelGGL(gn_ica_fused<false>, grd, blk, 0, c->stream, src_state, prev_part, fa.prev_nblk, fa);
+      launch_level_bound(c, grd, blk, fa, c->stream);
       fa.prev_level = level;
       fa.prev_nblk = fa.g.nblk;
       fa.seq++;
@@ -1707,8 +1719,11 @@ static ellc_status launch_align_graph(ellc_ctx* c, int B, int nu, int mode, int 
   }
   // (cur_adaptive_first: launches of the first graph of a state-driven schedule; it varies with the context's hint)
   const int first = schedule_is_adaptive(c, mode, B) ? c->cur_adaptive_first : 0;
+  // (every choice in a field of its own: packed into one word, grid_batch << 12 reached the bits of the flags above it — a
+  // grid_batch of 65536 made a kept-H^-1 ICA graph the twin of the one that rebuilds H^-1)
   const auto key = std::make_tuple(B, continuation ? 0 : nu, mode,
-                                   (save_weights ? 1 : 0) | (continuation ? 2 : 0) | (c->track_call ? 4 : 0) | (c->cur_pollable ? 8 : 0) | (first << 4) | (c->cfg.grid_batch << 12) | (c->cur_dense ? (1 << 29) : 0) | (c->cur_need == 16 ? (1 << 28) : 0), set);
+                                   (save_weights ? 1 : 0) | (continuation ? 2 : 0) | (c->track_call ? 4 : 0) | (c->cur_pollable ? 8 : 0), first,
+                                   c->cfg.grid_batch, c->cur_dense ? 1 : 0, c->cur_need, set);
   auto it = c->graphs.find(key);
   if (it == c->graphs.end()) {
     hipGraph_t graph = nullptr;
@@ -2253,7 +2268,7 @@ ellc_status ellc_profile_gn_kernel(ellc_ctx* c, int B, const int* kf_slots, cons
     fa.stride_part = (size_t)c->group_cap * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
     c->cur_dense = dense;
     auto launch = [&]() {
-      launch_fused(c, grd, blk, fa, c->stream);
+      launch_level_bound(c, grd, blk, fa, c->stream);
       fa.seq++;
     };
     for (int i = 0; i < 3; i++) launch();
@@ -2299,6 +2314,69 @@ ellc_status ellc_profile_gn_kernel(ellc_ctx* c, int B, const int* kf_slots, cons
   }
   if (valid_pixels) *valid_pixels = V;
   if (algorithmic_bytes) *algorithmic_bytes = 4.0 * (double)c->geom_h[level].n * B + 14.0 * (double)V;
+  return ELLC_OK;
+}
+
+// One launch of the kernel the level-bound schedule runs at `level` for this context, batch and mode, with nothing pending, from the
+// callers' poses; its per-block partial sums summed per alignment in double, and the step the finish kernel solves from them.
+ellc_status ellc_debug_schedule_sums(ellc_ctx* c, int B, const int* kf_slots, const int* frame_slots, int level, int mode, const float* pose,
+                                     double* sums27, float* new_pose, float* ica_hinv36, char* kernel, int kernel_len, int* grid) {
+  ELLC_ENTER(c);
+  if (!c || !kf_slots || !frame_slots || !pose || level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, "bad argument");
+  if (mode != ELLC_MODE_FCA && mode != ELLC_MODE_ICA) return fail(c, ELLC_ERR_BAD_ARG, "unknown mode");
+  if (c->n_inflight > 0 || c->open_set >= 0) return fail(c, ELLC_ERR_NOT_READY, "ellc_debug_schedule_sums: fetch the enqueued batches first");
+  if (!c->use_fused || schedule_is_adaptive(c, mode, B))
+    return fail(c, ELLC_ERR_BAD_ARG, "ellc_debug_schedule_sums: this context and batch do not run the level-bound schedule");
+  select_batch_set(c, 0);
+  int nu = 0;
+  ellc_status s = stage_batch(c, B, kf_slots, frame_slots, pose, &nu);
+  if (s != ELLC_OK) return s;
+  for (int b = 0; b < B; b++) invalidate_records(c, kf_slots[b]);   // rebuilt here, outside the cache's bookkeeping
+  // the lists, or none (dense maps), and the record set as launch_group chooses them
+  bool dense = runs_dense(c, mode, B, 0);
+  for (int b = 0; b < B; b++) dense = dense && c->kf_dense[kf_slots[b]];
+  enqueue_stage_in(c, B);
+  if (!dense) {
+    const int need = need_of(c, mode);
+    s = run_prep(c, nu, need);
+    if (s != ELLC_OK) return s;
+    if (need & 4) enqueue_ica_hinv(c, nu);
+  }
+  // a record that no block writes stays NaN (all bits set) and shows in its alignment's sums
+  const size_t part_floats = (size_t)B * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
+  ELLC_HIP(c, hipMemsetAsync(c->partials_d, 0xff, part_floats * 4, c->stream));
+  c->cur_dense = dense;
+  FusedArgs fa = level_bound_args(c, B, 0, mode == ELLC_MODE_ICA);
+  fa.res = nullptr;
+  level_bound_level(c, fa, level, B);
+  const char* name = launch_level_bound(c, dim3(fa.g.nblk, B), dim3(ELLC_GN_THREADS), fa, c->stream);
+  c->cur_dense = false;
+  // the finish kernel solves the launch's sums (state buffer 1, partial buffer 0) into state buffer 0
+  fa.prev_level = level;
+  fa.prev_nblk = fa.g.nblk;
+  fa.seq = 1;
+  launch_finish(c, B, fa);
+  ELLC_HIP(c, hipGetLastError());
+  std::vector<float> part(part_floats);
+  std::vector<AlignState> st(B);
+  ELLC_HIP(c, hipMemcpyAsync(part.data(), c->partials_d, part_floats * 4, hipMemcpyDeviceToHost, c->stream));
+  ELLC_HIP(c, copy_blocking(c, st.data(), c->state_d, sizeof(AlignState) * B, hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; b++) {
+    double acc[27] = {};
+    for (int k = 0; k < fa.g.nblk; k++)
+      for (int i = fa.ica ? 21 : 0; i < 27; i++) acc[i] += (double)part[((size_t)b * ELLC_NBLK_MAX + k) * ELLC_PART_STRIDE + i];
+    if (sums27) std::memcpy(sums27 + 27 * b, acc, sizeof(acc));
+    if (new_pose) std::memcpy(new_pose + 6 * b, st[b].pose, 24);
+    if (ica_hinv36) {
+      if (fa.ica) ELLC_HIP(c, copy_blocking(c, ica_hinv36 + 36 * b, c->kf_tab_h[(size_t)level * c->cfg.max_keyframes + kf_slots[b]].hinv, 144, hipMemcpyDeviceToHost));
+      else std::memset(ica_hinv36 + 36 * b, 0, 144);
+    }
+  }
+  if (kernel && kernel_len > 0) {
+    std::strncpy(kernel, name, kernel_len - 1);
+    kernel[kernel_len - 1] = 0;
+  }
+  if (grid) { grid[0] = fa.g.nblk; grid[1] = fa.age_rounds; grid[2] = fa.xcd_map; }
   return ELLC_OK;
 }
 

@@ -44,6 +44,18 @@ ellc_status ellc_selftest_div_pair(ellc_ctx* ctx, int n, const float* a, const f
 ellc_status ellc_selftest_lu(ellc_ctx* ctx, int n, const double* tri21, float* inv36);
 
 
+/* Parity hook of the level-bound schedule kernels (gn_fca_fused, gn_fca_dense, gn_fca_dense4, gn_fca_dense_x, gn_ica_fused): stages
+ * the batch with pose[b] ([B][6]) as alignment b's pose, builds its compact lists (or H^-1 of the constant-weight path, or none for
+ * dense maps) as ellc_align does, launches ONCE the kernel the schedule runs at `level` for this context, batch and mode — the same
+ * grid, age-balanced split and XCD relabelling, nothing pending — and runs the finish kernel on its sums. sums27[b]: the blocks'
+ * partial records of alignment b summed in double (21 upper-triangular H by rows, then 6 b; the constant-weight kernel writes b only,
+ * H is returned as 0); new_pose[b]: the pose after that one Gauss-Newton step; ica_hinv36[b]: the row-major H^-1 of the constant-weight
+ * path at `level` (0 in FCA mode). kernel: the launched kernel's name; grid: {blocks per alignment, age rounds, XCD relabelling}.
+ * Output pointers may be NULL. Fails for a context or batch that runs the state-driven schedule. */
+ellc_status ellc_debug_schedule_sums(ellc_ctx* ctx, int B, const int* kf_slots, const int* frame_slots, int level, int mode,
+                                     const float* pose, double* sums27, float* new_pose, float* ica_hinv36, char* kernel, int kernel_len,
+                                     int* grid);
+
 /* ---- test hooks of the resident schedule (gn_fca_persist, the tracking call's one-launch form) ------------------------------ */
 /* Blocks with index >= first_block of every later resident launch start `polls` sleeps (about a microsecond each) late, as if the
  * dispatcher had placed them late: what a block that writes no records at the coarse levels must survive (it is lapped by the
