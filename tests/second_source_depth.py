@@ -10,6 +10,17 @@ A scalar f32 restatement, in numpy scalars, of
     frame::getInterpolatedElement (u8 and gradient)       Frame.h:181-394
     frame::calculateGradient                              Frame.cpp:185-285
 
+and (DepthMapStages, r08; vectorised over pixels, each pixel's f32 operations in the reference's order)
+
+    depthMap::updateDepthImage                            DepthPropagation.cpp:1254-1315
+    depthMap::fillDepthHoles / buildValIntegralBuffer     DepthPropagation.cpp:1317-1432
+    depthMap::regularizeDepthMap (both modes)             DepthPropagation.cpp:1436-1543
+    depthMap::makeInvDepthOne(true)                       DepthPropagation.cpp:1546-1587
+    depthMap::doRegularization                            DepthPropagation.cpp:1627-1635
+    depthMap::buildInvVarDepth / mapDepthArr2Mat          DepthPropagation.cpp:1637-1746
+    depthMap::finaliseKeyframe / createKeyFrame           DepthPropagation.cpp:1749-1794
+    depthMap::calculate_no_of_Seeds(true)                 DepthPropagation.cpp:1804-1830
+
 written FROM THE REFERENCE'S TEXT, statement by statement, WITHOUT looking at oracle/ellc_oracle_depth.cpp or at the HIP kernels: the
 C++ oracle and the kernels are one author's reading of those lines, and a shared misreading would be green in every GPU-vs-oracle
 test. tests/test_second_source_depth.py runs both on the same scenes and compares every field of every pixel.
@@ -584,3 +595,303 @@ class DepthSecondSource:
                     other["varianceSmoothed"][newY, newX] = F(-1.0)
         self.st = other          # std::swap(currentDepthHypothesis, otherDepthHypothesis)
         return other
+
+
+# ==================================================================================================================================
+# The stages that turn a map into what the tracker reads (DepthPropagation.cpp:1254-1830): fillDepthHoles / buildValIntegralBuffer,
+# regularizeDepthMap (both occlusion modes), doRegularization, makeInvDepthOne(true), updateDepthImage / buildInvVarDepth /
+# mapDepthArr2Mat, finaliseKeyframe, calculate_no_of_Seeds, createKeyFrame. Also written from the reference's text alone.
+#
+# Vectorised over pixels, each pixel's f32 operations in the reference's order: a stencil loop runs tap by tap over whole planes, a
+# skipped tap is np.where(taken, s + t, s) (the sum keeps its bits, whatever an untaken tap holds); serial f32 sums over the map run
+# through np.add.accumulate (sequential), never np.sum (pairwise). Taken as given in addition to the above: nothing (these stages call
+# no third-party arithmetic). Out: displayColourDepthMap (display only, no state), checkHighVariancePatch, scaleDepthMap and
+# makeInvDepthOne(false) (no callers), the unused sumIdepth / numIdepth of updateDepthImage (:1260-1268, never read).
+
+# ExternVariable.h:82-157 (the float constants that are compared with ints are kept float: the comparison promotes the int)
+VAR_RANDOM_INIT_INITIAL = F(0.125)
+VAL_SUM_MIN_FOR_CREATE = F(30.0)
+VAL_SUM_MIN_FOR_UNBLACKLIST = F(100.0)
+VAL_SUM_MIN_FOR_KEEP = F(24.0)
+REG_DIST_VAR = F(0.075) * F(0.075) * F(1.0) * F(1.0)
+DIFF_FAC_SMOOTHING = F(1.0) * F(1.0)
+REF_PYRAMID_LEVELS = 4                     # util::MAX_PYRAMID_LEVEL
+
+
+def unzero_planes(val):
+    """`unzero` above, applied to a plane: the same double comparisons and the same clamped values, one pixel at a time."""
+    v = np.asarray(val, np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        r = np.where(v < 0, np.where(v > -1e-10, -1e-10, v), np.where(v < 1e-10, 1e-10, v))
+    return r.astype(np.float32)
+
+
+def _add_if(take, s, t):
+    return np.where(take, s + t, s).astype(np.float32)
+
+
+def F_arr(a):
+    return np.asarray(a, np.float32)
+
+
+class DepthMapStages(DepthSecondSource):
+    """DepthSecondSource plus the stencil, rescale and export stages. Extra state, as in depthMap (DepthPropagation.h:47-78):
+    validityIntegralBuffer (zeroed by the constructor :26-28 and never cleared again: the rows buildValIntegralBuffer does not write
+    keep what they held), the level arrays deptharr / depthvararr, and the keyframe's depth Mats (level 0 differs from the array at
+    invalid pixels: 0 against -1). The *_classes dicts count the branch classes each stage took on its last call (for the tests)."""
+
+    def __init__(self, W, H, fx, fy, cx, cy, kinv, kf_image, kf_maxgrad, state, levels=REF_PYRAMID_LEVELS):
+        super().__init__(W, H, fx, fy, cx, cy, kinv, kf_image, kf_maxgrad, state)
+        self.levels = levels
+        self.validityIntegralBuffer = np.zeros((H, W), np.int32)
+        self.deptharr = [None] * levels
+        self.depthvararr = [None] * levels
+        self.depth_mat = [None] * levels
+        self.fill_classes, self.reg_classes, self.export_classes, self.rescale_classes = {}, {}, {}, {}
+
+    # ---- DepthPropagation.cpp:1403-1432: a running sum along each row, reset at every row (a per-row prefix sum, not a 2-D one)
+    def build_val_integral_buffer(self):
+        st = self.st
+        ymin, ymax = 3, self.H - 3                                   # util::YMIN, util::YMAX; the pointers start at row 3
+        contrib = np.where(st["valid"][ymin:ymax] != 0, st["validity"][ymin:ymax], 0).astype(np.int64)
+        self.validityIntegralBuffer[ymin:ymax] = np.cumsum(contrib, axis=1).astype(np.int32)
+
+    # ---- DepthPropagation.cpp:1317-1399
+    def fill_depth_holes(self):
+        W, H = self.W, self.H
+        self.build_val_integral_buffer()
+        cur = self.st
+        other = {k: np.array(v, copy=True) for k, v in cur.items()}          # memcpy(other, current)
+        y0, y1, x0, x1 = 3, H - 3, 3, W - 2                                  # y in [YMIN, YMAX), x in [3, ORIG_COLS - 2)
+        ys = slice(y0, y1); xs = slice(x0, x1)
+        io = self.validityIntegralBuffer.astype(np.int64)
+        sl = lambda dy, dx: (slice(y0 + dy, y1 + dy), slice(x0 + dx, x1 + dx))
+        val = io[sl(2, 2)] - io[sl(-3, 2)] - io[sl(2, -3)] + io[sl(-3, -3)]    # int arithmetic
+        was_valid = other["valid"][ys, xs] != 0
+        low_grad = F_arr(self.kf_maxgrad[ys, xs]) < MIN_ABS_GRAD_DECREASE
+        bl = other["blacklisted"][ys, xs]
+        valf = val.astype(np.float32)                                        # int compared with a float constant
+        create = (bl >= MIN_BLACKLIST) & (valf > VAL_SUM_MIN_FOR_CREATE)
+        accept = create | (valf > VAL_SUM_MIN_FOR_UNBLACKLIST)
+        evaluated = ~was_valid & ~low_grad
+        go = evaluated & accept
+        s_id = np.zeros(val.shape, np.float32)
+        s_iv = np.zeros(val.shape, np.float32)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            for dy in range(-2, 3):                                          # s1: rows y-2 .. y+2
+                for dx in range(-2, 3):                                      # source: columns x-2 .. x+2
+                    tv = other["valid"][sl(dy, dx)] != 0
+                    idp = other["invDepth"][sl(dy, dx)]
+                    var = other["variance"][sl(dy, dx)]
+                    s_id = _add_if(tv, s_id, idp / var)
+                    s_iv = _add_if(tv, s_iv, F(1.0) / var)
+            obs = unzero_planes(s_id / s_iv)
+        for k, v in (("invDepth", obs), ("variance", VAR_RANDOM_INIT_INITIAL), ("validity", 0), ("valid", 1), ("blacklisted", 0),
+                     ("invDepthSmoothed", -1), ("varianceSmoothed", -1)):
+            plane = cur[k][ys, xs]
+            plane[go] = v[go] if isinstance(v, np.ndarray) else v
+        rows = np.arange(y0, y1)[:, None] + np.zeros(val.shape, int)
+        cols = np.arange(x0, x1)[None, :] + np.zeros(val.shape, int)
+        band = np.zeros((H, W), bool)
+        band[:3] = band[-3:] = True
+        band[:, :3] = band[:, -3:] = True
+        near_band = np.zeros(val.shape, bool)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                near_band |= band[sl(dy, dx)] & (other["valid"][sl(dy, dx)] != 0)
+        self.fill_classes = {
+            "reject_valid": int(was_valid.sum()),
+            "reject_grad": int((~was_valid & low_grad).sum()),
+            "reject_val_le_30": int((evaluated & ~(valf > VAL_SUM_MIN_FOR_CREATE)).sum()),
+            "reject_blacklisted": int((evaluated & (valf > VAL_SUM_MIN_FOR_CREATE) & ~accept).sum()),
+            "create": int((go & create).sum()),
+            "unblacklist": int((go & ~create).sum()),
+            "negative_val": int((evaluated & (val < 0)).sum()),
+            "fill_rows_3_5": int((go & (rows <= 5)).sum()),
+            "fill_next_to_band_hypotheses": int((go & near_band).sum()),
+            "evaluated_rows_H5_H4": int((evaluated & (rows >= H - 5)).sum()),
+            "fill_rows_H5_H4": int((go & (rows >= H - 5)).sum()),
+            "fill_x_3": int((go & (cols == 3)).sum()),
+            "fill_x_W3": int((go & (cols == W - 3)).sum()),
+            "nan": int((go & np.isnan(obs)).sum()),
+        }
+
+    # ---- DepthPropagation.cpp:1436-1543, the loop nest as written: dx outer, dy inner
+    def regularize_depth_map(self, remove_occlusions=False):
+        W, H = self.W, self.H
+        cur = self.st
+        other = {k: np.array(v, copy=True) for k, v in cur.items()}          # memcpy(other, current): destRead / source
+        y0, y1, x0, x1 = 3, H - 3, 2, W - 2                                  # y in [YMIN, YMAX), x in [2, ORIG_COLS - 2)
+        ys = slice(y0, y1); xs = slice(x0, x1)
+        sl = lambda dy, dx: (slice(y0 + dy, y1 + dy), slice(x0 + dx, x1 + dx))
+        d_valid = other["valid"][ys, xs] != 0
+        d_id = other["invDepth"][ys, xs]
+        d_var = other["variance"][ys, xs]
+        shape = d_id.shape
+        s = np.zeros(shape, np.float32); val_sum = np.zeros(shape, np.float32); s_ivar = np.zeros(shape, np.float32)
+        n_occ = np.zeros(shape, np.int32); n_not = np.zeros(shape, np.int32)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            for dx in range(-2, 3):
+                for dy in range(-2, 3):
+                    tv = other["valid"][sl(dy, dx)] != 0
+                    s_id = other["invDepth"][sl(dy, dx)]
+                    s_var = other["variance"][sl(dy, dx)]
+                    diff = s_id - d_id
+                    inconsistent = DIFF_FAC_SMOOTHING * diff * diff > s_var + d_var
+                    if remove_occlusions:
+                        n_occ += (tv & inconsistent & (s_id > d_id)).astype(np.int32)
+                    take = tv & ~inconsistent
+                    val_sum = _add_if(take, val_sum, other["validity"][sl(dy, dx)].astype(np.float32))   # int += into a float
+                    if remove_occlusions:
+                        n_not += take.astype(np.int32)
+                    dist_fac = F(dx * dx + dy * dy) * REG_DIST_VAR
+                    ivar = F(1.0) / (s_var + dist_fac)
+                    s = _add_if(take, s, s_id * ivar)
+                    s_ivar = _add_if(take, s_ivar, ivar)
+            drop_bl = d_valid & (val_sum < F(int(VAL_SUM_MIN_FOR_KEEP)))      # int validityTH = 24.0f; float < int
+            drop_occ = d_valid & ~drop_bl & (n_occ > n_not) if remove_occlusions else np.zeros(shape, bool)
+            upd = d_valid & ~drop_bl & ~drop_occ
+            sm = unzero_planes(s / s_ivar)
+            vs = F(1.0) / s_ivar
+        v = cur["valid"][ys, xs]; v[drop_bl | drop_occ] = 0
+        b = cur["blacklisted"][ys, xs]; b[drop_bl] -= 1
+        p = cur["invDepthSmoothed"][ys, xs]; p[upd] = sm[upd]
+        p = cur["varianceSmoothed"][ys, xs]; p[upd] = vs[upd]
+        cols = np.arange(x0, x1)[None, :] + np.zeros(shape, int)
+        self.reg_classes = {
+            "smoothed": int(upd.sum()),
+            "dropped_blacklist": int(drop_bl.sum()),
+            "dropped_occluded": int(drop_occ.sum()),
+            "val_sum_24": int((d_valid & (val_sum == F(24))).sum()),
+            "tie": int((upd & (n_occ == n_not) & (n_occ > 0)).sum()) if remove_occlusions else 0,
+            "smoothed_x_2": int((upd & (cols == 2)).sum()),
+            "smoothed_x_W3": int((upd & (cols == W - 3)).sum()),
+            "nan_or_inf": int((upd & ~(np.isfinite(sm) & np.isfinite(vs) & (vs != 0))).sum()),
+        }
+
+    # ---- DepthPropagation.cpp:1627-1635, 1749-1756
+    def do_regularization(self, remove_occlusions=False):
+        self.fill_depth_holes()
+        self.regularize_depth_map(remove_occlusions)
+
+    def finalise_keyframe(self):
+        self.do_regularization()
+        self.update_depth_image()
+
+    # ---- DepthPropagation.cpp:1546-1587 (calculate_on_current): a serial f32 sum in raster order over every valid hypothesis (the
+    # 3-px band included). Returns this serial factor; scales with `factor` instead when one is given (the tests pass the GPU's).
+    def make_inv_depth_one(self, factor=None):
+        st = self.st
+        m = (st["valid"] != 0).ravel()
+        ids = st["invDepthSmoothed"].ravel()[m].astype(np.float32)
+        sumIdepth = np.add.accumulate(np.concatenate([np.zeros(1, np.float32), ids]), dtype=np.float32)[-1]
+        numIdepth = F(m.sum())                                   # numIdepth++ on a float: exact below 2^24
+        own = F(numIdepth / sumIdepth)
+        self.factor_serial = own
+        self.factor_f64_sum = numIdepth / F(math.fsum(ids.astype(np.float64)))     # f32(count) / f32(the exact sum, rounded once)
+        band = np.zeros(st["valid"].shape, bool)
+        band[:3] = band[-3:] = True
+        band[:, :3] = band[:, -3:] = True
+        self.rescale_classes = {"valid": int(m.sum()), "valid_in_band": int(((st["valid"] != 0) & band).sum())}
+        f = own if factor is None else F(factor)
+        f2 = f * f
+        v = st["valid"] != 0
+        for k, g in (("invDepth", f), ("invDepthSmoothed", f), ("variance", f2), ("varianceSmoothed", f2)):
+            st[k][v] = st[k][v] * g
+        return own
+
+    # ---- DepthPropagation.cpp:1254-1315
+    def update_depth_image(self):
+        W, H = self.W, self.H
+        st = self.st
+        band = np.zeros((H, W), bool)
+        band[:3] = band[-3:] = True
+        band[:, :3] = band[:, -3:] = True
+        cleared = int(((st["valid"] != 0) & band).sum())
+        st["valid"][band] = 0                                          # pt->isValid = false, in the map itself
+        ids = st["invDepthSmoothed"]
+        v = st["valid"] != 0
+        with np.errstate(invalid="ignore"):
+            ok = v & (ids >= F(-0.05))
+        with np.errstate(divide="ignore"):
+            inv = F(1) / ids                                             # 1 / float: int 1 promoted
+        self.depth_mat[0] = np.where(ok, inv, F(0.0)).astype(np.float32)
+        self.deptharr[0] = np.where(ok, inv, F(-1.0)).astype(np.float32)
+        self.depthvararr[0] = np.where(ok, st["varianceSmoothed"], F(-1.0)).astype(np.float32)
+        with np.errstate(invalid="ignore"):
+            self.export_classes = {
+                "band_cleared": cleared,
+                "ids_small_negative": int((v & (ids >= F(-0.05)) & (ids < 0)).sum()),
+                "ids_below": int((v & (ids < F(-0.05))).sum()),
+                "ids_minus_one": int((v & (ids == F(-1))).sum()),
+                "exported": int(ok.sum()),
+            }
+        self.build_inv_var_depth()
+        self.map_depth_arr2mat()
+
+    # ---- DepthPropagation.cpp:1637-1719. Each level reads the finer level's array with the stride 2 * width of ITS OWN width: when
+    # the finer level's width is odd (2 * width + 1) the rows drift. The reference has four levels (MAX_PYRAMID_LEVEL); for other level
+    # counts the same rule continues (level i from level i - 1, width ORIG_COLS >> i).
+    def build_inv_var_depth(self):
+        cells = {}
+        for i in range(1, self.levels):
+            width = self.W >> i
+            height = self.H >> i
+            sw = 2 * width
+            vsrc = self.depthvararr[i - 1].ravel()
+            dsrc = self.deptharr[i - 1].ravel()
+            yy, xx = np.meshgrid(np.arange(height), np.arange(width), indexing="ij")
+            idx = 2 * (xx + yy * sw)
+            ivs = np.zeros((height, width), np.float32)
+            ids = np.zeros((height, width), np.float32)
+            num = np.zeros((height, width), np.int32)
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                for off in (0, 1, sw, sw + 1):
+                    var = vsrc[idx + off]
+                    take = var > 0
+                    ivar = F(1.0) / var
+                    ivs = _add_if(take, ivs, ivar)
+                    ids = _add_if(take, ids, (ivar * F(1.0)) / dsrc[idx + off])    # `ivar * 1.0f/depthSource[..]`: (ivar * 1) / depth
+                    num += take.astype(np.int32)
+                depth = ivs / ids
+                vdest = num.astype(np.float32) / ivs                              # int / float
+            self.deptharr[i] = np.where(num > 0, depth, F(0.0)).astype(np.float32)
+            self.depthvararr[i] = np.where(num > 0, vdest, F(-1.0)).astype(np.float32)
+            cells[i] = np.bincount(num.ravel(), minlength=5)
+        self.export_classes["children"] = cells
+        self.export_classes["odd_source_width"] = [i for i in range(1, self.levels) if (self.W >> (i - 1)) & 1]
+
+    # ---- DepthPropagation.cpp:1722-1746: level 0 IS keyFrame->depth (cv::Mat assignment shares the data), the rest copy the arrays
+    def map_depth_arr2mat(self):
+        for i in range(1, self.levels):
+            self.depth_mat[i] = self.deptharr[i].copy()
+
+    # ---- DepthPropagation.cpp:1804-1830 (calculate_on_current): float count += float(isValid), serially; count / (cols * rows) * 100
+    def calculate_no_of_seeds(self):
+        v = (self.st["valid"] != 0).ravel().astype(np.float32)
+        count = np.add.accumulate(np.concatenate([np.zeros(1, np.float32), v]), dtype=np.float32)[-1]
+        return F(count / F(self.W * self.H)) * F(100)
+
+    # ---- DepthPropagation.cpp:1758-1794: propagate into the new keyframe, switch the keyframe (the fill reads ITS gradient), then
+    # regularise with occlusions, doRegularization(false), makeInvDepthOne, updateDepthImage(true). Returns the serial factor.
+    def create_keyframe(self, new_kf_image, new_kf_maxgrad, mats, factor=None):
+        self.propagate_depth(new_kf_image, new_kf_maxgrad, mats)
+        self.switch_keyframe(new_kf_image, new_kf_maxgrad)
+        return self.new_keyframe_stages(factor)
+
+    def new_keyframe_stages(self, factor=None):
+        """createKeyFrame after the switch (:1775-1781), on the propagated map this object holds"""
+        self.stage_classes = {}
+        self.regularize_depth_map(True)
+        self.stage_classes["regularize(true)"] = self.reg_classes
+        self.do_regularization(False)
+        self.stage_classes["fill"] = self.fill_classes
+        self.stage_classes["regularize(false)"] = self.reg_classes
+        f = self.make_inv_depth_one(factor)
+        self.update_depth_image()
+        return f
+
+    def switch_keyframe(self, new_kf_image, new_kf_maxgrad):
+        self.kf_image = new_kf_image
+        self.kf_gradx, self.kf_grady = calculate_gradient(new_kf_image)
+        self.kf_maxgrad = new_kf_maxgrad

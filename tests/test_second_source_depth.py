@@ -150,3 +150,286 @@ def test_gradient_planes_agree(oracle):
         gx, gy = f.gradient(0)
         gx2, gy2 = S2.calculate_gradient(img)
         assert np.array_equal(gx, gx2) and np.array_equal(gy, gy2)
+
+
+# ==================================================================================================================================
+# The stencil, rescale and export stages (DepthPropagation.cpp:1254-1830) against the second source's DepthMapStages, bit for bit:
+# flags at every pixel, values at valid pixels (assert_states_equal), the validity integral buffer, every level's depth / variance
+# array and depth Mat, the rescale factor and the seeds percentage. The scenes are built so that every branch class of every stage
+# occurs; the class counts are asserted (a scene that stops producing one fails).
+
+# (W, H, levels): 202 x 150 reads an odd source width at level 2 (101 wide), and with five levels also at level 4 (25 wide)
+STAGE_SIZES = [(64, 48, 4), (160, 120, 4), (202, 150, 4), (480, 270, 4), (64, 48, 3), (202, 150, 5)]
+size_id = lambda s: "%dx%d_L%d" % s
+
+
+def same_bits(a, b):
+    a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def _sites(rng, w, h, n, margin=8, spacing=12):
+    """n interior sites, far enough apart that their 9 x 9 neighbourhoods do not touch"""
+    out = []
+    for _ in range(50 * n):
+        y, x = int(rng.integers(margin, h - margin)), int(rng.integers(margin, w - margin))
+        if all(abs(y - a) >= spacing or abs(x - b) >= spacing for a, b in out):
+            out.append((y, x))
+        if len(out) == n:
+            break
+    return out
+
+
+def stencil_scene(oracle, w, h, levels, seed, plant_export=True, zero_var=False):
+    """A keyframe and a hypothesis map for the stencil / export stages: hypotheses in the 3-px band too (propagation puts them there
+    in the reference), validity counters up to 79, a quarter of the pixels blacklisted 0 .. -4, near (occluding) and far (occluded)
+    outliers, isolated hypotheses with validity exactly 24, occluder / non-occluder ties; for the export, smoothed inverse depths in
+    [-0.05, 0), below -0.05 and exactly -1; with zero_var, hypotheses whose variance is 0 (inf / NaN in the stencils)."""
+    rng = np.random.default_rng(seed)
+    pair = synth.make_pair(w, h, seed=seed, rot=0.004, trans=0.03)
+    fx, fy, cx, cy = pair["intrinsics"]
+    cfg = oracle.make_config(w, h, levels, fx, fy, cx, cy)
+    kf = oracle.Frame(cfg, pair["kf_image"], 1)
+    mg, _ = kf.max_gradient()
+    valid = (mg >= 5.0) & (rng.random((h, w)) < 0.5)
+    valid[:, [3, w - 3]] &= rng.random((h, 2)) < 0.35                   # holes in the fill's first and last column
+    idm = (pair["idepth_true"] * (1.0 + 0.03 * rng.normal(size=(h, w)))).astype(np.float32)
+    idm = np.where(rng.random((h, w)) < 0.03, idm * rng.uniform(1.6, 2.5, size=(h, w)), idm)
+    idm = np.where(rng.random((h, w)) < 0.03, idm * rng.uniform(0.3, 0.5, size=(h, w)), idm).astype(np.float32)
+    var = (0.01 * rng.uniform(0.5, 2.0, size=(h, w))).astype(np.float32)
+    st = dict(invDepth=np.where(valid, idm, 0).astype(np.float32), variance=np.where(valid, var, 0).astype(np.float32),
+              validity=np.where(valid, rng.integers(0, 80, size=(h, w)), 0).astype(np.int32),
+              blacklisted=np.where(rng.random((h, w)) < 0.25, -rng.integers(0, 5, size=(h, w)), 0).astype(np.int32),
+              valid=valid.astype(np.uint8))
+    sites = _sites(rng, w, h, 12)
+    for k, (y, x) in enumerate(sites):
+        win = (slice(y - 4, y + 5), slice(x - 4, x + 5))
+        st["valid"][win] = 0
+        st["valid"][y, x] = 1
+        st["invDepth"][y, x] = 1.0; st["variance"][y, x] = 0.01
+        if k % 2 == 0:
+            st["validity"][y, x] = 24                              # alone in its window: val_sum exactly 24, kept
+        else:
+            st["validity"][y, x] = 40                              # one closer, inconsistent neighbour: one occluding, one not
+            st["valid"][y, x + 1] = 1
+            st["invDepth"][y, x + 1] = 3.0; st["variance"][y, x + 1] = 0.01; st["validity"][y, x + 1] = 10
+    st["invDepthSmoothed"] = st["invDepth"].copy()
+    st["varianceSmoothed"] = st["variance"].copy()
+    ys, xs = np.nonzero(st["valid"][4:-4, 4:-4])
+    pick = rng.permutation(len(ys))
+    if plant_export:
+        for k, i in enumerate(pick[:max(12, len(ys) // 50)]):
+            y, x = ys[i] + 4, xs[i] + 4
+            st["invDepthSmoothed"][y, x] = (-0.01, -0.05, -0.2, -1.0)[k % 4]
+    if zero_var:
+        for i in pick[-max(4, len(ys) // 200):]:
+            st["variance"][ys[i] + 4, xs[i] + 4] = 0.0
+    return cfg, pair, kf, st
+
+
+def stages_of(cfg, pair, kf, st, levels):
+    fx, fy, cx, cy = pair["intrinsics"]
+    mg, _ = kf.max_gradient()
+    return S2.DepthMapStages(cfg.width, cfg.height, fx, fy, cx, cy, kf.kinv(), pair["kf_image"], mg, st, levels=levels)
+
+
+def oracle_map(oracle, cfg, kf, st):
+    dm = oracle.DepthMap(cfg)
+    dm.set_keyframe(kf)
+    dm.set_state(st)
+    return dm
+
+
+def assert_export_equal(dm, kf, s2, levels, what):
+    """every level: the arrays (level 0: -1 where invalid) and the keyframe's depth Mats (level 0: 0 where invalid)"""
+    for l in range(levels):
+        d, v = dm.pyr_level(l)
+        assert same_bits(d, s2.deptharr[l]), "%s: deptharr level %d" % (what, l)
+        assert same_bits(v, s2.depthvararr[l]), "%s: depthvararr level %d" % (what, l)
+        assert same_bits(kf.depth(l), s2.depth_mat[l]), "%s: depth Mat level %d" % (what, l)
+
+
+def require(classes, names, what):
+    missing = [n for n in names if not classes.get(n, 0)]
+    assert not missing, "%s: the scene no longer produces %r (%r)" % (what, missing, classes)
+
+
+FILL_CLASSES = ("reject_valid", "reject_grad", "reject_val_le_30", "reject_blacklisted", "create", "unblacklist", "negative_val",
+                "fill_rows_3_5", "fill_next_to_band_hypotheses", "evaluated_rows_H5_H4", "fill_x_3", "fill_x_W3")
+REG_CLASSES = ("smoothed", "dropped_blacklist", "val_sum_24", "smoothed_x_2", "smoothed_x_W3")
+REG_CLASSES_OCCL = REG_CLASSES + ("dropped_occluded", "tie")
+
+
+def check_fill_classes(c, what):
+    print("%s: fill classes %r" % (what, c))
+    require(c, FILL_CLASSES, what)
+    # rows H-5 and H-4 read rows H-3 / H-2 of the buffer, which buildValIntegralBuffer never writes (zero since the constructor):
+    # there val = -(window of row y - 3) <= 0, so no hole is ever filled in the last two rows of the fill's range
+    assert c["fill_rows_H5_H4"] == 0, c
+
+
+@pytest.mark.parametrize("size", STAGE_SIZES, ids=size_id)
+def test_fill_holes_agrees_with_the_second_source(oracle, size):
+    w, h, L = size
+    for zero_var in (False, True):
+        cfg, pair, kf, st = stencil_scene(oracle, w, h, L, 100 + w, zero_var=zero_var)
+        dm = oracle_map(oracle, cfg, kf, st)
+        dm.fill_holes()
+        s2 = stages_of(cfg, pair, kf, st, L)
+        s2.fill_depth_holes()
+        what = "fillDepthHoles %dx%d%s" % (w, h, " zero variances" if zero_var else "")
+        assert np.array_equal(dm.integral(), s2.validityIntegralBuffer), what + ": validityIntegralBuffer"
+        assert_states_equal(dm.get_state(), s2.st, what)
+        check_fill_classes(s2.fill_classes, what)
+        if zero_var:
+            assert s2.fill_classes["nan"] > 0, s2.fill_classes
+
+
+@pytest.mark.parametrize("remove_occlusions", [False, True])
+@pytest.mark.parametrize("size", STAGE_SIZES, ids=size_id)
+def test_regularize_agrees_with_the_second_source(oracle, size, remove_occlusions):
+    w, h, L = size
+    for zero_var in (False, True):
+        cfg, pair, kf, st = stencil_scene(oracle, w, h, L, 200 + w, zero_var=zero_var)
+        dm = oracle_map(oracle, cfg, kf, st)
+        dm.regularize(remove_occlusions)
+        s2 = stages_of(cfg, pair, kf, st, L)
+        s2.regularize_depth_map(remove_occlusions)
+        what = "regularizeDepthMap(%s) %dx%d%s" % (remove_occlusions, w, h, " zero variances" if zero_var else "")
+        assert_states_equal(dm.get_state(), s2.st, what)
+        print("%s: %r" % (what, s2.reg_classes))
+        require(s2.reg_classes, REG_CLASSES_OCCL if remove_occlusions else REG_CLASSES, what)
+        if zero_var:
+            assert s2.reg_classes["nan_or_inf"] > 0, s2.reg_classes
+
+
+@pytest.mark.parametrize("remove_occlusions", [False, True])
+@pytest.mark.parametrize("size", STAGE_SIZES, ids=size_id)
+def test_do_regularization_agrees_with_the_second_source(oracle, size, remove_occlusions):
+    w, h, L = size
+    cfg, pair, kf, st = stencil_scene(oracle, w, h, L, 300 + w)
+    dm = oracle_map(oracle, cfg, kf, st)
+    dm.fill_holes(); dm.regularize(remove_occlusions)                   # doRegularization(removeOcclusions), :1627-1635
+    s2 = stages_of(cfg, pair, kf, st, L)
+    s2.do_regularization(remove_occlusions)
+    what = "doRegularization(%s) %dx%d" % (remove_occlusions, w, h)
+    assert_states_equal(dm.get_state(), s2.st, what)
+    check_fill_classes(s2.fill_classes, what)
+    print("%s: %r" % (what, s2.reg_classes))
+    require(s2.reg_classes, REG_CLASSES_OCCL if remove_occlusions else REG_CLASSES, what)
+
+
+@pytest.mark.parametrize("size", STAGE_SIZES, ids=size_id)
+def test_update_depth_image_and_seeds_agree_with_the_second_source(oracle, size):
+    """updateDepthImage alone (border band cleared in the map, the export's three branches, every level and both level-0 forms),
+    then calculate_no_of_Seeds with ==, on the planted scene and on the same scene after a doRegularization."""
+    w, h, L = size
+    for regularised in (False, True):
+        cfg, pair, kf, st = stencil_scene(oracle, w, h, L, 400 + w)
+        dm = oracle_map(oracle, cfg, kf, st)
+        s2 = stages_of(cfg, pair, kf, st, L)
+        if regularised:
+            dm.fill_holes(); dm.regularize(False); s2.do_regularization()
+        dm.update_depth_image()
+        s2.update_depth_image()
+        what = "updateDepthImage %dx%d L%d%s" % (w, h, L, " after doRegularization" if regularised else "")
+        assert_states_equal(dm.get_state(), s2.st, what)
+        assert_export_equal(dm, kf, s2, L, what)
+        assert dm.seeds() == s2.calculate_no_of_seeds(), what
+        c = s2.export_classes
+        print("%s: %r" % (what, c))
+        require(c, ("band_cleared", "exported") + (() if regularised else ("ids_small_negative", "ids_below", "ids_minus_one")), what)
+        for l, n in c["children"].items():
+            if (w >> l) >= 8 and not regularised:
+                assert (n > 0).all(), (what, l, n)                 # 2 x 2 cells with 0, 1, 2, 3 and 4 valid children
+        if w == 202:
+            assert 2 in c["odd_source_width"] and (L < 5 or 4 in c["odd_source_width"]), c["odd_source_width"]
+
+
+@pytest.mark.parametrize("size", STAGE_SIZES[:4], ids=size_id)
+def test_make_inv_depth_one_agrees_with_the_second_source(oracle, size):
+    """makeInvDepthOne(true): the serial f32 factor == the oracle's, every field after the rescale; hypotheses in the 3-px band
+    (left there by propagation in the reference) are part of the sum. Prints how far the f64 sum's factor lies."""
+    w, h, L = size
+    cfg, pair, kf, st = stencil_scene(oracle, w, h, L, 500 + w, plant_export=False)
+    dm = oracle_map(oracle, cfg, kf, st)
+    dm.regularize(False)
+    s2 = stages_of(cfg, pair, kf, st, L)
+    s2.regularize_depth_map(False)
+    f_ref = dm.make_inv_depth_one()
+    f = s2.make_inv_depth_one()
+    rel = abs(float(s2.factor_f64_sum) / float(f) - 1)
+    print("makeInvDepthOne %dx%d: serial f32 factor %r, f32(count) / f32(f64 sum) %r (%.2e relative), %r" % (
+        w, h, f, s2.factor_f64_sum, rel, s2.rescale_classes))
+    assert np.float32(f_ref) == f
+    assert_states_equal(dm.get_state(), s2.st, "makeInvDepthOne %dx%d" % (w, h))
+    require(s2.rescale_classes, ("valid", "valid_in_band"), "makeInvDepthOne")
+    assert rel < 5e-5
+
+
+@pytest.mark.parametrize("size", STAGE_SIZES[:3], ids=size_id)
+def test_finalise_keyframe_agrees_with_the_second_source(oracle, size):
+    w, h, L = size
+    cfg, pair, kf, st = stencil_scene(oracle, w, h, L, 600 + w)
+    dm = oracle_map(oracle, cfg, kf, st)
+    dm.fill_holes(); dm.regularize(False); dm.update_depth_image()       # finaliseKeyframe, :1749-1756
+    s2 = stages_of(cfg, pair, kf, st, L)
+    s2.finalise_keyframe()
+    assert_states_equal(dm.get_state(), s2.st, "finaliseKeyframe")
+    assert_export_equal(dm, kf, s2, L, "finaliseKeyframe")
+
+
+@pytest.mark.parametrize("size,seed,trans", [((64, 48), 11, 0.05), ((160, 120), 12, 0.035)])
+def test_tracked_frame_tail_agrees_with_the_second_source(oracle, size, seed, trans):
+    """main.cpp:500-502: observeDepthRowParallel, doRegularization(), updateDepthImage()"""
+    w, h = size
+    cfg, pair, kf, cur, st = scene(oracle, w, h, seed, trans, degenerate=False)
+    dm = oracle.DepthMap(cfg)
+    dm.set_keyframe(kf); dm.set_current(cur); dm.set_state(st)
+    dm.observe(); dm.fill_holes(); dm.regularize(False); dm.update_depth_image()
+    s2 = stages_of(cfg, pair, kf, st, 3)
+    s2.set_current(pair["cur_image"], cur.calc_se3(kf))
+    s2.observe_depth_row(3, h - 3)
+    s2.do_regularization()
+    s2.update_depth_image()
+    what = "observe + doRegularization + updateDepthImage %dx%d" % size
+    assert_states_equal(dm.get_state(), s2.st, what)
+    assert_export_equal(dm, kf, s2, 3, what)
+    assert dm.seeds() == s2.calculate_no_of_seeds()
+    print("%s: fill %r, regularise %r" % (what, s2.fill_classes, s2.reg_classes))
+    require(s2.fill_classes, ("create", "reject_val_le_30"), what)
+    require(s2.reg_classes, ("smoothed", "dropped_blacklist"), what)
+
+
+@pytest.mark.parametrize("size", [(64, 48, 3), (160, 120, 4), (202, 150, 4), (480, 270, 4), (160, 120, 5)], ids=size_id)
+def test_create_keyframe_agrees_with_the_second_source(oracle, size):
+    """createKeyFrame (:1758-1794): propagate into the new keyframe, the keyframe switch, regularise with occlusions,
+    doRegularization(false), makeInvDepthOne, updateDepthImage — the factor, every field and every level, bit for bit"""
+    w, h, L = size
+    cfg, pair, kf, st = stencil_scene(oracle, w, h, L, 700 + w, plant_export=False)
+    cur = oracle.Frame(cfg, pair["cur_image"], 2)
+    cur.set_pose(origin=pair["xi_true"])
+    mats = cur.calc_se3(kf)                                              # before createKeyFrame zeroes the new keyframe's pose
+    mg_new, _ = cur.max_gradient()
+    dm = oracle_map(oracle, cfg, kf, st)
+    dm.create_keyframe(cur)
+    s2 = stages_of(cfg, pair, kf, st, L)
+    f = s2.create_keyframe(pair["cur_image"], mg_new, mats)
+    what = "createKeyFrame %dx%d L%d" % size
+    assert np.float32(cur.rescale_factor()) == f, (what, cur.rescale_factor(), f)
+    assert_states_equal(dm.get_state(), s2.st, what)
+    assert_export_equal(dm, cur, s2, L, what)
+    for k, c in s2.stage_classes.items():
+        print("%s: %s %r" % (what, k, c))
+    print("%s: rescale %r, export %r" % (what, s2.rescale_classes, s2.export_classes))
+    # (the occlusion drop and the tie need outliers that survive propagation: the per-stage tests above hold those branches)
+    require(s2.stage_classes["regularize(true)"], ("smoothed",) + (("dropped_blacklist",) if w > 64 else ()), what)
+    require(s2.stage_classes["fill"], ("create", "reject_val_le_30", "reject_valid"), what)
+    require(s2.rescale_classes, ("valid_in_band",), what)
+    require(s2.export_classes, ("band_cleared", "exported"), what)
+
+
+def test_unzero_planes_is_unzero():
+    v = np.array([0.0, -0.0, 1e-11, -1e-11, 1e-10, -1e-10, 2e-10, -2e-10, 1.0, -1.0, np.inf, -np.inf, np.nan, 9.99999e-11,
+                  np.float32(1e-10), -np.float32(1e-10)], np.float32)
+    assert same_bits(S2.unzero_planes(v), np.array([S2.unzero(x) for x in v], np.float32))
