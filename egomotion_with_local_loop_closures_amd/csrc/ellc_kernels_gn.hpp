@@ -1512,15 +1512,11 @@ struct FusedArgs {
   int early_exit;
   int stride_state;     // elements between the two AlignState buffers
   size_t stride_part;   // floats between the two partial buffers
-  // Age-balanced split (0 = off). When the grid is R full rounds of resident blocks, the blocks dispatched first share
-  // their SIMDs with younger ones and are served first (oldest-wave-first arbitration), so with equal chunks the launch
-  // waits for the youngest round (measured: pixel phases of 15 / 17 / 20 / 23 us for rounds 0..3 of an equal split).
-  // With age_rounds = R every alignment gets nblk / R blocks in each round and round q is given the share
-  // (age_cum[q+1] - age_cum[q]) / 65536 of the alignment's pixels. The mapping only assumes that blocks are dispatched
-  // in linear order; if that were not so the result is unchanged (the split is static) and only the balance is lost.
+  // Age-balanced split (0 = off, see block_map): with age_rounds = R round q is given the share (age_cum[q+1] - age_cum[q]) / 65536
+  // of the alignment's pixels.
   int age_rounds;
   int age_cum[5];
-  int xcd_map;          // 1: blocks are renumbered so that all blocks of an alignment run on one XCD (see gn_fca_fused)
+  int xcd_map;          // 1: blocks are renumbered so that all blocks of an alignment run on one XCD (see block_map)
   AlignResult* res;     // gn_fused_finish: host-visible result records (null: none)
   int ica;              // 1: constant-weight schedule (gn_ica_fused): the pending sums are b only, H^-1 comes from the keyframe slot
   // state-driven schedule (gn_fca_adaptive): blocks and iteration caps per level, the grid's x extent
@@ -1537,6 +1533,210 @@ struct FusedArgs {
   int continuation;     // 1: this graph continues a state-driven schedule whose first graph has already run (and added the saved weights
                         // of the alignments that ended there): its first launch marks those records cur_level = -2
 };
+
+// ---------------------------------------------------------------------------------------------------
+// What the kernels of a schedule share around their pixel passes: which alignment and chunk a block is, the double buffers'
+// addresses, the advance of the state record, the first record's request and the walk over a plane. Everything here that is
+// block-uniform stays provably so (kernel arguments and readfirstlane in, structs by value out of force-inlined functions:
+// nothing that could put a slot or a level into a vector register, NOTEBOOK 6.4).
+
+// The double buffers by launch parity (see above): launch n writes state[(n+1)&1] and partials[n&1]; the sums launch n - 1
+// left for it are in partials[(n+1)&1]. (gn_fca_persist: n is the round.)
+__device__ __forceinline__ AlignState* next_state(const FusedArgs& fa, int b) { return fa.g.state + (size_t)((fa.seq + 1) & 1) * fa.stride_state + b; }
+__device__ __forceinline__ float* partial_record(const FusedArgs& fa, int seq, int b, int sub) {
+  return fa.g.partials + (size_t)(seq & 1) * fa.stride_part + ((size_t)b * ELLC_NBLK_MAX + sub) * ELLC_PART_STRIDE;
+}
+__device__ __forceinline__ const float* pending_partials(const FusedArgs& fa, int seq, int b) { return partial_record(fa, seq + 1, b, 0); }
+// (the same from the pending buffer's address, which the launch-per-iteration kernels get as a preloaded argument)
+__device__ __forceinline__ const float* pending_partials(const float* prev_part, int b) { return prev_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE; }
+
+// Which alignment and which of its chunks a block of a schedule launch is, and that chunk of V elements.
+struct Chunk { int begin, end; };
+struct BlockMap {
+  int b, sub;            // alignment, chunk
+  int rounds;            // age-balanced split: the launch's rounds (<= 1: even split)
+  int age, per_age;      //   the round this block is dispatched in, the alignment's blocks in each round
+  // contiguous chunk per block (keeps a block's taps in a few image rows: 25 % less fetch traffic than a tile-cyclic
+  // split, which was tried in r01 and did not change the run time — co-resident blocks finish staggered because the
+  // SIMD arbiter serves the oldest wave first, not because their pixels differ)
+  __device__ __forceinline__ Chunk chunk(const int (&age_cum)[5], int V, int nblk) const {
+    Chunk c;
+    if (rounds > 1) {
+      const int gb = (int)(((long long)V * age_cum[age]) >> 16), ge = (int)(((long long)V * age_cum[age + 1]) >> 16);
+      const int n = (ge - gb + per_age - 1) / per_age;
+      c.begin = gb + (sub - age * per_age) * n;
+      c.end = min(ge, c.begin + n);
+    } else {
+      const int n = (V + nblk - 1) / nblk;
+      c.begin = sub * n;
+      c.end = min(V, c.begin + n);
+    }
+    return c;
+  }
+};
+// nblk: blocks per alignment of the grid (its x extent). Both relabellings are pure renamings of (alignment, chunk) and only
+// assume that blocks are dispatched in linear order: if that were not so the result is unchanged (the split is static) and
+// only the balance, or the locality, is lost.
+__device__ __forceinline__ BlockMap block_map(int nblk, int age_rounds, int xcd_map) {
+  BlockMap m = {(int)blockIdx.y, (int)blockIdx.x, age_rounds, 0, nblk};
+  if (age_rounds > 1) {
+    // Age-balanced split. When the grid is R full rounds of resident blocks, the blocks dispatched first share their SIMDs
+    // with younger ones and are served first (oldest-wave-first arbitration), so with equal chunks the launch waits for the
+    // youngest round (measured: pixel phases of 15 / 17 / 20 / 23 us for rounds 0..3 of an equal split). With age_rounds = R
+    // every alignment gets nblk / R blocks in each round and round q is given the share (age_cum[q+1] - age_cum[q]) / 65536
+    // of the alignment's pixels (FusedArgs).
+    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+    const int per_round = (int)(gridDim.x * gridDim.y) / age_rounds;
+    m.per_age = nblk / age_rounds;
+    m.age = lin / per_round;
+    const int j = lin - m.age * per_round;
+    m.b = j / m.per_age;
+    m.sub = m.age * m.per_age + (j - m.b * m.per_age);
+  } else if (xcd_map) {
+    // Workgroups are dealt round-robin over the 8 XCDs in dispatch order, each XCD with an L2 of its own. Renumbered so that
+    // alignment b's blocks are the linear ids congruent to b mod 8, all of an alignment's taps (and its record list) go
+    // through ONE L2: with a frame per alignment (1280x960: 1.2 MB each) every XCD otherwise pulls every image.
+    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+    const int w = lin >> 3, bl = w / nblk;
+    m.sub = w - bl * nblk;
+    m.b = bl * 8 + (lin & 7);
+  }
+  return m;
+}
+
+// The pose of this launch into `sh` (new pose, exp(new pose), weightedPose, level_done), for every thread: the record's, when no
+// sums are pending ...
+__device__ __forceinline__ void carry_pose(SolveShared& sh, const AlignState& src) {
+  const int t = threadIdx.x;
+  if (t < 6) sh.newpose[t] = src.pose[t];
+  if (t < 12) sh.newS[t] = src.S[t];
+  if (t == 0) { sh.weighted = src.weighted; sh.level_done = src.level_done; }
+  __syncthreads();
+}
+// ... else the solve of the pending sums of `level` (every block of the alignment redoes it). H, b, delta and H^-1 of the state
+// record serve the single-step API only, which runs gn_solve: not stored here. hinv_at: mode 2, where the pointer to the level's
+// H^-1 stands (the keyframe slot's table entry) — read only when there is something to solve.
+template <bool FAST>
+__device__ __forceinline__ void advance_pose(SolveShared& sh, int pending, double group_sum, int mode, int level, int early_exit, const AlignState& src,
+                                             const float* const* hinv_at = nullptr) {
+  if (pending) solve_step<FAST>(sh, group_sum, mode, level, early_exit, src, nullptr, hinv_at ? *hinv_at : nullptr);
+  else carry_pose(sh, src);
+}
+// The next state record of a launch that is bound to `level` (writer: the alignment's first block stores it); true when that
+// level has already ended for this alignment: the launch has nothing to do.
+__device__ __forceinline__ bool publish_level_bound(const SolveShared& sh, const AlignState& src, AlignState* dst, bool writer, int pending, int prev_level,
+                                                    int level) {
+  const int t = threadIdx.x;
+  const int level_done = sh.level_done;
+  const bool skip = (level_done == level);
+  if (writer) {
+    if (t < 6) dst->pose[t] = sh.newpose[t];
+    if (t < 12) dst->S[t] = sh.newS[t];
+    if (t < ELLC_MAX_LEVELS) dst->iters[t] = src.iters[t] + ((pending && t == prev_level) ? 1 : 0);
+    if (t == 0) {
+      dst->weighted = sh.weighted;
+      dst->level_done = level_done;
+      dst->pending = skip ? 0 : 1;
+    }
+  }
+  return skip;
+}
+// State-driven schedules: what the solve of the sums of level `lvl` (iteration it_in of that level) means for the record.
+struct LevelStep {
+  bool over;   // the level has ended: early exit, or its cap
+  int nl;      // the level of the pixel pass that follows (-1: the schedule has ended)
+  int it;      // iterations done at that level
+};
+__device__ __forceinline__ LevelStep level_step(const SolveShared& sh, const FusedArgs& fa, int pending, int lvl, int it_in) {
+  const int it = it_in + (pending ? 1 : 0);
+  LevelStep s;
+  s.over = pending && (sh.level_done == lvl || it >= fa.max_it[lvl]);
+  s.nl = s.over ? lvl - 1 : lvl;
+  s.it = s.over ? 0 : it;
+  return s;
+}
+// Thread t's first record of the chunk (exact mode: together with its pose-independent products), requested before the solve so
+// that it arrives while the solve runs. takes_part: block-uniform, false for a block that only solves (state-driven schedules).
+// Tolerance mode: a thread past the chunk's end starts on a copy of its last record (the pixel loop is block-uniform).
+// PIN: the exact mode's products are pinned where they stand — in front of a solve the compiler would otherwise sink the
+// arithmetic below it, onto the critical path. Not set for a level change (the solve is over). gn_fca_persist never had the
+// pin and is left as it was measured: with the pin its exact build keeps its 240 registers and only its schedule moves.
+struct FirstRec { FcaIn in; FcaInF inf; FcaPre pre; };
+__device__ __forceinline__ FirstRec no_record() { return FirstRec{fca_in_empty(), fcaf_empty(), FcaPre{}}; }
+template <bool DIVC, bool FAST, bool PIN>
+__device__ __forceinline__ void request_first(FirstRec& r, const KfLevelDev& K, const LevelGeom& g, const Chunk& c, int t, bool takes_part) {
+  if constexpr (FAST) {
+    if (takes_part && c.begin < c.end) r.inf = fcaf_load(K, (unsigned)min(c.begin + t, c.end - 1));
+  } else {
+    if (takes_part && c.begin + t < c.end) r.in = fca_load<DIVC>(K, g, (unsigned)(c.begin + t));
+    r.pre = fca_prepare<DIVC>(g, r.in);
+    if constexpr (PIN)
+      asm volatile("" ::"v"(r.pre.c_t0), "v"(r.pre.c_b1), "v"(r.pre.d), "v"(r.pre.fxz), "v"(r.pre.fyz), "v"(r.pre.nvz), "v"(r.pre.nuz));
+  }
+}
+// State-driven schedules: what a block works with at level `lvl` — the level's tables, its block count and the block's chunk of
+// the list. Read with the state record's arrival and again at a level change (at most L - 1 per alignment).
+struct LevelWork {
+  LevelGeom g;
+  KfLevelDev K;
+  const FrLevelDev* F;
+  int nb;
+  Chunk c;
+};
+__device__ __forceinline__ LevelWork level_work(const FusedArgs& fa, const BlockMap& m, int lvl, int slot, int frs) {
+  const GnArgs& a = fa.g;
+  LevelWork w;
+  w.nb = fa.nblk_lv[lvl];
+  w.g = a.geom[lvl];
+  w.K = a.kf_tab[lvl * a.max_kf + slot];
+  w.F = &a.fr_tab[lvl * a.max_fr + frs];
+  w.c = m.chunk(fa.age_cum, *as_global(w.K.count), w.nb);
+  return w;
+}
+
+// The block-uniform trip count of a pixel loop over [begin, end), thread t taking begin + t, begin + t + 256, ...: every thread
+// has n_full elements, the first `rem` threads one more; a thread without one in the last step runs it without accumulating.
+struct TripCount {
+  int n_full, rem, n_steps;
+  __device__ __forceinline__ bool active(int k) const { return k != n_steps - 1 || rem == 0 || (int)threadIdx.x < rem; }
+};
+__device__ __forceinline__ TripCount trip_count(int begin, int end) {
+  TripCount tc;
+  tc.n_full = __builtin_amdgcn_readfirstlane((end - begin) / ELLC_GN_THREADS);
+  tc.rem = __builtin_amdgcn_readfirstlane((end - begin) - tc.n_full * ELLC_GN_THREADS);
+  tc.n_steps = tc.n_full + (tc.rem > 0 ? 1 : 0);
+  return tc;
+}
+
+// The walk of a thread over its block's chunk of a PLANE of `cols` elements a row (pixels, or quads: gn_fca_dense4).
+__device__ __forceinline__ void plane_xy(int i, int cols, int& x, int& y) {
+  y = (int)(((float)i + 0.5f) * (1.0f / (float)cols));   // i < 2^24: exact conversion; corrected to the exact quotient
+  if (y * cols > i) y--;
+  if ((y + 1) * cols <= i) y++;
+  x = i - y * cols;
+}
+struct PlaneWalk { int cols, qstep, rstep; };   // a step advances a thread by 256 elements: qstep rows and rstep columns
+struct PlanePos { int i, x, y; };               // i runs on past the chunk's end; (x, y) is the position of min(i, end - 1)
+__device__ __forceinline__ PlaneWalk plane_walk(int cols) {
+  PlaneWalk w;
+  w.cols = cols;
+  w.qstep = ELLC_GN_THREADS / cols;
+  w.rstep = ELLC_GN_THREADS - w.qstep * cols;
+  return w;
+}
+// (a thread past the chunk's end starts on a copy of its last element: the loops are block-uniform)
+__device__ __forceinline__ PlanePos plane_first(const PlaneWalk& w, const Chunk& c, int t) {
+  PlanePos p = {c.begin + t, 0, 0};
+  if (c.begin < c.end) plane_xy(min(p.i, c.end - 1), w.cols, p.x, p.y);   // block-uniform
+  return p;
+}
+// the next element of this thread: 256 further on (clamped to the chunk's last element: every request is unconditional)
+__device__ __forceinline__ PlanePos plane_next(const PlaneWalk& w, const PlanePos& p, int last) {
+  PlanePos n = {p.i + ELLC_GN_THREADS, p.x + w.rstep, p.y + w.qstep};
+  if (n.x >= w.cols) { n.x -= w.cols; n.y++; }
+  if (n.i > last) plane_xy(last, w.cols, n.x, n.y);
+  return n;
+}
 
 // The pixel pass of one block of a fused launch over its chunk [begin, end) of the compact list, thread t taking the
 // entries begin + t, begin + t + 256, ...; the thread's first record (and, in the exact mode, its pose-independent products)
@@ -1567,12 +1767,9 @@ __device__ __forceinline__ void fca_chunk_pass(const GnArgs& a, const KfLevelDev
       unsigned off = (unsigned)i * ELLC_FREC, idx = (unsigned)i;
       const unsigned off_last = (unsigned)(end - 1) * ELLC_FREC;
       constexpr unsigned S16 = stride * ELLC_FREC;
-      const int n_full = __builtin_amdgcn_readfirstlane((end - begin) / stride);
-      const int rem = __builtin_amdgcn_readfirstlane((end - begin) - n_full * stride);
-      const int n_steps = n_full + (rem > 0 ? 1 : 0);
+      const TripCount tc = trip_count(begin, end);
       FcaInF r0 = firstf, r1 = firstf;
-      auto step = [&](const FcaInF& cur_rec, FcaInF& next_rec, bool last) {
-        const bool active = !last || rem == 0 || t < rem;
+      auto step = [&](const FcaInF& cur_rec, FcaInF& next_rec, bool active) {
         auto refill = [&]() { next_rec = fcaf_load_off(K, min(off + S16, off_last)); };
         const FcafStage st = fcaf_stage_a(g, tr, fc, cur_rec, refill);
         ELLC_PTRACE(5, 0);
@@ -1580,10 +1777,10 @@ __device__ __forceinline__ void fca_chunk_pass(const GnArgs& a, const KfLevelDev
         ELLC_PTRACE(6, 0);
         off += S16; idx += stride;
       };
-      for (int k = 0; k < n_steps; k += 2) {
-        step(r0, r1, k == n_steps - 1);
-        if (k + 1 >= n_steps) break;   // block-uniform
-        step(r1, r0, k + 1 == n_steps - 1);
+      for (int k = 0; k < tc.n_steps; k += 2) {
+        step(r0, r1, tc.active(k));
+        if (k + 1 >= tc.n_steps) break;   // block-uniform
+        step(r1, r0, tc.active(k + 1));
       }
     }
   } else if (i < end) {
@@ -1627,30 +1824,11 @@ template <bool DIVC, bool PIPE, bool FAST = false, int SAVEW = -1>   // SAVEW: s
 __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_fused(const AlignState* src_state, const float* prev_part, int prev_nblk,
                                                                    int nblk, int age_rounds, FusedArgs fa) {   // 4 waves per SIMD: at most 128 VGPRs
   const GnArgs& a = fa.g;
-  int b = blockIdx.y, sub = blockIdx.x, age = 0, per_age = nblk;
-  if (age_rounds > 1) {
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int per_round = (int)(gridDim.x * gridDim.y) / age_rounds;
-    per_age = nblk / age_rounds;          // blocks of one alignment in each round
-    age = lin / per_round;
-    const int j = lin - age * per_round;
-    b = j / per_age;
-    sub = age * per_age + (j - b * per_age);
-  } else if (fa.xcd_map) {
-    // Workgroups are dealt round-robin over the 8 XCDs in dispatch order, each XCD with an L2 of its own. Renumbered so that
-    // alignment b's blocks are the linear ids congruent to b mod 8, all of an alignment's taps (and its record list) go
-    // through ONE L2: with a frame per alignment (1280x960: 1.2 MB each) every XCD otherwise pulls every image. Pure
-    // relabelling of (alignment, chunk): results unchanged; a different dispatch order would only lose the locality.
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int w = lin >> 3, bl = w / nblk;
-    sub = w - bl * nblk;
-    b = bl * 8 + (lin & 7);
-  }
+  const BlockMap m = block_map(nblk, age_rounds, fa.xcd_map);
+  const int b = m.b, sub = m.sub;
   const AlignState& src = src_state[b];
-  AlignState* dst = a.state + (size_t)((fa.seq + 1) & 1) * fa.stride_state + b;
   __shared__ SolveShared sh;
   const int t = threadIdx.x;
-  const bool writer = (sub == 0);
   ELLC_STAMP(0);
   ELLC_BSTAMP(0);
   ELLC_SEQSTAMP(0, fa.seq);
@@ -1658,73 +1836,26 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_fused(const AlignSt
   // entries): the scalar chain slot -> table entry -> count is started first, the pending partial sums are read
   // unconditionally next (prev_nblk is 0 on the first launch of a schedule) so that they share one memory round trip
   // with the chain and the state record, and this thread's first compact pixel is requested last, to arrive while
-  // the solve runs. None of it depends on the pose.
+  // the solve runs. None of it depends on the pose. (Every kernel of a schedule keeps this order.)
   const LevelGeom g = a.geom[a.level];
   const KfLevelDev K = a.kf_tab[a.level * a.max_kf + a.kf_slot[b]];   // by value: uniform, lives in SGPRs
   const FrLevelDev& F = a.fr_tab[a.level * a.max_fr + a.fr_slot[b]];
   const int pending = src.pending;
   const int V = *as_global(K.count);
-  const double group_sum = partial_group_sum(prev_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE, prev_nblk);
-  // contiguous chunk per block (keeps a block's taps in a few image rows: 25 % less fetch traffic than a tile-cyclic
-  // split, which was tried in r01 and did not change the run time — co-resident blocks finish staggered because the
-  // SIMD arbiter serves the oldest wave first, not because their pixels differ)
-  int begin, end;
-  if (age_rounds > 1) {
-    const int gb = (int)(((long long)V * fa.age_cum[age]) >> 16), ge = (int)(((long long)V * fa.age_cum[age + 1]) >> 16);
-    const int chunk = (ge - gb + per_age - 1) / per_age;
-    begin = gb + (sub - age * per_age) * chunk;
-    end = min(ge, begin + chunk);
-  } else {
-    const int chunk = (V + nblk - 1) / nblk;
-    begin = sub * chunk;
-    end = min(V, begin + chunk);
-  }
+  const double group_sum = partial_group_sum(pending_partials(prev_part, b), prev_nblk);
+  const Chunk c = m.chunk(fa.age_cum, V, nblk);
   g_u8 cur = as_global(F.img);
-  // this thread's first compact pixel, requested before the solve (exact mode: together with its pose-independent products)
-  FcaIn first = fca_in_empty();
-  FcaInF firstf = fcaf_empty();
-  FcaPre first_pre;
-  if constexpr (FAST) {
-    if (begin < end) firstf = fcaf_load(K, (unsigned)min(begin + t, end - 1));   // (a thread past the chunk's end starts on a copy of its last record: the pixel loop is block-uniform)
-  } else {
-    if (begin + t < end) {
-      first = fca_load<DIVC>(K, g, (unsigned)(begin + t));
-    }
-    first_pre = fca_prepare<DIVC>(g, first);
-    // pin the arithmetic here (the compiler would otherwise sink it below the solve, onto the critical path)
-    asm volatile("" ::"v"(first_pre.c_t0), "v"(first_pre.c_b1), "v"(first_pre.d), "v"(first_pre.fxz), "v"(first_pre.fyz),
-                 "v"(first_pre.nvz), "v"(first_pre.nuz));
-  }
-  if (pending) {
-    // (H, b, delta and H^-1 of the state record serve the single-step API only, which runs gn_solve: not stored here)
-    solve_step<FAST>(sh, group_sum, 0, fa.prev_level, fa.early_exit, src, nullptr);
-  } else {
-    if (t < 6) sh.newpose[t] = src.pose[t];
-    if (t < 12) sh.newS[t] = src.S[t];
-    if (t == 0) { sh.weighted = src.weighted; sh.level_done = src.level_done; }
-    __syncthreads();
-  }
+  FirstRec first = no_record();
+  request_first<DIVC, FAST, true>(first, K, g, c, t, true);
+  advance_pose<FAST>(sh, pending, group_sum, 0, fa.prev_level, fa.early_exit, src);
   ELLC_STAMP(6);
   ELLC_BSTAMP(1);
-  const int level_done = sh.level_done;
-  const bool skip = (level_done == a.level);
-  if (writer) {
-    if (t < 6) dst->pose[t] = sh.newpose[t];
-    if (t < 12) dst->S[t] = sh.newS[t];
-    if (t < ELLC_MAX_LEVELS) dst->iters[t] = src.iters[t] + ((pending && t == fa.prev_level) ? 1 : 0);
-    if (t == 0) {
-      dst->weighted = sh.weighted;
-      dst->level_done = level_done;
-      dst->pending = skip ? 0 : 1;
-    }
-  }
-  if (skip) return;
+  if (publish_level_bound(sh, src, next_state(fa, b), sub == 0, pending, fa.prev_level, a.level)) return;
   float sums[27];
-  fca_chunk_pass<DIVC, PIPE, FAST, SAVEW>(a, K, g, cur, sh.newS, begin, end, first, firstf, first_pre, sums);
+  fca_chunk_pass<DIVC, PIPE, FAST, SAVEW>(a, K, g, cur, sh.newS, c.begin, c.end, first.in, first.inf, first.pre, sums);
   ELLC_STAMP(7);
   ELLC_BSTAMP(2);
-  float* out = a.partials + (size_t)(fa.seq & 1) * fa.stride_part + ((size_t)b * ELLC_NBLK_MAX + sub) * ELLC_PART_STRIDE;
-  block_reduce_store<27>(sums, out);
+  block_reduce_store<27>(sums, partial_record(fa, fa.seq, b, sub));
   ELLC_STAMP(8);
   ELLC_BSTAMP(3);
   ELLC_SEQSTAMP(32, fa.seq);
@@ -1757,83 +1888,45 @@ __device__ __forceinline__ FcaInF dense_form(const LevelGeom& g, const DensePix&
   in.v = (u32x4_t){(uint32_t)x | ((uint32_t)y << 12) | (p.I << 24), __builtin_bit_cast(uint32_t, p.var), __builtin_bit_cast(uint32_t, dd), 0u};
   return in;
 }
+// The pixel loop of gn_fca_dense and gn_fca_dense_x over the block's chunk of the plane (not empty), trip count block-uniform
+// (fca_chunk_pass). `pix` holds the planes' values of the thread's pixel at p, requested a step ahead: step(pix, p, active,
+// refill) forms the pixel from them, then calls refill() where the next pixel's request belongs (behind its tap loads), and
+// accumulates.
+template <class Pix, class Request, class Step>
+__device__ __forceinline__ void dense_plane_pass(const Chunk& c, const PlaneWalk& w, int sw, PlanePos p, Pix& pix, Request request, Step step) {
+  const TripCount tc = trip_count(c.begin, c.end);
+  for (int k = 0; k < tc.n_steps; k++) {
+    const PlanePos n = plane_next(w, p, c.end - 1);
+    auto refill = [&]() { pix = request((unsigned)min(n.i, c.end - 1), (unsigned)(n.y * sw + n.x)); };
+    step(pix, p, tc.active(k), refill);
+    p = n;
+  }
+}
 
 __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_dense(const AlignState* src_state, const float* prev_part, int prev_nblk, int nblk, int age_rounds,
                                                                    FusedArgs fa) {
   const GnArgs& a = fa.g;
-  int b = blockIdx.y, sub = blockIdx.x, age = 0, per_age = nblk;
-  if (age_rounds > 1) {   // see gn_fca_fused
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int per_round = (int)(gridDim.x * gridDim.y) / age_rounds;
-    per_age = nblk / age_rounds;
-    age = lin / per_round;
-    const int j = lin - age * per_round;
-    b = j / per_age;
-    sub = age * per_age + (j - b * per_age);
-  } else if (fa.xcd_map) {
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int w = lin >> 3, bl = w / nblk;
-    sub = w - bl * nblk;
-    b = bl * 8 + (lin & 7);
-  }
+  const BlockMap m = block_map(nblk, age_rounds, fa.xcd_map);
+  const int b = m.b, sub = m.sub;
   const AlignState& src = src_state[b];
-  AlignState* dst = a.state + (size_t)((fa.seq + 1) & 1) * fa.stride_state + b;
   __shared__ SolveShared sh;
   const int t = threadIdx.x;
-  const bool writer = (sub == 0);
   const LevelGeom g = a.geom[a.level];
   const KfLevelDev K = a.kf_tab[a.level * a.max_kf + a.kf_slot[b]];   // by value: uniform, lives in SGPRs
   const FrLevelDev& F = a.fr_tab[a.level * a.max_fr + a.fr_slot[b]];
   const int pending = src.pending;
-  const int V = g.n;   // the "list" is the plane
-  const double group_sum = partial_group_sum(prev_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE, prev_nblk);
-  int begin, end;
-  if (age_rounds > 1) {
-    const int gb = (int)(((long long)V * fa.age_cum[age]) >> 16), ge = (int)(((long long)V * fa.age_cum[age + 1]) >> 16);
-    const int chunk = (ge - gb + per_age - 1) / per_age;
-    begin = gb + (sub - age * per_age) * chunk;
-    end = min(ge, begin + chunk);
-  } else {
-    const int chunk = (V + nblk - 1) / nblk;
-    begin = sub * chunk;
-    end = min(V, begin + chunk);
-  }
+  const double group_sum = partial_group_sum(pending_partials(prev_part, b), prev_nblk);
+  const Chunk c = m.chunk(fa.age_cum, g.n, nblk);   // the "list" is the plane
   g_u8 cur = as_global(F.img);
   // this thread's first pixel: position and planes, requested before the solve
-  const int cols = g.cols, sw = g.sw;
-  const int qstep = ELLC_GN_THREADS / cols, rstep = ELLC_GN_THREADS - qstep * cols;   // a step advances a thread by 256 pixels: qstep rows and rstep columns
-  int x = 0, y = 0;
+  const int sw = g.sw;
+  const PlaneWalk w = plane_walk(g.cols);
+  const PlanePos p0 = plane_first(w, c, t);
   DensePix pix;
   pix.Z = 0.0f; pix.var = 0.0f; pix.I = 0u;
-  if (begin < end) {   // block-uniform (a thread past the chunk's end starts on a copy of its last pixel: the pixel loop is block-uniform)
-    const int i0 = min(begin + t, end - 1);
-    y = (int)(((float)i0 + 0.5f) * (1.0f / (float)cols));   // i < 2^24: exact conversion; corrected to the exact quotient
-    if (y * cols > i0) y--;
-    if ((y + 1) * cols <= i0) y++;
-    x = i0 - y * cols;
-    pix = dense_request(K, (unsigned)i0, (unsigned)(y * sw + x));
-  }
-  if (pending) {
-    solve_step<true>(sh, group_sum, 0, fa.prev_level, fa.early_exit, src, nullptr);
-  } else {
-    if (t < 6) sh.newpose[t] = src.pose[t];
-    if (t < 12) sh.newS[t] = src.S[t];
-    if (t == 0) { sh.weighted = src.weighted; sh.level_done = src.level_done; }
-    __syncthreads();
-  }
-  const int level_done = sh.level_done;
-  const bool skip = (level_done == a.level);
-  if (writer) {
-    if (t < 6) dst->pose[t] = sh.newpose[t];
-    if (t < 12) dst->S[t] = sh.newS[t];
-    if (t < ELLC_MAX_LEVELS) dst->iters[t] = src.iters[t] + ((pending && t == fa.prev_level) ? 1 : 0);
-    if (t == 0) {
-      dst->weighted = sh.weighted;
-      dst->level_done = level_done;
-      dst->pending = skip ? 0 : 1;
-    }
-  }
-  if (skip) return;
+  if (c.begin < c.end) pix = dense_request(K, (unsigned)min(p0.i, c.end - 1), (unsigned)(p0.y * sw + p0.x));   // block-uniform
+  advance_pose<true>(sh, pending, group_sum, 0, fa.prev_level, fa.early_exit, src);
+  if (publish_level_bound(sh, src, next_state(fa, b), sub == 0, pending, fa.prev_level, a.level)) return;
   float sums[27];
   {
     float S[12];
@@ -1841,40 +1934,20 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_dense(const AlignSt
     for (int i = 0; i < 12; i++) S[i] = sh.newS[i];
     FcaAcc acc;
     fca_acc_zero(acc);
-    if (begin < end) {   // block-uniform
+    if (c.begin < c.end) {   // block-uniform
       const TapRows tr = tap_rows(cur, sw);
       const FcafConst fc = fcaf_const(g, S);
-      const int n_full = __builtin_amdgcn_readfirstlane((end - begin) / ELLC_GN_THREADS);
-      const int rem = __builtin_amdgcn_readfirstlane((end - begin) - n_full * ELLC_GN_THREADS);
-      const int n_steps = n_full + (rem > 0 ? 1 : 0);
-      int i = begin + t;
-      for (int k = 0; k < n_steps; k++) {
-        const bool last = (k == n_steps - 1);
-        const bool active = !last || rem == 0 || t < rem;
-        bool valid;
-        const FcaInF rec = dense_form(g, pix, x, y, valid);
-        // the next pixel of this thread: 256 further on (clamped to the chunk's last pixel: every request is unconditional)
-        int xn = x + rstep, yn = y + qstep;
-        if (xn >= cols) { xn -= cols; yn++; }
-        const int in_ = i + ELLC_GN_THREADS;
-        if (in_ > end - 1) {   // past the end: the chunk's last pixel
-          const int il = end - 1;
-          yn = (int)(((float)il + 0.5f) * (1.0f / (float)cols));
-          if (yn * cols > il) yn--;
-          if ((yn + 1) * cols <= il) yn++;
-          xn = il - yn * cols;
-        }
-        const unsigned inext = (unsigned)min(in_, end - 1);
-        auto refill = [&]() { pix = dense_request(K, inext, (unsigned)(yn * sw + xn)); };
-        const FcafStage st = fcaf_stage_a(g, tr, fc, rec, refill);
-        if (active && valid) fca_accumulate_pixel(acc, fcaf_stage_b<false, 0>(a, K, g, cur, fc, (unsigned)i, st));
-        x = xn; y = yn; i = in_;
-      }
+      dense_plane_pass(c, w, sw, p0, pix, [&](unsigned i, unsigned img_off) { return dense_request(K, i, img_off); },
+                       [&](const DensePix& px, const PlanePos& p, bool active, auto refill) {
+                         bool valid;
+                         const FcaInF rec = dense_form(g, px, p.x, p.y, valid);
+                         const FcafStage st = fcaf_stage_a(g, tr, fc, rec, refill);
+                         if (active && valid) fca_accumulate_pixel(acc, fcaf_stage_b<false, 0>(a, K, g, cur, fc, (unsigned)p.i, st));
+                       });
     }
     fca_acc_unpack<true>(acc, sums);
   }
-  float* out = a.partials + (size_t)(fa.seq & 1) * fa.stride_part + ((size_t)b * ELLC_NBLK_MAX + sub) * ELLC_PART_STRIDE;
-  block_reduce_store<27>(sums, out);
+  block_reduce_store<27>(sums, partial_record(fa, fa.seq, b, sub));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1897,78 +1970,26 @@ template <bool DIVC>
 __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_dense_x(const AlignState* src_state, const float* prev_part, int prev_nblk, int nblk, int age_rounds,
                                                                      FusedArgs fa) {
   const GnArgs& a = fa.g;
-  int b = blockIdx.y, sub = blockIdx.x, age = 0, per_age = nblk;
-  if (age_rounds > 1) {   // see gn_fca_fused
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int per_round = (int)(gridDim.x * gridDim.y) / age_rounds;
-    per_age = nblk / age_rounds;
-    age = lin / per_round;
-    const int j = lin - age * per_round;
-    b = j / per_age;
-    sub = age * per_age + (j - b * per_age);
-  } else if (fa.xcd_map) {
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int w = lin >> 3, bl = w / nblk;
-    sub = w - bl * nblk;
-    b = bl * 8 + (lin & 7);
-  }
+  const BlockMap m = block_map(nblk, age_rounds, fa.xcd_map);
+  const int b = m.b, sub = m.sub;
   const AlignState& src = src_state[b];
-  AlignState* dst = a.state + (size_t)((fa.seq + 1) & 1) * fa.stride_state + b;
   __shared__ SolveShared sh;
   const int t = threadIdx.x;
-  const bool writer = (sub == 0);
   const LevelGeom g = a.geom[a.level];
   const KfLevelDev K = a.kf_tab[a.level * a.max_kf + a.kf_slot[b]];
   const FrLevelDev& F = a.fr_tab[a.level * a.max_fr + a.fr_slot[b]];
   const int pending = src.pending;
-  const int V = g.n;   // the "list" is the plane
-  const double group_sum = partial_group_sum(prev_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE, prev_nblk);
-  int begin, end;
-  if (age_rounds > 1) {
-    const int gb = (int)(((long long)V * fa.age_cum[age]) >> 16), ge = (int)(((long long)V * fa.age_cum[age + 1]) >> 16);
-    const int chunk = (ge - gb + per_age - 1) / per_age;
-    begin = gb + (sub - age * per_age) * chunk;
-    end = min(ge, begin + chunk);
-  } else {
-    const int chunk = (V + nblk - 1) / nblk;
-    begin = sub * chunk;
-    end = min(V, begin + chunk);
-  }
+  const double group_sum = partial_group_sum(pending_partials(prev_part, b), prev_nblk);
+  const Chunk c = m.chunk(fa.age_cum, g.n, nblk);   // the "list" is the plane
   g_u8 cur = as_global(F.img);
-  const int cols = g.cols, sw = g.sw;
-  const int qstep = ELLC_GN_THREADS / cols, rstep = ELLC_GN_THREADS - qstep * cols;
-  int x = 0, y = 0;
+  const int sw = g.sw;
+  const PlaneWalk w = plane_walk(g.cols);
+  const PlanePos p0 = plane_first(w, c, t);
   DensePixX pix;
   pix.Z = 0.0f; pix.var = 0.0f; pix.I = 0u; pix.invZ = 1.0;
-  if (begin < end) {   // block-uniform (a thread past the chunk's end starts on a copy of its last pixel: the pixel loop is block-uniform)
-    const int i0 = min(begin + t, end - 1);
-    y = (int)(((float)i0 + 0.5f) * (1.0f / (float)cols));
-    if (y * cols > i0) y--;
-    if ((y + 1) * cols <= i0) y++;
-    x = i0 - y * cols;
-    pix = dense_request_x(K, (unsigned)i0, (unsigned)(y * sw + x));
-  }
-  if (pending) {
-    solve_step<false>(sh, group_sum, 0, fa.prev_level, fa.early_exit, src, nullptr);
-  } else {
-    if (t < 6) sh.newpose[t] = src.pose[t];
-    if (t < 12) sh.newS[t] = src.S[t];
-    if (t == 0) { sh.weighted = src.weighted; sh.level_done = src.level_done; }
-    __syncthreads();
-  }
-  const int level_done = sh.level_done;
-  const bool skip = (level_done == a.level);
-  if (writer) {
-    if (t < 6) dst->pose[t] = sh.newpose[t];
-    if (t < 12) dst->S[t] = sh.newS[t];
-    if (t < ELLC_MAX_LEVELS) dst->iters[t] = src.iters[t] + ((pending && t == fa.prev_level) ? 1 : 0);
-    if (t == 0) {
-      dst->weighted = sh.weighted;
-      dst->level_done = level_done;
-      dst->pending = skip ? 0 : 1;
-    }
-  }
-  if (skip) return;
+  if (c.begin < c.end) pix = dense_request_x(K, (unsigned)min(p0.i, c.end - 1), (unsigned)(p0.y * sw + p0.x));   // block-uniform
+  advance_pose<false>(sh, pending, group_sum, 0, fa.prev_level, fa.early_exit, src);
+  if (publish_level_bound(sh, src, next_state(fa, b), sub == 0, pending, fa.prev_level, a.level)) return;
   float sums[27];
   {
     float S[12];
@@ -1976,46 +1997,25 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_dense_x(const Align
     for (int i = 0; i < 12; i++) S[i] = sh.newS[i];
     FcaAcc acc;
     fca_acc_zero(acc);
-    if (begin < end) {   // block-uniform
-      const int n_full = __builtin_amdgcn_readfirstlane((end - begin) / ELLC_GN_THREADS);
-      const int rem = __builtin_amdgcn_readfirstlane((end - begin) - n_full * ELLC_GN_THREADS);
-      const int n_steps = n_full + (rem > 0 ? 1 : 0);
-      int i = begin + t;
-      for (int k = 0; k < n_steps; k++) {
-        const bool last = (k == n_steps - 1);
-        const bool active = !last || rem == 0 || t < rem;
-        const bool valid = pix.Z > 0.0f;
-        FcaIn in;   // fca_load's values, from the planes
-        in.xy = ((uint32_t)y << 16) | (uint32_t)x;
-        in.Ikf = (float)pix.I;
-        in.Z = valid ? pix.Z : 1.0f;
-        in.var = pix.var;
-        in.invZ = valid ? pix.invZ : 1.0;
-        const float aX = ((float)x - g.cx) * in.Z, aY = ((float)y - g.cy) * in.Z;
-        in.X = DIVC ? div_const(aX, g.fx, g.rfx) : aX / g.fx;
-        in.Y = DIVC ? div_const(aY, g.fy, g.rfy) : aY / g.fy;
-        // the next pixel of this thread: 256 further on (clamped to the chunk's last pixel: every request is unconditional)
-        int xn = x + rstep, yn = y + qstep;
-        if (xn >= cols) { xn -= cols; yn++; }
-        const int in_ = i + ELLC_GN_THREADS;
-        if (in_ > end - 1) {
-          const int il = end - 1;
-          yn = (int)(((float)il + 0.5f) * (1.0f / (float)cols));
-          if (yn * cols > il) yn--;
-          if ((yn + 1) * cols <= il) yn++;
-          xn = il - yn * cols;
-        }
-        const unsigned inext = (unsigned)min(in_, end - 1);
-        auto refill = [&]() { pix = dense_request_x(K, inext, (unsigned)(yn * sw + xn)); };
-        const FcaPix q = fca_pixel_in<false, DIVC>(a, K, g, cur, S, (unsigned)i, in, refill);
-        if (active && valid) fca_accumulate_pixel(acc, q);
-        x = xn; y = yn; i = in_;
-      }
-    }
+    if (c.begin < c.end)   // block-uniform
+      dense_plane_pass(c, w, sw, p0, pix, [&](unsigned i, unsigned img_off) { return dense_request_x(K, i, img_off); },
+                       [&](const DensePixX& px, const PlanePos& p, bool active, auto refill) {
+                         const bool valid = px.Z > 0.0f;
+                         FcaIn in;   // fca_load's values, from the planes
+                         in.xy = ((uint32_t)p.y << 16) | (uint32_t)p.x;
+                         in.Ikf = (float)px.I;
+                         in.Z = valid ? px.Z : 1.0f;
+                         in.var = px.var;
+                         in.invZ = valid ? px.invZ : 1.0;
+                         const float aX = ((float)p.x - g.cx) * in.Z, aY = ((float)p.y - g.cy) * in.Z;
+                         in.X = DIVC ? div_const(aX, g.fx, g.rfx) : aX / g.fx;
+                         in.Y = DIVC ? div_const(aY, g.fy, g.rfy) : aY / g.fy;
+                         const FcaPix q = fca_pixel_in<false, DIVC>(a, K, g, cur, S, (unsigned)p.i, in, refill);
+                         if (active && valid) fca_accumulate_pixel(acc, q);
+                       });
     fca_acc_unpack<false>(acc, sums);
   }
-  float* out = a.partials + (size_t)(fa.seq & 1) * fa.stride_part + ((size_t)b * ELLC_NBLK_MAX + sub) * ELLC_PART_STRIDE;
-  block_reduce_store<27>(sums, out);
+  block_reduce_store<27>(sums, partial_record(fa, fa.seq, b, sub));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2060,82 +2060,32 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
                                                                     FusedArgs fa) {
   ELLC_BSTAMP(0);
   const GnArgs& a = fa.g;
-  int b = blockIdx.y, sub = blockIdx.x, age = 0, per_age = nblk;
-  if (age_rounds > 1) {   // see gn_fca_fused
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int per_round = (int)(gridDim.x * gridDim.y) / age_rounds;
-    per_age = nblk / age_rounds;
-    age = lin / per_round;
-    const int j = lin - age * per_round;
-    b = j / per_age;
-    sub = age * per_age + (j - b * per_age);
-  } else if (fa.xcd_map) {
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int w = lin >> 3, bl = w / nblk;
-    sub = w - bl * nblk;
-    b = bl * 8 + (lin & 7);
-  }
+  const BlockMap m = block_map(nblk, age_rounds, fa.xcd_map);
+  const int b = m.b, sub = m.sub;
   const AlignState& src = src_state[b];
-  AlignState* dst = a.state + (size_t)((fa.seq + 1) & 1) * fa.stride_state + b;
   __shared__ SolveShared sh;
   __shared__ uint32_t qbuf[ELLC_GN_THREADS / 64][ELLC_QUAD_QCAP];
   const int t = threadIdx.x;
-  const bool writer = (sub == 0);
   const LevelGeom g = a.geom[a.level];
   const KfLevelDev K = a.kf_tab[a.level * a.max_kf + a.kf_slot[b]];   // by value: uniform, lives in SGPRs
   const FrLevelDev& F = a.fr_tab[a.level * a.max_fr + a.fr_slot[b]];
   const int pending = src.pending;
   const int cols = g.cols, sw = g.sw;
   const int cols4 = cols >> 2;      // quads per row (the host launches this kernel for cols % 4 == 0 only)
-  const int V = g.n >> 2;           // the "list" is the plane, in quads
-  const double group_sum = partial_group_sum(prev_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE, prev_nblk);
-  int begin, end;
-  if (age_rounds > 1) {
-    const int gb = (int)(((long long)V * fa.age_cum[age]) >> 16), ge = (int)(((long long)V * fa.age_cum[age + 1]) >> 16);
-    const int chunk = (ge - gb + per_age - 1) / per_age;
-    begin = gb + (sub - age * per_age) * chunk;
-    end = min(ge, begin + chunk);
-  } else {
-    const int chunk = (V + nblk - 1) / nblk;
-    begin = sub * chunk;
-    end = min(V, begin + chunk);
-  }
+  const double group_sum = partial_group_sum(pending_partials(prev_part, b), prev_nblk);
+  const Chunk c = m.chunk(fa.age_cum, g.n >> 2, nblk);   // the "list" is the plane, in quads
+  const int begin = c.begin, end = c.end;
   g_u8 cur = as_global(F.img);
-  // this thread's first quad: position and planes, requested before the solve
-  const int qstep = ELLC_GN_THREADS / cols4, rstep = ELLC_GN_THREADS - qstep * cols4;   // a step advances a thread by 256 quads: qstep rows and rstep quad columns
-  int xq = 0, y = 0;   // quad column, row
+  // this thread's first quad: position (quad column, row) and planes, requested before the solve
+  const PlaneWalk w = plane_walk(cols4);
+  PlanePos p = plane_first(w, c, t);
   QuadPlanes pl;
   pl.Z = (f32x4_t)(0.0f); pl.var = (f32x4_t)(0.0f); pl.I = 0u;
-  if (begin < end) {   // block-uniform (a thread past the chunk's end starts on a copy of its last quad: the loop is block-uniform)
-    const int i0 = min(begin + t, end - 1);
-    y = (int)(((float)i0 + 0.5f) * (1.0f / (float)cols4));   // i < 2^24: exact conversion; corrected to the exact quotient
-    if (y * cols4 > i0) y--;
-    if ((y + 1) * cols4 <= i0) y++;
-    xq = i0 - y * cols4;
-    pl = quad_request(K, 4u * (unsigned)i0, __umul24((unsigned)y, (unsigned)sw) + 4u * (unsigned)xq);
-  }
-  if (pending) {
-    solve_step<true>(sh, group_sum, 0, fa.prev_level, fa.early_exit, src, nullptr);
-  } else {
-    if (t < 6) sh.newpose[t] = src.pose[t];
-    if (t < 12) sh.newS[t] = src.S[t];
-    if (t == 0) { sh.weighted = src.weighted; sh.level_done = src.level_done; }
-    __syncthreads();
-  }
-  const int level_done = sh.level_done;
-  const bool skip = (level_done == a.level);
-  if (writer) {
-    if (t < 6) dst->pose[t] = sh.newpose[t];
-    if (t < 12) dst->S[t] = sh.newS[t];
-    if (t < ELLC_MAX_LEVELS) dst->iters[t] = src.iters[t] + ((pending && t == fa.prev_level) ? 1 : 0);
-    if (t == 0) {
-      dst->weighted = sh.weighted;
-      dst->level_done = level_done;
-      dst->pending = skip ? 0 : 1;
-    }
-  }
+  if (begin < end)   // block-uniform
+    pl = quad_request(K, 4u * (unsigned)min(p.i, end - 1), __umul24((unsigned)p.y, (unsigned)sw) + 4u * (unsigned)p.x);
+  advance_pose<true>(sh, pending, group_sum, 0, fa.prev_level, fa.early_exit, src);
   ELLC_BSTAMP(1);
-  if (skip) return;
+  if (publish_level_bound(sh, src, next_state(fa, b), sub == 0, pending, fa.prev_level, a.level)) return;
   float sums[27];
   {
     // exp(pose) of this iteration: uniform, so into scalar registers (the per-pixel operands get vector copies below: an SGPR
@@ -2158,34 +2108,20 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
       const float s_rfy = g.rfy, s_qc = -(g.cy * g.rfy), s_pc = -(g.cx * g.rfx);
       float vP0 = P[0], vP3 = P[3], vP4 = P[4], vP7 = P[7], vP8 = P[8], vP11 = P[11], v_rfx = g.rfx, v_hfx = 0.5f * g.fx, v_hfy = 0.5f * g.fy;
       asm volatile("" : "+v"(vP0), "+v"(vP3), "+v"(vP4), "+v"(vP7), "+v"(vP8), "+v"(vP11), "+v"(v_rfx), "+v"(v_hfx), "+v"(v_hfy));
-      const int n_full = __builtin_amdgcn_readfirstlane((end - begin) / ELLC_GN_THREADS);
-      const int rem = __builtin_amdgcn_readfirstlane((end - begin) - n_full * ELLC_GN_THREADS);
-      const int n_steps = n_full + (rem > 0 ? 1 : 0);
+      const TripCount tc = trip_count(begin, end);
       const int lane = t & 63;
       uint32_t* const q = qbuf[t >> 6];
       int qn = 0;   // wave-uniform: entries queued
-      int i = begin + t;
       for (int k = 0;; k++) {
-        const bool more = (k < n_steps);   // block-uniform
+        const bool more = (k < tc.n_steps);   // block-uniform
         if (more) {
-          const bool last = (k == n_steps - 1);
-          const bool active = !last || rem == 0 || t < rem;
+          const bool active = tc.active(k);
           const f32x4_t cZ = pl.Z, cvar = pl.var;
           const uint32_t cI = pl.I;
-          const unsigned i4 = 4u * (unsigned)min(i, end - 1);
-          const int x = 4 * xq, yrow = y;
-          // the next quad of this thread: 256 further on (clamped to the chunk's last quad: every request is unconditional)
-          int xn = xq + rstep, yn = y + qstep;
-          if (xn >= cols4) { xn -= cols4; yn++; }
-          const int in_ = i + ELLC_GN_THREADS;
-          if (in_ > end - 1) {
-            const int il = end - 1;
-            yn = (int)(((float)il + 0.5f) * (1.0f / (float)cols4));
-            if (yn * cols4 > il) yn--;
-            if ((yn + 1) * cols4 <= il) yn++;
-            xn = il - yn * cols4;
-          }
-          const unsigned inext = 4u * (unsigned)min(in_, end - 1);
+          const unsigned i4 = 4u * (unsigned)min(p.i, end - 1);
+          const int x = 4 * p.x, yrow = p.y;
+          const PlanePos n = plane_next(w, p, end - 1);
+          const unsigned inext = 4u * (unsigned)min(n.i, end - 1);
           // inverse depths (the slot's reciprocal planes: the v_rcp_f32 the compaction would store; 0 = no depth); a pixel without
           // depth takes a neighbour's (its point then lands beside theirs and does not spoil the fit)
           const bool v0 = cZ.x > 0.0f, v1 = cZ.y > 0.0f, v2 = cZ.z > 0.0f, v3 = cZ.w > 0.0f;
@@ -2231,7 +2167,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
           const u32x2_t wE = *(const ELLC_GLOBAL u32x2_a1*)(row_e + off);
           __builtin_amdgcn_sched_barrier(0);
           // the next quad's planes, behind the row requests (vector loads return in issue order)
-          pl = quad_request(K, inext, __umul24((unsigned)yn, (unsigned)sw) + 4u * (unsigned)xn);
+          pl = quad_request(K, inext, __umul24((unsigned)n.y, (unsigned)sw) + 4u * (unsigned)n.x);
           __builtin_amdgcn_sched_barrier(0);
           const float var[4] = {cvar.x, cvar.y, cvar.z, cvar.w};
           const uint32_t wAx = wA.x, wAy = wA.y, wBx = wB.x, wBy = wB.y, wCx = wC.x, wCy = wC.y, wDx = wD.x, wDy = wD.y, wEx = wE.x, wEy = wE.y;
@@ -2306,7 +2242,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
 #ifdef ELLC_QUAD_STATS
           { const unsigned long long ma = __builtin_amdgcn_ballot_w64(active); if (lane == 0) atomicAdd(&g_quad_stats[0], (unsigned long long)__builtin_popcountll(ma)); }
 #endif
-          xq = xn; y = yn; i = in_;
+          p = n;
         }
         // the queue: 64 at a time through the per-pixel step while the chunk lasts, then what is left
         while (__builtin_expect(qn >= (more ? 64 : 1), 0)) {   // (cold: what the register allocator must spill, it spills here)
@@ -2315,10 +2251,8 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
           const unsigned idx = q[qn - n + min(lane, n - 1)];   // (a lane without an entry runs on a copy of the last one and accumulates nothing)
           __builtin_amdgcn_wave_barrier();
           qn -= n;
-          int yy = (int)(((float)idx + 0.5f) * (1.0f / (float)cols));
-          if (yy * cols > (int)idx) yy--;
-          if ((yy + 1) * cols <= (int)idx) yy++;
-          const int xx = (int)idx - yy * cols;
+          int xx, yy;
+          plane_xy((int)idx, cols, xx, yy);
           const DensePix dp = dense_request(K, idx, (unsigned)(yy * sw + xx));
           bool valid;
           const FcaInF rec = dense_form(g, dp, xx, yy, valid);
@@ -2334,9 +2268,8 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
     }
     fca_acc_unpack<true>(acc, sums);
   }
-  float* out = a.partials + (size_t)(fa.seq & 1) * fa.stride_part + ((size_t)b * ELLC_NBLK_MAX + sub) * ELLC_PART_STRIDE;
   ELLC_BSTAMP(2);
-  block_reduce_store<27>(sums, out);
+  block_reduce_store<27>(sums, partial_record(fa, fa.seq, b, sub));
   ELLC_BSTAMP(3);
 }
 
@@ -2360,19 +2293,14 @@ template <bool DIVC, bool FAST, int SAVEW>
 __global__ __launch_bounds__(ELLC_GN_THREADS, FAST ? 4 : 3) void gn_fca_adaptive(const AlignState* src_state, const float* prev_part, int nblk_grid,
                                                                       FusedArgs fa) {
   const GnArgs& a = fa.g;
-  int b = blockIdx.y, sub = blockIdx.x;
-  if (fa.xcd_map) {   // see gn_fca_fused
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int w = lin >> 3, bl = w / nblk_grid;
-    sub = w - bl * nblk_grid;
-    b = bl * 8 + (lin & 7);
-  }
+  const BlockMap m = block_map(nblk_grid, 0, fa.xcd_map);
+  const int b = m.b, sub = m.sub;
   const AlignState& src = src_state[b];
-  AlignState* dst = a.state + (size_t)((fa.seq + 1) & 1) * fa.stride_state + b;
+  AlignState* dst = next_state(fa, b);
   __shared__ SolveShared sh;
   const int t = threadIdx.x;
   const bool writer = (sub == 0);
-  const float* pend = prev_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
+  const float* pend = pending_partials(prev_part, b);
   float pv[8];
   partial_preload(pend, min(nblk_grid, 8 * (ELLC_SOLVE_THREADS / 32)), pv);
   const int slot = a.kf_slot[b], frs = a.fr_slot[b];
@@ -2390,43 +2318,14 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, FAST ? 4 : 3) void gn_fca_adaptive
     }
     return;
   }
-  const int nb_l = fa.nblk_lv[lvl];
-  if (sub >= max(nb_l, lvl > 0 ? fa.nblk_lv[lvl - 1] : 0)) return;   // needed neither at this level nor at the next (block 0 always is)
+  if (sub >= max(fa.nblk_lv[lvl], lvl > 0 ? fa.nblk_lv[lvl - 1] : 0)) return;   // needed neither at this level nor at the next (block 0 always is)
   // speculatively the tables of the record's level (the pixel pass stays there unless the solve ends the level)
-  LevelGeom g = a.geom[lvl];
-  KfLevelDev K = a.kf_tab[lvl * a.max_kf + slot];
-  const FrLevelDev* F = &a.fr_tab[lvl * a.max_fr + frs];
-  int V = *as_global(K.count);
-  const double group_sum = partial_group_sum_from(pend, pv, nb_l);
-  int begin, end;
-  {
-    const int chunk = (V + nb_l - 1) / nb_l;
-    begin = sub * chunk;
-    end = min(V, begin + chunk);
-  }
-  // this thread's first record (exact mode: and its pose-independent products), requested before the solve
-  FcaIn first = fca_in_empty();
-  FcaInF firstf = fcaf_empty();
-  FcaPre first_pre;
-  if constexpr (FAST) {
-    if (sub < nb_l && begin < end) firstf = fcaf_load(K, (unsigned)min(begin + t, end - 1));
-  } else {
-    if (sub < nb_l && begin + t < end) first = fca_load<DIVC>(K, g, (unsigned)(begin + t));
-    first_pre = fca_prepare<DIVC>(g, first);
-    asm volatile("" ::"v"(first_pre.c_t0), "v"(first_pre.c_b1), "v"(first_pre.d), "v"(first_pre.fxz), "v"(first_pre.fyz),
-                 "v"(first_pre.nvz), "v"(first_pre.nuz));   // pinned above the solve, see gn_fca_fused
-  }
-  if (pending) {
-    solve_step<FAST>(sh, group_sum, 0, lvl, fa.early_exit, src, nullptr);
-  } else {
-    if (t < 6) sh.newpose[t] = src.pose[t];
-    if (t < 12) sh.newS[t] = src.S[t];
-    if (t == 0) { sh.weighted = src.weighted; sh.level_done = src.level_done; }
-    __syncthreads();
-  }
-  const int it = src.it_in_level + (pending ? 1 : 0);
-  const bool over = pending && (sh.level_done == lvl || it >= fa.max_it[lvl]);   // the level has ended: early exit, or its cap
-  const int nl = over ? lvl - 1 : lvl;
+  LevelWork L = level_work(fa, m, lvl, slot, frs);
+  const double group_sum = partial_group_sum_from(pend, pv, L.nb);
+  FirstRec first = no_record();
+  request_first<DIVC, FAST, true>(first, L.K, L.g, L.c, t, sub < L.nb);
+  advance_pose<FAST>(sh, pending, group_sum, 0, lvl, fa.early_exit, src);
+  const LevelStep ls = level_step(sh, fa, pending, lvl, src.it_in_level);
   if (writer) {
     if (t < 6) dst->pose[t] = sh.newpose[t];
     if (t < 12) dst->S[t] = sh.newS[t];
@@ -2434,36 +2333,23 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, FAST ? 4 : 3) void gn_fca_adaptive
     if (t == 0) {
       dst->weighted = sh.weighted;
       dst->level_done = sh.level_done;
-      dst->pending = nl >= 0 ? 1 : 0;
-      dst->cur_level = nl;
-      dst->it_in_level = over ? 0 : it;
+      dst->pending = ls.nl >= 0 ? 1 : 0;
+      dst->cur_level = ls.nl;
+      dst->it_in_level = ls.it;
     }
   }
-  if (nl < 0) return;
-  if (over) {   // a level change (at most L - 1 per alignment): tables, chunk and first record of the finer level
-    const int nb_n = fa.nblk_lv[nl];
-    if (sub >= nb_n) return;
-    g = a.geom[nl];
-    K = a.kf_tab[nl * a.max_kf + slot];
-    F = &a.fr_tab[nl * a.max_fr + frs];
-    V = *as_global(K.count);
-    const int chunk = (V + nb_n - 1) / nb_n;
-    begin = sub * chunk;
-    end = min(V, begin + chunk);
-    if constexpr (FAST) {
-      if (begin < end) firstf = fcaf_load(K, (unsigned)min(begin + t, end - 1));   // (a thread past the chunk's end starts on a copy of its last record: the pixel loop is block-uniform)
-    } else {
-      if (begin + t < end) first = fca_load<DIVC>(K, g, (unsigned)(begin + t));
-      first_pre = fca_prepare<DIVC>(g, first);
-    }
-  } else if (sub >= nb_l) {
+  if (ls.nl < 0) return;
+  if (ls.over) {   // a level change: tables, chunk and first record of the finer level
+    L = level_work(fa, m, ls.nl, slot, frs);
+    if (sub >= L.nb) return;
+    request_first<DIVC, FAST, false>(first, L.K, L.g, L.c, t, true);
+  } else if (sub >= L.nb) {
     return;
   }
-  g_u8 cur = as_global(F->img);
+  g_u8 cur = as_global(L.F->img);
   float sums[27];
-  fca_chunk_pass<DIVC, true, FAST, SAVEW>(a, K, g, cur, sh.newS, begin, end, first, firstf, first_pre, sums);
-  float* out = a.partials + (size_t)(fa.seq & 1) * fa.stride_part + ((size_t)b * ELLC_NBLK_MAX + sub) * ELLC_PART_STRIDE;
-  block_reduce_store<27>(sums, out);
+  fca_chunk_pass<DIVC, true, FAST, SAVEW>(a, L.K, L.g, cur, sh.newS, L.c.begin, L.c.end, first.in, first.inf, first.pre, sums);
+  block_reduce_store<27>(sums, partial_record(fa, fa.seq, b, sub));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2668,7 +2554,8 @@ template <bool DIVC, bool FAST, int SAVEW>
 __global__ __launch_bounds__(ELLC_GN_THREADS, FAST ? 3 : 2) void gn_fca_persist(FusedArgs fa, int max_rounds, unsigned epoch, unsigned spin_limit,
                                                                               int delay_from, int delay_polls, PersistStage ps) {
   const GnArgs& a = fa.g;
-  const int b = blockIdx.y, sub = blockIdx.x, t = threadIdx.x;
+  const BlockMap m = block_map(0, 0, 0);   // no relabelling: (blockIdx.y, blockIdx.x)
+  const int b = m.b, sub = m.sub, t = threadIdx.x;
   if (ps.on && sub >= ps.persist_blocks) {   // block-uniform: a count block (see PersistStage)
     if (b == 0 && sub - ps.persist_blocks < ps.count_blocks)
       dm_count_valid_body(ps.count_valid, ps.count_n, ps.count_acc, ps.count_host, sub - ps.persist_blocks, ps.count_blocks);
@@ -2725,35 +2612,18 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, FAST ? 3 : 2) void gn_fca_persist(
     }
     const int lvl = st.cur_level, pending = st.pending, it_in = st.it_in_level;
     if (lvl < 0) break;
-    const int nb_l = fa.nblk_lv[lvl];
-    LevelGeom g = a.geom[lvl];
-    KfLevelDev K = a.kf_tab[lvl * a.max_kf + slot];
-    const FrLevelDev* F = &a.fr_tab[lvl * a.max_fr + frs];
-    int V = *as_global(K.count);
-    const unsigned* pend = (const unsigned*)(a.partials + (size_t)((seq + 1) & 1) * fa.stride_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE);
-    int begin, end;
-    {
-      const int chunk = (V + nb_l - 1) / nb_l;
-      begin = sub * chunk;
-      end = min(V, begin + chunk);
-    }
+    LevelWork L = level_work(fa, m, lvl, slot, frs);
+    const unsigned* pend = (const unsigned*)pending_partials(fa, seq, b);
     // this thread's first record of the level the record names, requested before the solve (as gn_fca_adaptive)
-    FcaIn first = fca_in_empty();
-    FcaInF firstf = fcaf_empty();
-    FcaPre first_pre;
-    if constexpr (FAST) {
-      if (sub < nb_l && begin < end) firstf = fcaf_load(K, (unsigned)min(begin + t, end - 1));
-    } else {
-      if (sub < nb_l && begin + t < end) first = fca_load<DIVC>(K, g, (unsigned)(begin + t));
-      first_pre = fca_prepare<DIVC>(g, first);
-    }
+    FirstRec first = no_record();
+    request_first<DIVC, FAST, false>(first, L.K, L.g, L.c, t, sub < L.nb);
     bool adopted = false;
     ELLC_PTRACE(1, 0);
-    ELLC_PTRACE(11, (lvl << 8) | (sub < nb_l ? 1 : 0));
+    ELLC_PTRACE(11, (lvl << 8) | (sub < L.nb ? 1 : 0));
     if (pending) {
       double group_sum;
-      const int got = persist_group_sum(pend, nb_l, (epoch << 8) | (unsigned)seq, abortw, epoch | 0x80000000u, spin_limit, group_sum);   // the records of round seq (the previous iteration's)
-      if (got != PERSIST_OK && (t & 63) == 0) atomicMax(&s_flag, got == PERSIST_LAPPED && sub >= nb_l ? 2 : 1);   // (a writer cannot be lapped: treated as a reason to abandon)
+      const int got = persist_group_sum(pend, L.nb, (epoch << 8) | (unsigned)seq, abortw, epoch | 0x80000000u, spin_limit, group_sum);   // the records of round seq (the previous iteration's)
+      if (got != PERSIST_OK && (t & 63) == 0) atomicMax(&s_flag, got == PERSIST_LAPPED && sub >= L.nb ? 2 : 1);   // (a writer cannot be lapped: treated as a reason to abandon)
       ELLC_PTRACE(2, 0);
       __syncthreads();
       if (s_flag == 1) break;   // abandoned (block-uniform); the record still names this iteration's level with its sums unsolved
@@ -2772,54 +2642,38 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, FAST ? 3 : 2) void gn_fca_persist(
         solve_step<FAST>(sh, group_sum, 0, lvl, fa.early_exit, st, writer ? rec : nullptr);
       }
     } else {
-      if (t < 6) sh.newpose[t] = st.pose[t];
-      if (t < 12) sh.newS[t] = st.S[t];
-      if (t == 0) { sh.weighted = st.weighted; sh.level_done = st.level_done; }
-      __syncthreads();
+      carry_pose(sh, st);
     }
     ELLC_PTRACE(3, 0);
-    const int it = it_in + (pending ? 1 : 0);
-    const bool over = adopted || (pending && (sh.level_done == lvl || it >= fa.max_it[lvl]));   // the level has ended: early exit, or its cap
-    const int nl = adopted ? s_level : (over ? lvl - 1 : lvl);
-    if (writer && over) persist_publish_state(state_line, (epoch << 8) | (unsigned)seq, sh, seq, nl);   // (see persist_publish_state)
-    // (every read of `st` of this iteration lies in front of the barrier that ends the solve)
+    LevelStep ls = level_step(sh, fa, pending, lvl, it_in);
+    if (adopted) { ls.over = true; ls.nl = s_level; ls.it = 0; }   // (the state line names the level that begins)
+    if (writer && ls.over) persist_publish_state(state_line, (epoch << 8) | (unsigned)seq, sh, seq, ls.nl);   // (see persist_publish_state)
+    // (every read of `st` of this iteration lies in front of the barrier that ends the solve. The stores stay spelled out
+    // here: through gn_fca_adaptive's form — iters[t] = iters[t] + ... by every t < ELLC_MAX_LEVELS — the exact build takes 241
+    // registers instead of 240)
     if (t < 6) st.pose[t] = sh.newpose[t];
     if (t < 12) st.S[t] = sh.newS[t];
     if (t == lvl && pending) st.iters[t] += 1;
     if (t == 0) {
       st.weighted = sh.weighted;
       st.level_done = sh.level_done;
-      st.pending = nl >= 0 ? 1 : 0;
-      st.cur_level = nl;
-      st.it_in_level = over ? 0 : it;
+      st.pending = ls.nl >= 0 ? 1 : 0;
+      st.cur_level = ls.nl;
+      st.it_in_level = ls.it;
     }
-    if (nl < 0) break;
-    bool work = sub < nb_l;
-    if (over) {   // a level change (at most L - 1 per alignment): tables, chunk and first record of the finer level
-      const int nb_n = fa.nblk_lv[nl];
-      work = sub < nb_n;
-      g = a.geom[nl];
-      K = a.kf_tab[nl * a.max_kf + slot];
-      F = &a.fr_tab[nl * a.max_fr + frs];
-      V = *as_global(K.count);
-      const int chunk = (V + nb_n - 1) / nb_n;
-      begin = sub * chunk;
-      end = min(V, begin + chunk);
-      if (work) {
-        if constexpr (FAST) {
-          if (begin < end) firstf = fcaf_load(K, (unsigned)min(begin + t, end - 1));
-        } else {
-          if (begin + t < end) first = fca_load<DIVC>(K, g, (unsigned)(begin + t));
-          first_pre = fca_prepare<DIVC>(g, first);
-        }
-      }
+    if (ls.nl < 0) break;
+    bool work = sub < L.nb;
+    if (ls.over) {   // a level change: tables, chunk and first record of the finer level
+      L = level_work(fa, m, ls.nl, slot, frs);
+      work = sub < L.nb;
+      if (work) request_first<DIVC, FAST, false>(first, L.K, L.g, L.c, t, true);
     }
     if (work) {   // block-uniform
-      g_u8 cur = as_global(F->img);
+      g_u8 cur = as_global(L.F->img);
       float sums[27];
-      fca_chunk_pass<DIVC, true, FAST, SAVEW, true>(a, K, g, cur, sh.newS, begin, end, first, firstf, first_pre, sums);
+      fca_chunk_pass<DIVC, true, FAST, SAVEW, true>(a, L.K, L.g, cur, sh.newS, L.c.begin, L.c.end, first.in, first.inf, first.pre, sums);
       ELLC_PTRACE(7, 0);
-      unsigned* out = (unsigned*)(a.partials + (size_t)(seq & 1) * fa.stride_part + ((size_t)b * ELLC_NBLK_MAX + sub) * ELLC_PART_STRIDE);
+      unsigned* out = (unsigned*)partial_record(fa, seq, b, sub);
       persist_store_record(sums, out, (epoch << 8) | (unsigned)(seq + 1));
       ELLC_PTRACE(10, 0);
     }
@@ -2927,47 +2781,25 @@ __device__ __forceinline__ void ica_accumulate_pixel(float (&acc)[6], const type
 template <bool FAST>
 __global__ __launch_bounds__(ELLC_GN_THREADS) void gn_ica_fused(const AlignState* src_state, const float* prev_part, int prev_nblk, FusedArgs fa) {
   const GnArgs& a = fa.g;   // leading scalars: preloaded kernel arguments, see gn_fca_fused
-  const int b = blockIdx.y, sub = blockIdx.x;
+  const BlockMap m = block_map(a.nblk, 0, 0);
+  const int b = m.b, sub = m.sub;
   const AlignState& src = src_state[b];
-  AlignState* dst = a.state + (size_t)((fa.seq + 1) & 1) * fa.stride_state + b;
   __shared__ SolveShared sh;
   const int t = threadIdx.x;
-  const bool writer = (sub == 0);
   const LevelGeom g = a.geom[a.level];
   const int slot = a.kf_slot[b];
   const KfLevelDev K = a.kf_tab[a.level * a.max_kf + slot];   // by value: uniform, lives in SGPRs
   const FrLevelDev& F = a.fr_tab[a.level * a.max_fr + a.fr_slot[b]];
   const int pending = src.pending;
   const int V = *as_global(K.count);
-  const double group_sum = partial_group_sum(prev_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE, prev_nblk);
-  const int chunk = (V + a.nblk - 1) / a.nblk;
-  const int begin = sub * chunk;
-  const int end = min(V, begin + chunk);
+  const double group_sum = partial_group_sum(pending_partials(prev_part, b), prev_nblk);
+  const Chunk c = m.chunk(fa.age_cum, V, a.nblk);
+  const int begin = c.begin, end = c.end;
   g_u8 cur = as_global(F.img);
   typename IcaInOf<FAST>::type first = ica_in_empty<FAST>();
   if (begin + t < end) first = ica_load_any<FAST>(K, (unsigned)(begin + t));
-  if (pending) {
-    const float* hinv = a.kf_tab[fa.prev_level * a.max_kf + slot].hinv;
-    solve_step<FAST>(sh, group_sum, 2, fa.prev_level, fa.early_exit, src, nullptr, hinv);
-  } else {
-    if (t < 6) sh.newpose[t] = src.pose[t];
-    if (t < 12) sh.newS[t] = src.S[t];
-    if (t == 0) { sh.weighted = src.weighted; sh.level_done = src.level_done; }
-    __syncthreads();
-  }
-  const int level_done = sh.level_done;
-  const bool skip = (level_done == a.level);
-  if (writer) {
-    if (t < 6) dst->pose[t] = sh.newpose[t];
-    if (t < 12) dst->S[t] = sh.newS[t];
-    if (t < ELLC_MAX_LEVELS) dst->iters[t] = src.iters[t] + ((pending && t == fa.prev_level) ? 1 : 0);
-    if (t == 0) {
-      dst->weighted = sh.weighted;
-      dst->level_done = level_done;
-      dst->pending = skip ? 0 : 1;
-    }
-  }
-  if (skip) return;
+  advance_pose<FAST>(sh, pending, group_sum, 2, fa.prev_level, fa.early_exit, src, &a.kf_tab[fa.prev_level * a.max_kf + slot].hinv);
+  if (publish_level_bound(sh, src, next_state(fa, b), sub == 0, pending, fa.prev_level, a.level)) return;
   float S[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) S[i] = sh.newS[i];
@@ -2979,8 +2811,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS) void gn_ica_fused(const AlignState
     ica_accumulate_pixel<FAST>(acc, first, g, cur, S);
     for (i += ELLC_GN_THREADS; i < end; i += ELLC_GN_THREADS) ica_accumulate_pixel<FAST>(acc, ica_load_any<FAST>(K, (unsigned)i), g, cur, S);
   }
-  float* out = a.partials + (size_t)(fa.seq & 1) * fa.stride_part + ((size_t)b * ELLC_NBLK_MAX + sub) * ELLC_PART_STRIDE;
-  block_reduce_store<6>(acc, out + 21);   // the b slots of the partial record; the H slots are not read by a mode-2 solve
+  block_reduce_store<6>(acc, partial_record(fa, fa.seq, b, sub) + 21);   // the b slots of the partial record; the H slots are not read by a mode-2 solve
 }
 
 // Final solve of a fused schedule: consumes the last pending partials; result always lands in state buffer 0. (The body of
@@ -2997,23 +2828,14 @@ __device__ __forceinline__ void fused_finish_body(const FusedArgs& fa, int b, co
   __shared__ int it_copy[ELLC_MAX_LEVELS];
   if (t < ELLC_MAX_LEVELS) it_copy[t] = src.iters[t];
   if (pending) {
-    const float* prev = a.partials + (size_t)((fa.seq + 1) & 1) * fa.stride_part + (size_t)b * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
     const float* hinv = fa.ica ? a.kf_tab[lvl * a.max_kf + a.kf_slot[b]].hinv : nullptr;
-    solve_step<FAST>(sh, partial_group_sum(prev, ADAPT ? fa.nblk_lv[lvl] : fa.prev_nblk), fa.ica ? 2 : 0, lvl, fa.early_exit, src, dst, hinv);
+    solve_step<FAST>(sh, partial_group_sum(pending_partials(fa, fa.seq, b), ADAPT ? fa.nblk_lv[lvl] : fa.prev_nblk), fa.ica ? 2 : 0, lvl, fa.early_exit, src, dst, hinv);
   } else {
-    if (t < 6) sh.newpose[t] = src.pose[t];
-    if (t < 12) sh.newS[t] = src.S[t];
-    if (t == 0) { sh.weighted = src.weighted; sh.level_done = src.level_done; }
-    __syncthreads();
+    carry_pose(sh, src);
   }
-  int nl = -1, nit = 0;
-  if (ADAPT && lvl >= 0) {
-    const int it = it_in + (pending ? 1 : 0);
-    const bool over = pending && (sh.level_done == lvl || it >= fa.max_it[lvl]);
-    nl = over ? lvl - 1 : lvl;
-    nit = over ? 0 : it;
-  }
-  const bool ended = nl < 0;
+  LevelStep ls = {false, -1, 0};
+  if (ADAPT && lvl >= 0) ls = level_step(sh, fa, pending, lvl, it_in);
+  const bool ended = ls.nl < 0;
   if (FAST && ended) {   // tolerance mode carries exp(pose) through the schedule; the twist is its log, taken once here
     if (t == 0) {
       float S[12], np[6];
@@ -3030,8 +2852,8 @@ __device__ __forceinline__ void fused_finish_body(const FusedArgs& fa, int b, co
     dst->weighted = sh.weighted;
     dst->level_done = sh.level_done;
     dst->pending = 0;
-    dst->cur_level = (ADAPT && lvl < 0) ? lvl : nl;   // -2 stays -2: the weights of this alignment were added by an earlier graph
-    dst->it_in_level = nit;
+    dst->cur_level = (ADAPT && lvl < 0) ? lvl : ls.nl;   // -2 stays -2: the weights of this alignment were added by an earlier graph
+    dst->it_in_level = ls.it;
   }
   if (fa.res) {
     // the record lives in pinned host memory and a host thread may be polling its pad word (resolve_batch): the fields first,
