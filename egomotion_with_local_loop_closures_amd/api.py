@@ -329,6 +329,17 @@ class Context:
         self._need_diag("ellc_debug_set_hinv_cache")
         self._ck(self._l.ellc_debug_set_hinv_cache(self.h, int(bool(on))), "ellc_debug_set_hinv_cache")
 
+    def debug_set_count_cache(self, on):
+        self._need_diag("ellc_debug_set_count_cache")
+        self._ck(self._l.ellc_debug_set_count_cache(self.h, int(bool(on))), "ellc_debug_set_count_cache")
+
+    def debug_count_cache_counters(self):
+        """(groups that compacted with a count launch, groups that compacted without one) so far."""
+        self._need_diag("ellc_debug_count_cache_counters")
+        a = C.c_longlong(0); b = C.c_longlong(0)
+        self._ck(self._l.ellc_debug_count_cache_counters(self.h, C.byref(a), C.byref(b)), "ellc_debug_count_cache_counters")
+        return a.value, b.value
+
     def debug_persist_counters(self):
         self._need_diag("ellc_debug_persist_counters")
         a = C.c_longlong(0); b = C.c_longlong(0); r = C.c_longlong(0)

@@ -67,6 +67,15 @@ struct ellc_ctx {
   // current (every writer of the planes clears it through invalidate_records): the next compaction builds the records only (r06)
   std::vector<char> kf_hinv_ok;
   bool hinv_cache = true;
+  // The compaction's count launch (prep_count) reads every level's depth plane of a slot to leave one integer per tile. Those
+  // integers depend on the depth planes alone. kf_counts_ok[slot]: KfLevelDev::tile_count of every level of the slot holds the plain
+  // counts a prep_count launch left, and the depth planes have not been written since (every writer clears it through
+  // invalidate_records; the count-free form, which stores tagged words there, clears it too): a group whose rebuilt slots all
+  // carry the mark launches prep_scatter alone, which reads the kept counts as it reads fresh ones
+  std::vector<char> kf_counts_ok;
+  bool count_cache = true;
+  bool cur_skip_count = false;   // the launch being enqueued relies on the kept counts: run_prep_levels launches no prep_count
+  long long groups_counted = 0, groups_count_skipped = 0;   // groups launch_group launched with / without a count launch (those that compact at all; the count-free form is neither)
   int cur_need = 0;   // record set of the launch being enqueued when it differs from need_of() (16: records without the H sums)
   bool cache_records = false;
   std::vector<std::array<int, ELLC_MAX_LEVELS>> kf_num_weights;
@@ -162,8 +171,8 @@ struct ellc_ctx {
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // captured launch sequences of ellc_align, keyed by (B, unique keyframes, mode, flags: save_weights | continuation | track | pollable,
-  // launches of a first state-driven graph, cfg.grid_batch, dense, cur_need, batch set): launch_align_graph
-  std::map<std::tuple<int, int, int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
+  // launches of a first state-driven graph, cfg.grid_batch, dense, cur_need, cur_skip_count, batch set): launch_align_graph
+  std::map<std::tuple<int, int, int, int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
   long long counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ELLC_CTR_* (ellc_abi.h): ellc_ctx_counters
   int poll_timeout_us = 2000;   // resolve_batch polls this long before it falls back to the event
   bool poll_results = true;     // resolve_batch polls the pinned result records of small single-stream batches; ELLC_NO_POLL=1 (diag)
@@ -232,7 +241,8 @@ struct ellc_ctx {
 namespace ellc {
 ellc_status fail(ellc_ctx* c, ellc_status s, const std::string& msg);
 ellc_status enqueue_eager_lists(ellc_ctx* c, int slot);   // the tracking call's lists of a keyframe slot, built behind the export of its planes
-void invalidate_records(ellc_ctx* c, int slot);   // cfg.cache_records: the slot's compact lists no longer match its planes
+void invalidate_records(ellc_ctx* c, int slot);   // the slot's planes are about to change: its compact lists, H^-1 and tile counts no longer match them
+void invalidate_lists(ellc_ctx* c, int slot);     // ... its weight planes only: the lists and H^-1, not the tile counts (they depend on the depth alone)
 #define ELLC_HIP(ctx, expr)                                                                               \
   do {                                                                                                    \
     hipError_t e__ = (expr);                                                                              \

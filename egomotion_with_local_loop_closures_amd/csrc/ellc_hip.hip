@@ -27,8 +27,12 @@ ellc_status fail(ellc_ctx* c, ellc_status s, const std::string& msg) {
 }
 
 // the compact lists of a keyframe slot no longer match its planes (cfg.cache_records)
-void invalidate_records(ellc_ctx* c, int slot) {
+void invalidate_lists(ellc_ctx* c, int slot) {
   if (slot >= 0 && slot < (int)c->kf_rec_tag.size()) { c->kf_rec_tag[slot] = 0; c->kf_rec_eager[slot] = 0; c->kf_hinv_ok[slot] = 0; }
+}
+void invalidate_records(ellc_ctx* c, int slot) {
+  invalidate_lists(c, slot);
+  if (slot >= 0 && slot < (int)c->kf_counts_ok.size()) c->kf_counts_ok[slot] = 0;
 }
 
 // blocking copy on the context's own stream: the legacy default stream would synchronise with every other stream of the
@@ -259,6 +263,11 @@ ellc_status build_depth_pyramid_from(ellc_ctx* c, int slot, int first_level) {
   return ELLC_OK;
 }
 
+// may a compaction of n_unique slots over all levels, launched kernel by kernel, take the count-free form (PrepArgs::lb_tag)?
+static bool prep_count_free(const ellc_ctx* c, int n_unique) {
+  return n_unique <= 2 && (c->tile_begin[c->L] - c->tile_begin[0]) * n_unique <= c->resident_blocks;
+}
+
 // compaction for pyramid levels lvl_lo .. lvl_hi of the listed keyframes, on stream `st`
 ellc_status run_prep_levels(ellc_ctx* c, int n_unique, int need, int lvl_lo, int lvl_hi, hipStream_t st) {
   if (lvl_lo > lvl_hi) return ELLC_OK;
@@ -275,10 +284,10 @@ ellc_status run_prep_levels(ellc_ctx* c, int n_unique, int need, int lvl_lo, int
   const int tiles = c->tile_begin[lvl_hi + 1] - c->tile_begin[lvl_lo];
   a.slot_inline = 0;
   a.lb_tag = 0;
-  if (c->direct_launch && n_unique <= 2 && lvl_lo == 0 && lvl_hi == c->L - 1 && tiles * n_unique <= c->resident_blocks) {
+  if (c->direct_launch && lvl_lo == 0 && lvl_hi == c->L - 1 && prep_count_free(c, n_unique)) {
     c->prep_tag = c->prep_tag % 0xfffffu + 1u;   // never 0, never what a count launch leaves in a word (its upper bits are 0)
-    a.lb_tag = c->prep_tag;
-  } else {
+    a.lb_tag = c->prep_tag;   // (tagged words replace the slots' plain counts: launch_group leaves kf_counts_ok cleared)
+  } else if (!c->cur_skip_count) {   // (cur_skip_count: the counts an earlier launch left in the slots are current, launch_group)
     hipLaunchKernelGGL(prep_count, dim3(tiles, n_unique), dim3(256), 0, st, a);
   }
   switch (need) {
@@ -639,6 +648,7 @@ ellc_status enqueue_eager_lists(ellc_ctx* c, int slot) {
   else if (need == 2) hipLaunchKernelGGL(prep_scatter<2>, dim3(tiles, 1), dim3(256), 0, c->stream, a);
   else return ELLC_OK;
   ELLC_HIP(c, hipGetLastError());
+  c->kf_counts_ok[slot] = 0;   // (tagged words in the slot's tile counts; the export that precedes this call has cleared it already)
   c->kf_rec_tag[slot] = need;
   c->kf_rec_eager[slot] = 1;
   return ELLC_OK;
@@ -1060,6 +1070,7 @@ ellc_status ellc_ctx_create(const ellc_config* cfg, ellc_ctx** out) {
   c->kf_rec_tag.assign(MK, 0);
   c->kf_rec_eager.assign(MK, 0);
   c->kf_hinv_ok.assign(MK, 0);
+  c->kf_counts_ok.assign(MK, 0);
   c->cache_records = cfg->cache_records != 0;
   c->kf_maxgrad.assign(MK, nullptr); c->fr_maxgrad.assign(MF, nullptr);
   c->kf_maxgrad_count.assign(MK, nullptr); c->fr_maxgrad_count.assign(MF, nullptr);
@@ -1300,6 +1311,19 @@ ellc_status ellc_debug_set_hinv_cache(ellc_ctx* c, int on) {
   if (!c) return ELLC_ERR_BAD_ARG;
   ELLC_ENTER(c);
   c->hinv_cache = on != 0;
+  return ELLC_OK;
+}
+ellc_status ellc_debug_set_count_cache(ellc_ctx* c, int on) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  ELLC_ENTER(c);
+  c->count_cache = on != 0;
+  return ELLC_OK;
+}
+ellc_status ellc_debug_count_cache_counters(ellc_ctx* c, long long* groups_counted, long long* groups_skipped) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  ELLC_ENTER(c);
+  if (groups_counted) *groups_counted = c->groups_counted;
+  if (groups_skipped) *groups_skipped = c->groups_count_skipped;
   return ELLC_OK;
 }
 ellc_status ellc_debug_persist_counters(ellc_ctx* c, long long* resident_launches, long long* abandoned_launches, long long* rejoined_blocks) {
@@ -1701,7 +1725,10 @@ static bool runs_dense(const ellc_ctx* c, int mode, int B, int save_weights) {
 // Enqueues the launch sequence of one batch on c->stream — replayed from a hipGraph captured on first use, keyed by
 // (B, unique keyframes, mode, save_weights, batch set, part). continuation: the rest of a state-driven schedule whose first
 // graph ended before every alignment had (enqueue_schedule_adaptive), for the batch set selected in the context.
-static ellc_status launch_align_graph(ellc_ctx* c, int B, int nu, int mode, int save_weights, int set, bool continuation) {
+// count_twin (launch_group, level-bound schedules that compact): a sequence captured for the first time is captured in both forms,
+// with and without the count launch — which of the two a later call replays depends on what was written to its slots in between,
+// and a caller that has rehearsed a call shape once must not meet a capture when the other form's turn comes.
+static ellc_status launch_align_graph(ellc_ctx* c, int B, int nu, int mode, int save_weights, int set, bool continuation, bool count_twin = false) {
   auto body = [&]() -> ellc_status {
     if (continuation) return enqueue_schedule_adaptive(c, B, save_weights, schedule_total_iters(c) - c->cur_adaptive_first, true);
     return enqueue_align_body(c, B, nu, mode, save_weights);
@@ -1721,11 +1748,12 @@ static ellc_status launch_align_graph(ellc_ctx* c, int B, int nu, int mode, int 
   const int first = schedule_is_adaptive(c, mode, B) ? c->cur_adaptive_first : 0;
   // (every choice in a field of its own: packed into one word, grid_batch << 12 reached the bits of the flags above it — a
   // grid_batch of 65536 made a kept-H^-1 ICA graph the twin of the one that rebuilds H^-1)
-  const auto key = std::make_tuple(B, continuation ? 0 : nu, mode,
-                                   (save_weights ? 1 : 0) | (continuation ? 2 : 0) | (c->track_call ? 4 : 0) | (c->cur_pollable ? 8 : 0), first,
-                                   c->cfg.grid_batch, c->cur_dense ? 1 : 0, c->cur_need, set);
-  auto it = c->graphs.find(key);
-  if (it == c->graphs.end()) {
+  auto key_of = [&]() {
+    return std::make_tuple(B, continuation ? 0 : nu, mode,
+                           (save_weights ? 1 : 0) | (continuation ? 2 : 0) | (c->track_call ? 4 : 0) | (c->cur_pollable ? 8 : 0), first,
+                           c->cfg.grid_batch, c->cur_dense ? 1 : 0, c->cur_need, c->cur_skip_count ? 1 : 0, set);
+  };
+  auto capture = [&]() -> ellc_status {   // the sequence of key_of() as it is now, into c->graphs
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     ELLC_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -1739,9 +1767,21 @@ static ellc_status launch_align_graph(ellc_ctx* c, int B, int nu, int mode, int 
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(c, ELLC_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    it = c->graphs.emplace(key, exec).first;
+    c->graphs.emplace(key_of(), exec);
+    return ELLC_OK;
+  };
+  const auto key = key_of();
+  if (c->graphs.find(key) == c->graphs.end()) {
+    ellc_status s = capture();
+    if (s != ELLC_OK) return s;
+    if (count_twin && c->count_cache && nu > 0 && !continuation) {
+      c->cur_skip_count = !c->cur_skip_count;
+      if (c->graphs.find(key_of()) == c->graphs.end()) s = capture();
+      c->cur_skip_count = !c->cur_skip_count;
+      if (s != ELLC_OK) return s;
+    }
   }
-  ELLC_HIP(c, hipGraphLaunch(it->second, c->stream));
+  ELLC_HIP(c, hipGraphLaunch(c->graphs.find(key)->second, c->stream));
   return ELLC_OK;
 }
 
@@ -1798,6 +1838,7 @@ static ellc_status resolve_batch(ellc_ctx* c, int set) {
   hipError_t ev = wait_batch_results(c, bs);   // the last kernel wrote bs.result_h (pinned, zero-copy)
   if (ev != hipSuccess) {
     std::fill(c->kf_rec_tag.begin(), c->kf_rec_tag.end(), 0);   // whatever was being built cannot be trusted
+    std::fill(c->kf_counts_ok.begin(), c->kf_counts_ok.end(), 0);
     return fail(c, ELLC_ERR_HIP, std::string("the batch failed on the device: ") + hipGetErrorString(ev));
   }
   if (!bs.adaptive) return ELLC_OK;
@@ -1864,6 +1905,12 @@ static ellc_status launch_group(ellc_ctx* c, int set) {
     for (int v : bs.built_slots) all_ok = all_ok && c->kf_hinv_ok[v];
     if (all_ok) need_run = 16;
   }
+  // the count launch: skipped when every slot that is rebuilt still holds the plain tile counts of its depth planes as they are
+  // (kf_counts_ok). All or nothing, as above: one stale slot and the launch counts for all of them. The count-free form of a
+  // tracking call (run_prep_levels) has no count launch to skip and stores tagged words over the counts.
+  const bool count_free = nu > 0 && launches_directly(c, bs.mode, B) && prep_count_free(c, nu);
+  bool skip_count = c->count_cache && nu > 0 && !count_free;
+  for (int v : bs.built_slots) skip_count = skip_count && c->kf_counts_ok[v];
   // stream
   bool busy[ellc_ctx::STREAMS] = {};
   for (int p = 0; p < ellc_ctx::SETS; p++)
@@ -1935,7 +1982,9 @@ static ellc_status launch_group(ellc_ctx* c, int set) {
     c->cur_pollable = bs.pollable;
     c->cur_dense = dense;
     c->cur_need = (need_run != need) ? need_run : 0;
-    const ellc_status s = launch_align_graph(c, B, nu, bs.mode, bs.save_weights, set, false);
+    c->cur_skip_count = skip_count;
+    const ellc_status s = launch_align_graph(c, B, nu, bs.mode, bs.save_weights, set, false, !dense);
+    c->cur_skip_count = false;
     c->cur_need = 0;
     c->cur_dense = false;
     c->cur_pollable = false;
@@ -1949,12 +1998,14 @@ static ellc_status launch_group(ellc_ctx* c, int set) {
     if (!c->done_deferred) ELLC_HIP(c, hipEventRecord(bs.done, c->stream));
   }
   for (int v : bs.built_slots) c->kf_rec_tag[v] = need;
+  for (int v : bs.built_slots) c->kf_counts_ok[v] = count_free ? 0 : 1;   // (left by this launch's prep_count, or already current)
+  if (nu > 0 && !count_free) (skip_count ? c->groups_count_skipped : c->groups_counted)++;
   if (need == 20)
     for (int v : bs.built_slots) c->kf_hinv_ok[v] = 1;   // (computed by this launch, or already current)
   if (saves)   // the weight planes change: lists that carry the saved weight (the constant-weight record sets) are stale, and so are the H^-1
     for (int v : bs.kf_slots) {
       c->kf_hinv_ok[v] = 0;
-      if (c->kf_rec_tag[v] != 8 && c->kf_rec_tag[v] != 2) invalidate_records(c, v);
+      if (c->kf_rec_tag[v] != 8 && c->kf_rec_tag[v] != 2) invalidate_lists(c, v);   // (not the tile counts: they do not depend on the weights)
     }
   bs.launched = true;
   bs.stream_idx = si;

@@ -78,6 +78,12 @@ ellc_status ellc_debug_set_fold_staging(ellc_ctx* ctx, int on);
  * per-call compaction then builds the records only (default on). 0: every compaction recomputes them, as up to r05 — the results
  * must not change by a bit (tests). */
 ellc_status ellc_debug_set_hinv_cache(ellc_ctx* ctx, int on);
+/* The compaction's count launch (prep_count) is left out while every slot a group rebuilds still holds the tile counts of its depth
+ * planes as they are (default on). 0: every compaction counts, as up to r06 - the results must not change by a bit (tests). */
+ellc_status ellc_debug_set_count_cache(ellc_ctx* ctx, int on);
+/* Groups of this context that compacted with a count launch, and without one because the kept counts were current. (A tracking
+ * call's count-free compaction and groups that build no lists are in neither.) Either pointer may be NULL. */
+ellc_status ellc_debug_count_cache_counters(ellc_ctx* ctx, long long* groups_counted, long long* groups_skipped);
 /* Resident launches of this context so far, how many of them the host had to finish with launches (abandoned), and — device-wide,
  * since the library was loaded — how many blocks were lapped and re-joined through the state line. Any pointer may be NULL. */
 ellc_status ellc_debug_persist_counters(ellc_ctx* ctx, long long* resident_launches, long long* abandoned_launches, long long* rejoined_blocks);
