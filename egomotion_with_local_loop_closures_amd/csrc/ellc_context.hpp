@@ -24,6 +24,50 @@ struct DepthSoA {   // DepthHypothesis.h:14-40, live fields, structure of arrays
   uint8_t* isValid = nullptr;
 };
 
+// Everything that shapes one enqueued launch sequence of the alignment path. Whoever starts a sequence (launch_group, the untracked
+// branch of align_enqueue_impl, resolve_batch for a continuation, the diagnostic hooks) builds one and passes it down by reference:
+// no function of the chain reads a choice from the context, and a new launch-time choice is a new member here (and, when captured
+// sequences differ by it, in GraphKey).
+struct LaunchPlan {
+  int B = 0;                  // alignments the sequence covers
+  int nu = 0;                 // unique keyframe slots whose compact lists it (re)builds (uniq_slot_h)
+  int mode = ELLC_MODE_FCA;
+  int save_weights = 0;
+  int set = 0;                // the batch set it runs in
+  bool continuation = false;  // the rest of a state-driven schedule whose first part ended early (no staging, no compaction)
+  bool dense = false;         // the list-free schedule (gn_fca_dense*)
+  int need = 0;               // the record set (PrepArgs::need) the compaction builds: need_of(), or 16 where the slots' H^-1 are current
+  bool skip_count = false;    // the compaction relies on the tile counts kept in the slots: no prep_count launch
+  bool pollable = false;      // the sequence ends in a finish kernel the host may poll (FusedArgs::host_polls)
+  bool resident = false;      // the state-driven schedule as one resident launch (gn_fca_persist)
+  int adaptive_first = 0;     // launches of the first part of a state-driven schedule (0: not that schedule, or the resident form)
+  bool direct = false;        // launched kernel by kernel, not replayed from a captured graph: the staging record goes through kernel arguments
+  bool track = false;         // the alignment belongs to ellc_track_frame (set_track_fields)
+  const void* count_valid = nullptr;   // ... whose count of the valid hypotheses the launch that stages the batch takes along
+  int count_n = 0;                     //     (the plane's size; 0: none)
+};
+
+// ellc_track_frame's request to align_enqueue_impl: the alignment is its own (LaunchPlan::track), and the count it would like taken along
+struct TrackRequest {
+  const void* count_valid;
+  int count_n;   // 0: no count
+};
+
+// What tells one captured launch sequence from another: the plan's members that change what is captured, and cfg.grid_batch (the
+// grids). resident, direct and the count request are absent: such sequences are never captured.
+struct GraphKey {
+  int B, nu, mode, save_weights, continuation, track, pollable, adaptive_first, grid_batch, dense, need, skip_count, set;
+  bool operator<(const GraphKey& o) const {
+    auto t = [](const GraphKey& k) {
+      return std::tie(k.B, k.nu, k.mode, k.save_weights, k.continuation, k.track, k.pollable, k.adaptive_first, k.grid_batch, k.dense, k.need, k.skip_count, k.set);
+    };
+    return t(*this) < t(o);
+  }
+};
+inline GraphKey graph_key(const LaunchPlan& p, int grid_batch) {
+  return GraphKey{p.B, p.nu, p.mode, p.save_weights ? 1 : 0, p.continuation, p.track, p.pollable, p.adaptive_first, grid_batch, p.dense, p.need, p.skip_count, p.set};
+}
+
 }  // namespace ellc
 
 struct ellc_ctx {
@@ -47,7 +91,6 @@ struct ellc_ctx {
   // counts them). A tolerance-mode FCA batch whose keyframes all carry the hint is aligned without compact lists (gn_fca_dense:
   // thread <-> pixel, the planes read directly). A hint, not a promise: pixels without depth are skipped where they occur.
   std::vector<char> kf_dense;
-  bool cur_dense = false;   // the schedule being enqueued is the list-free one
   bool dense_maps_off = false;   // ellc_ctx_set_dense_maps(1): dense maps take the list path too (bit-comparison runs)
 #ifdef ELLC_NO_DENSE_QUADS
   bool dense_quads = false;   // (A/B builds: the r05 kernel, one pixel per thread)
@@ -60,8 +103,7 @@ struct ellc_ctx {
   std::vector<int> kf_rec_tag;
   std::vector<char> kf_rec_eager;   // the slot's lists were built behind the depth map's export and are valid whatever cfg.cache_records says (enqueue_eager_lists)
   bool eager_lists = true;
-  bool fold_staging = true;   // a tracking call whose lists are there leaves its staging to the resident launch (PersistStage)
-  bool stage_folded = false;  // ... decided by enqueue_stage_in for the launch being enqueued
+  bool fold_staging = true;   // a tracking call whose lists are there leaves its staging to the resident launch (PersistStage, stage_folds)
   // ICA, tolerance mode: H^-1 per (slot, level) — the inverse of sum W J^T J over the keyframe's valid pixels (PixelWisePyramid.cpp:938-939)
   // — is a function of the keyframe's planes alone. kf_hinv_ok[slot]: the inverses the last compaction of the slot left are still
   // current (every writer of the planes clears it through invalidate_records): the next compaction builds the records only (r06)
@@ -74,9 +116,7 @@ struct ellc_ctx {
   // carry the mark launches prep_scatter alone, which reads the kept counts as it reads fresh ones
   std::vector<char> kf_counts_ok;
   bool count_cache = true;
-  bool cur_skip_count = false;   // the launch being enqueued relies on the kept counts: run_prep_levels launches no prep_count
   long long groups_counted = 0, groups_count_skipped = 0;   // groups launch_group launched with / without a count launch (those that compact at all; the count-free form is neither)
-  int cur_need = 0;   // record set of the launch being enqueued when it differs from need_of() (16: records without the H sums)
   bool cache_records = false;
   std::vector<std::array<int, ELLC_MAX_LEVELS>> kf_num_weights;
   std::vector<float*> kf_maxgrad, fr_maxgrad;
@@ -136,6 +176,14 @@ struct ellc_ctx {
     bool resident = false;                          //   as one resident launch (gn_fca_persist)
     int adaptive_first = 0;                         //   whose first graph holds this many launches
     bool pollable = false;                          // its finish kernel ordered its result records for a polling host (FusedArgs::host_polls)
+    // ellc_track_frame's alignment: the request (align_enqueue_impl) ...
+    bool track = false;                             // its finish kernel builds the observation's matrices and sets the depth stages' gate
+    const void* count_valid = nullptr;              // the validity plane whose count the launch that stages the batch is asked to take along
+    int count_n = 0;                                //   and its size (0: no count asked for)
+    // ... and what launch_group answers
+    bool count_rode = false;                        // that launch took the count along (a sequence launched kernel by kernel does)
+    bool done_by_caller = false;                    // `done` is left to the caller, who records it behind the depth stages
+    bool ride_weights = false;                      // the saved weights wait for the observation's selection launch (launch_observe)
     bool resolved = true;                           // `done` has been waited for and the continuation, if one was needed, has run
   } batch_set[SETS];
   hipStream_t batch_stream[STREAMS] = {};   // [0] = stream; the others are created when first needed
@@ -163,22 +211,18 @@ struct ellc_ctx {
   int persist_backoff = 0;                          // calls that still run as launches after a resident launch had to be abandoned
   long long persist_launches = 0, persist_abandoned = 0;   // resident launches so far / those the host had to finish with launches
   int persist_capacity = 0;                         // blocks of gn_fca_persist the device holds at once (occupancy x CUs)
-  bool cur_resident = false;                        // the schedule being enqueued is the resident form
   bool use_persist = true;                          // the state-driven schedule as one resident launch (gn_fca_persist)
   float* planes_d = nullptr;
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // captured launch sequences of ellc_align, keyed by (B, unique keyframes, mode, flags: save_weights | continuation | track | pollable,
-  // launches of a first state-driven graph, cfg.grid_batch, dense, cur_need, cur_skip_count, batch set): launch_align_graph
-  std::map<std::tuple<int, int, int, int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
+  // captured launch sequences, one per GraphKey (ellc::graph_key of the LaunchPlan): launch_align_graph
+  std::map<ellc::GraphKey, hipGraphExec_t> graphs;
   long long counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ELLC_CTR_* (ellc_abi.h): ellc_ctx_counters
   int poll_timeout_us = 2000;   // resolve_batch polls this long before it falls back to the event
   bool poll_results = true;     // resolve_batch polls the pinned result records of small single-stream batches; ELLC_NO_POLL=1 (diag)
   bool use_graph = true;
-  bool direct_launch = false;   // the launch sequence being enqueued is not captured: its staging record goes through kernel arguments
-  int direct_nu = 0;            //   unique keyframe slots whose lists it (re)builds
   int direct_max_batch = 0;     // level-bound launch sequences over at most this many alignments are launched kernel by kernel too (measured for B = 1: 0.225 ms either way)
   bool graph_adaptive = false;  // the state-driven (tracking) schedule as a captured graph too; ELLC_GRAPH_ADAPTIVE=1 (diag)
   bool age_balance = true;      // age-balanced split of full-round grids (FusedArgs::age_rounds); ELLC_NO_AGE_BALANCE=1 disables
@@ -187,7 +231,6 @@ struct ellc_ctx {
   bool use_adaptive = true;             // early-exit FCA schedules are state-driven (gn_fca_adaptive); ELLC_NO_ADAPTIVE=1 (diag) turns it off
   int adaptive_max_batch = 2;           //   for batches of at most this many alignments; ELLC_ADAPTIVE_MAX_BATCH (diag)
   int adaptive_hint = 0;                //   launches of the next first graph, from what the previous call needed (0: none yet)
-  int cur_adaptive_first = 0;           //   launches of the first graph of the schedule being enqueued / continued
   int adaptive_first_override = 0;      //   launches of the first graph; ELLC_ADAPTIVE_FIRST (diag)
   bool pipe = true;             // software-pipelined record loads in the fused FCA kernel (ELLC_PIPE=0 disables; r01: -10 % per launch at
                                 // 1280x960 dense where the records stream from HBM, neutral at 640x480 semi-dense)
@@ -221,18 +264,12 @@ struct ellc_ctx {
   // ellc_track_frame: the observation's matrices and the gate, built on the device behind the alignment; a host-visible record
   void* track_mats_d = nullptr;
   int* track_gate_d = nullptr;
-  const void* track_count_valid = nullptr;   // ellc_track_frame: the validity plane whose count the staging launch takes along
-  int track_count_n = 0;                     //   and its size (0: nothing pending)
-  bool cur_pollable = false;    // the launch sequence being enqueued ends in a finish kernel the host may poll
-  bool done_deferred = false;   // launch_group left the group's `done` event to its caller (ellc_track_frame records it behind the depth stages)
-  bool track_call = false;   // the alignment being enqueued belongs to ellc_track_frame (set_track_fields)
   int* seed_acc = nullptr;   // dm_count_valid_block: sum and arrival ticket (zero between calls)
   int obs_parity = 0;              // which of the two counter sets the next observation uses
   float2* obs_list_ep = nullptr;   // the epipolar direction of every list entry
   int *obs_list = nullptr, *obs_ctr = nullptr;   // work list of dm_observe_select / dm_observe_walk and its counters (zero between calls)
   int* track_h = nullptr;    // host-visible: [0] the valid hypotheses before the observation, [1] the number of the count that wrote it
-  bool track_ride_weights = false;   // the enqueued tracking call's saved weights wait for its selection launch (launch_observe)
-  bool ride_saved_weights = true;    //   (ellc_debug_set_fold_staging(0) keeps the launch of their own as well)
+  bool ride_saved_weights = true;   // a tracking call's saved weights wait for its selection launch (BatchSet::ride_weights; ellc_debug_set_fold_staging(0): a launch of their own)
   int track_counts = 0;      // counts launched so far (ellc_track_frame waits for [1] to say this one)
   int* track_dev_alias = nullptr;
   float Kinv[9], Kmat[9];
@@ -262,8 +299,8 @@ ellc_status enter(ellc_ctx* c, bool join);
 #define ELLC_ENTER(ctx) ELLC_ENTER_IMPL(ctx, true)          // runs on the main stream, behind the batches in flight
 #define ELLC_ENTER_BATCH(ctx) ELLC_ENTER_IMPL(ctx, false)   // ellc_align_enqueue / ellc_align_fetch
 
-int choose_nblk(const ellc_ctx* c, int level, int B);
-ellc_status run_prep(ellc_ctx* c, int n_unique, int need);
+int choose_nblk(const ellc_ctx* c, int level, int B, bool dense);   // dense: the grid of a list-free launch (callers outside the alignment path: false)
+ellc_status run_prep(ellc_ctx* c, const LaunchPlan& p);
 ellc_status build_depth_pyramid(ellc_ctx* c, int slot);
 ellc_status build_depth_pyramid_from(ellc_ctx* c, int slot, int first_level);
 ellc_status build_maxgrad(ellc_ctx* c, bool is_kf, int slot);

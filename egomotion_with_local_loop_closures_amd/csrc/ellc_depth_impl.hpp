@@ -287,7 +287,8 @@ static ObsArgs observe_args(const ellc_ctx* c, int frame_slot) {
 
 // observeDepthRow: candidate selection (a 32 x 8 tile per block), then the line stereo over the work list — a grid for the most
 // candidates there can be, the blocks past the list's end leave at once
-static void launch_observe(ellc_ctx* c, const ObsArgs& a, bool dev) {
+// ride_weights (dev only): the tracking call's saved weights wait for this selection launch (BatchSet::ride_weights)
+static void launch_observe(ellc_ctx* c, const ObsArgs& a, bool dev, bool ride_weights = false) {
   c->obs_parity ^= 1;   // (observe_args built `a` for the set this call uses; the next call takes the other)
   const dim3 tiles((a.W + 31) / 32, (a.H + 7) / 8), blk(256);
   const int most = std::max(0, a.W - 6) * std::max(0, a.H - 6);
@@ -295,8 +296,7 @@ static void launch_observe(ellc_ctx* c, const ObsArgs& a, bool dev) {
   RideWeights rw;
   if (dev) {
     dim3 grid = tiles;
-    if (c->track_ride_weights) {   // the tracking call's saved weights (enqueue_schedule_persist left them to this launch)
-      c->track_ride_weights = false;
+    if (ride_weights) {   // (enqueue_schedule_persist left them to this launch)
       rw.per_level = 128;
       rw.n = rw.per_level * c->L;
       rw.kf_tab = c->kf_tab_d; rw.kf_slot = c->kf_slot_d; rw.geom = c->geom_d; rw.state = c->state_d;
@@ -360,31 +360,24 @@ ellc_status ellc_track_frame(ellc_ctx* c, int frame_slot, const float* init_pose
   if (!rides)
     hipLaunchKernelGGL(dm_count_valid_block, dim3(std::max(1, ((n >> 4) + 1023) / 1024)), dim3(1024), 0, c->stream, c->dm_cur.isValid, n, c->seed_acc,
                        c->track_dev_alias);
-  c->done_deferred = false;
-  c->track_ride_weights = false;
-  c->track_call = true;   // this alignment's finish kernel builds the observation's matrices and sets the gate
-  c->track_count_valid = c->dm_cur.isValid;
-  c->track_count_n = rides ? n : 0;
-  s = ellc_align_enqueue(c, 1, &kf, &frame_slot, init_pose, ELLC_MODE_FCA, save_weights);   // one batch: it runs on the main stream
-  c->track_call = false;
-  const bool counted = !rides || c->track_count_n == 0;
-  c->track_count_n = 0;
+  // (this alignment's finish kernel builds the observation's matrices and sets the gate)
+  const TrackRequest request = {c->dm_cur.isValid, rides ? n : 0};
+  s = align_enqueue_impl(c, 1, &kf, &frame_slot, init_pose, ELLC_MODE_FCA, save_weights, true, &request);   // one batch: it runs on the main stream
   if (s != ELLC_OK) return s;
-  if (!counted) return fail(c, ELLC_ERR_HIP, "ellc_track_frame: the staging launch did not take the count along");
-  c->track_counts++;   // (one count per call, whichever launch carried it)
   const int set = c->inflight[0] / ellc_ctx::MAX_COALESCE;
-  ellc_ctx::BatchSet& bs = c->batch_set[set];
+  ellc_ctx::BatchSet& bs = c->batch_set[set];   // (launch_group left its answers here)
+  if (rides && !bs.count_rode) return fail(c, ELLC_ERR_HIP, "ellc_track_frame: the staging launch did not take the count along");
+  c->track_counts++;   // (one count per call, whichever launch carried it)
   // (launch_group may have left the group's `done` event to this call: it is recorded behind the depth stages, on every way out)
   struct DoneGuard {
     ellc_ctx* c; hipEvent_t ev; bool armed;
     ~DoneGuard() { if (armed) (void)hipEventRecord(ev, c->stream); }
-  } done_guard{c, bs.done, c->done_deferred};
-  c->done_deferred = false;
+  } done_guard{c, bs.done, bs.done_by_caller};
   if (!bs.launched || bs.stream_idx != 0) return fail(c, ELLC_ERR_HIP, "ellc_track_frame: the alignment did not take the main stream");
   ObsArgs a = observe_args(c, frame_slot);
   a.mats = (ObsMats*)c->track_mats_d;
   a.gate = c->track_gate_d;
-  launch_observe(c, a, true);
+  launch_observe(c, a, true, bs.ride_weights);
   ELLC_HIP(c, hipGetLastError());
   // doRegularization(false) :1627-1635 and updateDepthImage (an unchanged map exports the same planes): one launch
   if ((s = do_fill_regularize_and_update_depth_image(c, c->track_gate_d)) != ELLC_OK) return s;

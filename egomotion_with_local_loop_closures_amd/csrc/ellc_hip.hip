@@ -114,7 +114,7 @@ static bool dense_quads_at(const ellc_ctx* c, int level) {
   const LevelGeom& lg = c->geom_h[level];
   return c->fast && c->dense_quads && lg.cols % 4 == 0 && lg.sw % 4 == 0 && lg.cols >= 16 && lg.rows >= 8;   // (tolerance mode only)
 }
-int choose_nblk(const ellc_ctx* c, int level, int B) {
+int choose_nblk(const ellc_ctx* c, int level, int B, bool dense) {
 #ifdef ELLC_DIAG
   if (c->nblk_override[level] > 0) return std::min(ELLC_NBLK_MAX, c->nblk_override[level]);   // tuning knob (ELLC_NBLK=l0,l1,..)
 #endif
@@ -129,7 +129,7 @@ int choose_nblk(const ellc_ctx* c, int level, int B) {
   // pipeline's rate unchanged (tools/dbg/nblk_bench.sh); level 1 is slower with the full round)
   // (list-free launches with four pixels per thread hold three blocks per CU, not four: gn_fca_dense4)
   const int blocks_per_cu = c->use_fused ? 4 : 5;
-  const bool quads = c->cur_dense && dense_quads_at(c, level);
+  const bool quads = dense && dense_quads_at(c, level);
   const int resident = quads ? c->resident_blocks / blocks_per_cu * ELLC_QUAD_BLOCKS_PER_CU : c->resident_blocks;
   const int per_full = std::max(1, resident / B);
   const bool share = c->cfg.concurrent_batches > 1 && (double)n / (256.0 * per_full) < 100.0;
@@ -268,29 +268,37 @@ static bool prep_count_free(const ellc_ctx* c, int n_unique) {
   return n_unique <= 2 && (c->tile_begin[c->L] - c->tile_begin[0]) * n_unique <= c->resident_blocks;
 }
 
-// compaction for pyramid levels lvl_lo .. lvl_hi of the listed keyframes, on stream `st`
-ellc_status run_prep_levels(ellc_ctx* c, int n_unique, int need, int lvl_lo, int lvl_hi, hipStream_t st) {
-  if (lvl_lo > lvl_hi) return ELLC_OK;
+// The PrepArgs every compaction launch shares: record set `need` from level `lvl_lo` on, of the slots listed in uniq_slot_d, with a
+// count launch (lb_tag = 0; the count-free callers tag it themselves)
+static PrepArgs prep_args(const ellc_ctx* c, int need, int lvl_lo) {
   PrepArgs a;
   a.need = need;
   a.geom = c->geom_d;
   a.kf_tab = c->kf_tab_d;
   a.slots = c->uniq_slot_d;
+  a.slot_inline = 0;
   a.levels = c->L;
   a.max_kf = c->cfg.max_keyframes;
   for (int l = 0; l <= ELLC_MAX_LEVELS; l++) a.tile_begin[l] = c->tile_begin[std::min(l, c->L)];
   a.tile0 = c->tile_begin[lvl_lo];
   a.level0 = lvl_lo;
-  const int tiles = c->tile_begin[lvl_hi + 1] - c->tile_begin[lvl_lo];
-  a.slot_inline = 0;
   a.lb_tag = 0;
-  if (c->direct_launch && lvl_lo == 0 && lvl_hi == c->L - 1 && prep_count_free(c, n_unique)) {
+  return a;
+}
+
+// compaction (record set p.need) for pyramid levels lvl_lo .. lvl_hi of the p.nu listed keyframes, on stream `st`
+ellc_status run_prep_levels(ellc_ctx* c, const LaunchPlan& p, int lvl_lo, int lvl_hi, hipStream_t st) {
+  if (lvl_lo > lvl_hi) return ELLC_OK;
+  const int n_unique = p.nu;
+  PrepArgs a = prep_args(c, p.need, lvl_lo);
+  const int tiles = c->tile_begin[lvl_hi + 1] - c->tile_begin[lvl_lo];
+  if (p.direct && lvl_lo == 0 && lvl_hi == c->L - 1 && prep_count_free(c, n_unique)) {
     c->prep_tag = c->prep_tag % 0xfffffu + 1u;   // never 0, never what a count launch leaves in a word (its upper bits are 0)
     a.lb_tag = c->prep_tag;   // (tagged words replace the slots' plain counts: launch_group leaves kf_counts_ok cleared)
-  } else if (!c->cur_skip_count) {   // (cur_skip_count: the counts an earlier launch left in the slots are current, launch_group)
+  } else if (!p.skip_count) {   // (skip_count: the counts an earlier launch left in the slots are current, launch_group)
     hipLaunchKernelGGL(prep_count, dim3(tiles, n_unique), dim3(256), 0, st, a);
   }
-  switch (need) {
+  switch (p.need) {
     case 1: hipLaunchKernelGGL(prep_scatter<1>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;
     case 2: hipLaunchKernelGGL(prep_scatter<2>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;
     case 4: hipLaunchKernelGGL(prep_scatter<4>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;
@@ -303,22 +311,11 @@ ellc_status run_prep_levels(ellc_ctx* c, int n_unique, int need, int lvl_lo, int
   return ELLC_OK;
 }
 
-ellc_status run_prep(ellc_ctx* c, int n_unique, int need) { return run_prep_levels(c, n_unique, need, 0, c->L - 1, c->stream); }
+ellc_status run_prep(ellc_ctx* c, const LaunchPlan& p) { return run_prep_levels(c, p, 0, c->L - 1, c->stream); }
 
 // ICA: H^-1 of every (unique keyframe, level) from the per-tile sums the compaction (need bit 2) left behind
 static void enqueue_ica_hinv(ellc_ctx* c, int n_unique) {
-  PrepArgs a;
-  a.need = 4;
-  a.geom = c->geom_d;
-  a.kf_tab = c->kf_tab_d;
-  a.slots = c->uniq_slot_d;
-  a.slot_inline = 0;
-  a.levels = c->L;
-  a.max_kf = c->cfg.max_keyframes;
-  for (int l = 0; l <= ELLC_MAX_LEVELS; l++) a.tile_begin[l] = c->tile_begin[std::min(l, c->L)];
-  a.tile0 = 0;
-  a.level0 = 0;
-  a.lb_tag = 0;
+  const PrepArgs a = prep_args(c, 4, 0);
   hipLaunchKernelGGL(ica_hinv, dim3(c->L, n_unique), dim3(ELLC_SOLVE_THREADS), 0, c->stream, a);
 }
 
@@ -334,7 +331,7 @@ static int grid_batch(const ellc_ctx* c, int B) {
   return (c->coalesce > 1 && B % c->cfg.max_batch == 0) ? c->cfg.max_batch * c->coalesce : B;
 }
 
-static GnArgs make_gn_args(ellc_ctx* c, int level, int B, int save_w, float* planes) {
+static GnArgs make_gn_args(ellc_ctx* c, const LaunchPlan& p, int level, int save_w, float* planes) {
   GnArgs a;
   a.geom = c->geom_d;
   a.kf_tab = c->kf_tab_d;
@@ -347,7 +344,7 @@ static GnArgs make_gn_args(ellc_ctx* c, int level, int B, int save_w, float* pla
   a.level = level;
   a.max_kf = c->cfg.max_keyframes;
   a.max_fr = c->cfg.max_frames;
-  a.nblk = choose_nblk(c, level, grid_batch(c, B));
+  a.nblk = choose_nblk(c, level, grid_batch(c, p.B), p.dense);
   a.save_w = save_w;
   return a;
 }
@@ -470,27 +467,29 @@ static ellc_status stage_batch(ellc_ctx* c, int B, const int* kf_slots, const in
 }
 
 // device copy of the staged batch description, as a kernel reading the pinned record (part of the captured graph)
-static void enqueue_stage_in(ellc_ctx* c, int B) {
-  c->stage_folded = false;
-  if (c->direct_launch && B <= 2 && c->cur_resident && c->direct_nu == 0 && c->fold_staging) {
-    // the tracking call whose lists are already there (built behind the export): no staging launch — the resident launch builds the
-    // state records itself and takes the batch description and the seeds count along (PersistStage, enqueue_schedule_persist)
-    c->stage_folded = true;
-    return;
-  }
-  if (c->direct_launch && B <= 2) {   // not being captured: the record travels in the kernel arguments (stage_in_args)
+// the tracking call whose lists are already there (built behind the export): no staging launch — the resident launch builds the
+// state records itself and takes the batch description and the seeds count along (PersistStage, enqueue_schedule_persist)
+static bool stage_folds(const ellc_ctx* c, const LaunchPlan& p) {
+  return p.direct && p.B <= 2 && p.resident && p.nu == 0 && c->fold_staging;
+}
+// does the sequence's staging (its own launch, or the resident launch it is folded into) take the tracking call's count along?
+static bool count_rides(const LaunchPlan& p) { return p.direct && p.B <= 2 && p.count_n > 0; }
+
+// B: the alignment states to initialise (p.B; 0: staging only)
+static void enqueue_stage_in(ellc_ctx* c, const LaunchPlan& p, int B) {
+  if (stage_folds(c, p)) return;
+  if (p.direct && B <= 2) {   // not being captured: the record travels in the kernel arguments (stage_in_args)
     StageSmall ss;
     for (int b = 0; b < 2; b++) {
       ss.kf[b] = b < B ? c->kf_slot_h[b] : 0;
       ss.fr[b] = b < B ? c->fr_slot_h[b] : 0;
-      ss.uniq[b] = b < c->direct_nu ? c->uniq_slot_h[b] : 0;   // the slots whose lists this launch (re)builds (launch_group)
+      ss.uniq[b] = b < p.nu ? c->uniq_slot_h[b] : 0;   // the slots whose lists this launch (re)builds (launch_group)
       for (int i = 0; i < 6; i++) ss.pose[b * 6 + i] = b < B ? c->init_pose_h[b * 6 + i] : 0.0f;
     }
     // (ellc_track_frame's count of the valid hypotheses rides along in further blocks of the same launch)
-    const int count_blocks = c->track_count_n > 0 ? std::max(1, ((c->track_count_n >> 4) + 1023) / 1024) : 0;
-    hipLaunchKernelGGL(stage_in_args, dim3(1 + count_blocks), dim3(1024), 0, c->stream, c->kf_slot_d, ss, B, c->direct_nu, c->group_cap, c->state_d, c->L - 1,
-                       (const uint8_t*)c->track_count_valid, c->track_count_n, c->seed_acc, c->track_dev_alias);
-    c->track_count_n = 0;   // done (the caller launches the count by itself if this launch did not take it)
+    const int count_blocks = p.count_n > 0 ? std::max(1, ((p.count_n >> 4) + 1023) / 1024) : 0;
+    hipLaunchKernelGGL(stage_in_args, dim3(1 + count_blocks), dim3(1024), 0, c->stream, c->kf_slot_d, ss, B, p.nu, c->group_cap, c->state_d, c->L - 1,
+                       (const uint8_t*)p.count_valid, p.count_n, c->seed_acc, c->track_dev_alias);
     return;
   }
   const int n = 9 * c->group_cap;
@@ -523,17 +522,16 @@ static void set_age_split(ellc_ctx* c, FusedArgs& fa, int B) {
   fa.age_rounds = R;
 }
 
-static void set_track_fields(const ellc_ctx* c, FusedArgs& fa, bool continuation);
 static const char* launch_ica_fused(ellc_ctx* c, dim3 grd, dim3 blk, const FusedArgs& fa, hipStream_t st);
 
-// The one kernel launch of a level-bound schedule at fa.g.level (enqueue_schedule_fused, enqueue_schedule_ica_fused; the same
+// The one kernel launch of a level-bound schedule at fa.g.level (enqueue_schedule_level_bound; the same
 // choice in ellc_profile_gn_kernel and ellc_debug_schedule_sums): which kernel runs for this context, batch and record set.
 // Returns the kernel's name (the diagnostic hooks report it).
-static const char* launch_level_bound(ellc_ctx* c, dim3 grd, dim3 blk, const FusedArgs& fa, hipStream_t st) {
+static const char* launch_level_bound(ellc_ctx* c, const LaunchPlan& p, dim3 grd, dim3 blk, const FusedArgs& fa, hipStream_t st) {
   const AlignState* src_state = fa.g.state + (size_t)(fa.seq & 1) * fa.stride_state;
   const float* prev_part = fa.g.partials + (size_t)((fa.seq + 1) & 1) * fa.stride_part;
   if (fa.ica) return launch_ica_fused(c, grd, blk, fa, st);   // constant weights: b sums only, H^-1 from the keyframe slot
-  if (c->cur_dense) {   // dense maps: no compact lists (gn_fca_dense; launch_group decided)
+  if (p.dense) {   // dense maps: no compact lists (gn_fca_dense; launch_group decided)
     if (!c->fast) {   // the exact mode: a thread per pixel, the planes and the slot's 1 / Z plane in double (no 20-byte records)
       if (c->geom_h[0].divc_ok) hipLaunchKernelGGL(gn_fca_dense_x<true>, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
       else hipLaunchKernelGGL(gn_fca_dense_x<false>, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa.g.nblk, fa.age_rounds, fa);
@@ -562,31 +560,49 @@ static const char* launch_level_bound(ellc_ctx* c, dim3 grd, dim3 blk, const Fus
   }
 }
 
-// The FusedArgs of a level-bound schedule (FCA, or ICA with ica = true) before its first launch: nothing pending.
-static FusedArgs level_bound_args(ellc_ctx* c, int B, int save_weights, bool ica) {
+// ellc_track_frame's alignment (p.track): that schedule's finish kernel also builds the observation's matrices and sets the depth
+// stages' gate. (A continuation does not: the host then runs the depth stages the usual way.)
+static void set_track_fields(const ellc_ctx* c, const LaunchPlan& p, FusedArgs& fa) {
+  fa.host_polls = p.pollable ? 1 : 0;
+  const bool on = p.track && !p.continuation;
+  fa.track_mats = on ? (ObsMats*)c->track_mats_d : nullptr;
+  fa.track_gate = on ? c->track_gate_d : nullptr;
+  for (int i = 0; i < 9; i++) fa.track_K[i] = c->Kmat[i];
+}
+
+// The FusedArgs of a schedule before its first launch: nothing pending, level 0's grid. What the forms differ in: ica (no saved
+// weights then), xcd_map, and the state-driven forms' blocks and iteration caps per level with the grid's x extent (per_level;
+// the level-bound forms carry 1 / 0 / 1) and, the resident form, its abort words.
+static FusedArgs fused_args(ellc_ctx* c, const LaunchPlan& p, bool ica, int xcd_map, bool per_level, unsigned* persist_bar = nullptr) {
   FusedArgs fa;
-  fa.continuation = 0;
-  set_track_fields(c, fa, false);
+  fa.continuation = p.continuation ? 1 : 0;
+  set_track_fields(c, p, fa);
   fa.seq = 0;
   fa.prev_level = -1;
   fa.prev_nblk = 0;
   fa.early_exit = c->cfg.early_exit;
   fa.stride_state = c->group_cap;
   fa.stride_part = (size_t)c->group_cap * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
-  fa.g = make_gn_args(c, 0, B, (save_weights && !ica) ? 1 : 0, nullptr);
+  fa.g = make_gn_args(c, p, 0, (p.save_weights && !ica) ? 1 : 0, nullptr);
   fa.res = c->result_dev_alias;
   fa.ica = ica ? 1 : 0;
-  fa.xcd_map = (!ica && B % 8 == 0) ? 1 : 0;
-  for (int l = 0; l < ELLC_MAX_LEVELS; l++) { fa.nblk_lv[l] = 1; fa.max_it[l] = 0; }
+  fa.xcd_map = xcd_map;
   fa.nblk_grid = 1;
+  for (int l = 0; l < ELLC_MAX_LEVELS; l++) {
+    const bool on = per_level && l < c->L;
+    fa.nblk_lv[l] = on ? choose_nblk(c, l, grid_batch(c, p.B), p.dense) : 1;
+    fa.max_it[l] = on ? c->cfg.max_iter[l] : 0;
+    fa.nblk_grid = std::max(fa.nblk_grid, fa.nblk_lv[l]);
+  }
+  fa.persist_bar = persist_bar;
   fa.age_rounds = 0;
   for (int i = 0; i < 5; i++) fa.age_cum[i] = 0;
   return fa;
 }
-// ... and its launches at `level`: the grid (make_gn_args: the batch's grid size, cur_dense) and, FCA only, the age-balanced split
-static void level_bound_level(ellc_ctx* c, FusedArgs& fa, int level, int B) {
-  fa.g = make_gn_args(c, level, B, fa.g.save_w, nullptr);
-  if (!fa.ica) set_age_split(c, fa, B);
+// a level-bound schedule's launches at `level`: the grid (make_gn_args: the batch's grid size, p.dense) and, FCA only, the age-balanced split
+static void level_bound_level(ellc_ctx* c, const LaunchPlan& p, FusedArgs& fa, int level) {
+  fa.g = make_gn_args(c, p, level, fa.g.save_w, nullptr);
+  if (!fa.ica) set_age_split(c, fa, p.B);
 }
 
 static void launch_finish(ellc_ctx* c, int B, const FusedArgs& fa, bool adaptive = false) {
@@ -631,17 +647,9 @@ ellc_status enqueue_eager_lists(ellc_ctx* c, int slot) {
   const int tiles = c->tile_begin[c->L] - c->tile_begin[0];
   if (tiles > c->resident_blocks) return ELLC_OK;   // (the count-free form needs the tiles a block waits for resident or done)
   const int need = c->fast ? 8 : 2;   // the FCA record set of the context's arithmetic mode (need_of)
-  PrepArgs a;
-  a.need = need;
-  a.geom = c->geom_d;
-  a.kf_tab = c->kf_tab_d;
+  PrepArgs a = prep_args(c, need, 0);
   a.slots = nullptr;
   a.slot_inline = slot;
-  a.levels = c->L;
-  a.max_kf = c->cfg.max_keyframes;
-  for (int l = 0; l <= ELLC_MAX_LEVELS; l++) a.tile_begin[l] = c->tile_begin[std::min(l, c->L)];
-  a.tile0 = c->tile_begin[0];
-  a.level0 = 0;
   c->prep_tag = c->prep_tag % 0xfffffu + 1u;
   a.lb_tag = c->prep_tag;
   if (need == 8) hipLaunchKernelGGL(prep_scatter<8>, dim3(tiles, 1), dim3(256), 0, c->stream, a);
@@ -663,24 +671,14 @@ static int schedule_total_iters(const ellc_ctx* c) {
 // continuation holds the rest
 // — or, once the context has run such a call, what the previous one needed plus two (adaptive_hint: consecutive frames of a
 // tracked sequence need about the same; r03: 20 launches of which a tracked frame used 15, the other five still cost 4.8 us each)
-static int adaptive_first_launches(const ellc_ctx* c, int B) {
-  if (c->cur_resident) return 0;   // one resident launch runs the whole schedule; a continuation (only after an abandoned launch) holds all of it
+static int adaptive_first_launches(const ellc_ctx* c, bool resident) {
+  if (resident) return 0;   // one resident launch runs the whole schedule; a continuation (only after an abandoned launch) holds all of it
   const int total = schedule_total_iters(c);
   int first = c->adaptive_hint > 0 ? c->adaptive_hint : (total * 5 + 7) / 8;
 #ifdef ELLC_DIAG
   if (c->adaptive_first_override > 0) first = c->adaptive_first_override;   // ELLC_ADAPTIVE_FIRST
 #endif
   return std::min(total, std::max(c->L, first));
-}
-
-// ellc_track_frame marks the alignment it enqueues (c->track_call): that schedule's finish kernel also builds the observation's
-// matrices and sets the depth stages' gate. (A continuation does not: the host then runs the depth stages the usual way.)
-static void set_track_fields(const ellc_ctx* c, FusedArgs& fa, bool continuation) {
-  fa.host_polls = c->cur_pollable ? 1 : 0;
-  const bool on = c->track_call && !continuation;
-  fa.track_mats = on ? (ObsMats*)c->track_mats_d : nullptr;
-  fa.track_gate = on ? c->track_gate_d : nullptr;
-  for (int i = 0; i < 9; i++) fa.track_K[i] = c->Kmat[i];
 }
 
 // State-driven FCA schedule: `launches` launches of gn_fca_adaptive and the finish kernel. continuation: the records were
@@ -712,40 +710,24 @@ static bool may_run_resident(ellc_ctx* c, int mode, int B) {
 // blocks a resident launch of B alignments needs on the device at once
 static int persist_blocks(ellc_ctx* c, int B) {
   int G = 1;
-  for (int l = 0; l < c->L; l++) G = std::max(G, choose_nblk(c, l, grid_batch(c, B)));
+  for (int l = 0; l < c->L; l++) G = std::max(G, choose_nblk(c, l, grid_batch(c, B), false));   // (the state-driven schedule is never list-free)
   return G * B;
 }
-static ellc_status enqueue_schedule_persist(ellc_ctx* c, int B, int save_weights) {
-  FusedArgs fa;
-  fa.continuation = 0;
-  set_track_fields(c, fa, false);
-  fa.seq = 0;
-  fa.prev_level = -1;
-  fa.prev_nblk = 0;
-  fa.early_exit = c->cfg.early_exit;
-  fa.stride_state = c->group_cap;
-  fa.stride_part = (size_t)c->group_cap * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
-  fa.g = make_gn_args(c, 0, B, save_weights ? 1 : 0, nullptr);
-  fa.res = c->result_dev_alias;
-  fa.ica = 0;
-  fa.xcd_map = 0;
-  fa.age_rounds = 0;
-  for (int i = 0; i < 5; i++) fa.age_cum[i] = 0;
-  int G = 1;
-  for (int l = 0; l < ELLC_MAX_LEVELS; l++) {
-    fa.nblk_lv[l] = l < c->L ? choose_nblk(c, l, grid_batch(c, B)) : 1;
-    fa.max_it[l] = l < c->L ? c->cfg.max_iter[l] : 0;
-    G = std::max(G, fa.nblk_lv[l]);
-  }
-  fa.nblk_grid = G;
-  fa.persist_bar = c->persist_bar_d;
+// do the saved weights of the sequence wait for the tracking call's selection launch (BatchSet::ride_weights)? The resident form only
+static bool weights_ride(const ellc_ctx* c, const LaunchPlan& p) {
+  return p.resident && !p.continuation && p.save_weights && p.track && p.B == 1 && c->ride_saved_weights;
+}
+static ellc_status enqueue_schedule_persist(ellc_ctx* c, const LaunchPlan& p) {
+  const int B = p.B, save_weights = p.save_weights;
+  const FusedArgs fa = fused_args(c, p, false, 0, true, c->persist_bar_d);
+  const int G = fa.nblk_grid;
   const int max_rounds = persist_rounds(c);   // <= 255 (may_run_resident)
   const unsigned epoch = (++c->persist_epoch) & 0xffffffu;   // the records of earlier calls never match (the round sits in the low byte)
   c->persist_launches++;
   PersistStage ps;
   std::memset(&ps, 0, sizeof(ps));
   ps.persist_blocks = G;
-  if (c->stage_folded) {   // (enqueue_stage_in left the staging to this launch)
+  if (stage_folds(c, p)) {   // (enqueue_stage_in left the staging to this launch)
     ps.on = 1;
     for (int b = 0; b < 2; b++) {
       ps.s.kf[b] = b < B ? c->kf_slot_h[b] : 0;
@@ -756,13 +738,11 @@ static ellc_status enqueue_schedule_persist(ellc_ctx* c, int B, int save_weights
     ps.dst = c->kf_slot_d;
     ps.cap = c->group_cap;
     ps.top_level = c->L - 1;
-    ps.count_valid = (const uint8_t*)c->track_count_valid;
-    ps.count_n = c->track_count_n;
-    ps.count_blocks = c->track_count_n > 0 ? std::max(1, ((c->track_count_n >> 4) + ELLC_GN_THREADS - 1) / ELLC_GN_THREADS) : 0;
+    ps.count_valid = (const uint8_t*)p.count_valid;
+    ps.count_n = p.count_n;
+    ps.count_blocks = p.count_n > 0 ? std::max(1, ((p.count_n >> 4) + ELLC_GN_THREADS - 1) / ELLC_GN_THREADS) : 0;
     ps.count_acc = c->seed_acc;
     ps.count_host = c->track_dev_alias;
-    c->track_count_n = 0;   // (taken along)
-    c->stage_folded = false;
   }
   const dim3 grd(G + ps.count_blocks, B), blk(ELLC_GN_THREADS);
   if (c->fast) {
@@ -774,39 +754,18 @@ static ellc_status enqueue_schedule_persist(ellc_ctx* c, int B, int save_weights
     hipLaunchKernelGGL((gn_fca_persist<false, false, -1>), grd, blk, 0, c->stream, fa, max_rounds, epoch, c->persist_spin_limit, c->persist_delay_from, c->persist_delay_polls, ps);
   }
   // (no finish kernel: the launch's first block per alignment has written the final record, the result and the tracking fields)
-  if (save_weights) {
-    // (the tracking call: its observation's selection launch, the next one in this stream, takes them along — launch_observe)
-    if (c->track_call && B == 1 && c->ride_saved_weights) c->track_ride_weights = true;
-    else launch_add_saved_weights(c, B);
-  }
+  // (the tracking call's saved weights: its observation's selection launch, the next one in this stream, takes them along — launch_observe)
+  if (save_weights && !weights_ride(c, p)) launch_add_saved_weights(c, B);
   ELLC_HIP(c, hipGetLastError());
   return ELLC_OK;
 }
 
-static ellc_status enqueue_schedule_adaptive(ellc_ctx* c, int B, int save_weights, int launches, bool continuation = false) {
-  if (!continuation && c->cur_resident) return enqueue_schedule_persist(c, B, save_weights);
-  FusedArgs fa;
-  fa.continuation = continuation ? 1 : 0;
-  set_track_fields(c, fa, continuation);
-  fa.seq = 0;
-  fa.prev_level = -1;
-  fa.prev_nblk = 0;
-  fa.early_exit = c->cfg.early_exit;
-  fa.stride_state = c->group_cap;
-  fa.stride_part = (size_t)c->group_cap * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
-  fa.g = make_gn_args(c, 0, B, save_weights ? 1 : 0, nullptr);
-  fa.res = c->result_dev_alias;
-  fa.ica = 0;
-  fa.xcd_map = (B % 8 == 0) ? 1 : 0;
-  fa.age_rounds = 0;
-  for (int i = 0; i < 5; i++) fa.age_cum[i] = 0;
-  int grid_x = 1;
-  for (int l = 0; l < ELLC_MAX_LEVELS; l++) {
-    fa.nblk_lv[l] = l < c->L ? choose_nblk(c, l, grid_batch(c, B)) : 1;
-    fa.max_it[l] = l < c->L ? c->cfg.max_iter[l] : 0;
-    grid_x = std::max(grid_x, fa.nblk_lv[l]);
-  }
-  fa.nblk_grid = grid_x;
+static ellc_status enqueue_schedule_adaptive(ellc_ctx* c, const LaunchPlan& p) {
+  if (!p.continuation && p.resident) return enqueue_schedule_persist(c, p);
+  const int B = p.B, save_weights = p.save_weights;
+  const int launches = p.continuation ? schedule_total_iters(c) - p.adaptive_first : p.adaptive_first;
+  FusedArgs fa = fused_args(c, p, false, (B % 8 == 0) ? 1 : 0, true);
+  const int grid_x = fa.nblk_grid;
   const dim3 grd(grid_x, B), blk(ELLC_GN_THREADS);
   for (int i = 0; i < launches; i++) {
     const AlignState* src_state = fa.g.state + (size_t)(fa.seq & 1) * fa.stride_state;
@@ -827,30 +786,31 @@ static ellc_status enqueue_schedule_adaptive(ellc_ctx* c, int B, int save_weight
   return ELLC_OK;
 }
 
-// FCA schedule: the solve of iteration n is folded into the prologue of launch n+1 (gn_fca_fused): one launch per
+// The level-bound schedules, FCA and (ica) constant-weight. FCA: the solve of iteration n is folded into the prologue of launch n+1 (gn_fca_fused): one launch per
 // Gauss-Newton iteration plus one final solve. (r01 experiments that did not pay and were removed: cutting the batch
 // into independent chains on parallel graph branches — the queues interleave poorly and the per-node submission cost
 // dominates; compacting the fine levels on a second stream beside the coarse iterations — fork/join cost more than the
 // overlap gave; a one-block-per-alignment kernel running all coarse iterations — one CU is VALU-bound on a level.)
-static ellc_status enqueue_schedule_fused(ellc_ctx* c, int B, int save_weights) {
-  FusedArgs fa = level_bound_args(c, B, save_weights, false);
+static ellc_status enqueue_schedule_level_bound(ellc_ctx* c, const LaunchPlan& p, bool ica) {
+  const int B = p.B;
+  FusedArgs fa = fused_args(c, p, ica, (!ica && B % 8 == 0) ? 1 : 0, false);
   for (int level = c->L - 1; level >= 0; level--) {
-    level_bound_level(c, fa, level, B);
+    level_bound_level(c, p, fa, level);
     const dim3 grd(fa.g.nblk, B), blk(ELLC_GN_THREADS);
     for (int it = 0; it < c->cfg.max_iter[level]; it++) {
-      launch_level_bound(c, grd, blk, fa, c->stream);
+      launch_level_bound(c, p, grd, blk, fa, c->stream);
       fa.prev_level = level;
       fa.prev_nblk = fa.g.nblk;
       fa.seq++;
     }
   }
   launch_finish(c, B, fa);
-  if (save_weights) launch_add_saved_weights(c, B);
+  if (p.save_weights && !ica) launch_add_saved_weights(c, B);   // (saved weights: FCA only)
   ELLC_HIP(c, hipGetLastError());
   return ELLC_OK;
 }
 
-// Constant-weight (ICA) schedule in the fused form: H^-1 per (keyframe, level) comes from the compaction (ica_hinv), every
+// The constant-weight (ICA) launch of the level-bound schedule: H^-1 per (keyframe, level) comes from the compaction (ica_hinv), every
 // launch solves the previous launch's b sums in its prologue: one launch per iteration plus the final solve.
 // (defined here, not in launch_level_bound: the kernels' order in the code object follows where they are first launched)
 static const char* launch_ica_fused(ellc_ctx* c, dim3 grd, dim3 blk, const FusedArgs& fa, hipStream_t st) {
@@ -860,30 +820,14 @@ static const char* launch_ica_fused(ellc_ctx* c, dim3 grd, dim3 blk, const Fused
   else hipLaunchKernelGGL(gn_ica_fused<false>, grd, blk, 0, st, src_state, prev_part, fa.prev_nblk, fa);
   return c->fast ? "gn_ica_fused<fast>" : "gn_ica_fused<exact>";
 }
-static ellc_status enqueue_schedule_ica_fused(ellc_ctx* c, int B) {
-  FusedArgs fa = level_bound_args(c, B, 0, true);
-  for (int level = c->L - 1; level >= 0; level--) {
-    level_bound_level(c, fa, level, B);
-    const dim3 grd(fa.g.nblk, B), blk(ELLC_GN_THREADS);
-    for (int it = 0; it < c->cfg.max_iter[level]; it++) {
-      launch_level_bound(c, grd, blk, fa, c->stream);
-      fa.prev_level = level;
-      fa.prev_nblk = fa.g.nblk;
-      fa.seq++;
-    }
-  }
-  launch_finish(c, B, fa);
-  ELLC_HIP(c, hipGetLastError());
-  return ELLC_OK;
-}
 
 // the level / iteration schedule of GetImagePoseEstimate (ImageFunc.cpp:150-292) as a launch sequence
-static ellc_status enqueue_schedule(ellc_ctx* c, int B, int mode, int save_weights) {
-  if (schedule_is_adaptive(c, mode, B)) return enqueue_schedule_adaptive(c, B, save_weights, c->cur_adaptive_first);
-  if (mode == ELLC_MODE_FCA && c->use_fused) return enqueue_schedule_fused(c, B, save_weights);
-  if (mode == ELLC_MODE_ICA && c->use_fused) return enqueue_schedule_ica_fused(c, B);
+static ellc_status enqueue_schedule(ellc_ctx* c, const LaunchPlan& p) {
+  const int B = p.B, mode = p.mode, save_weights = p.save_weights;
+  if (schedule_is_adaptive(c, mode, B)) return enqueue_schedule_adaptive(c, p);
+  if (c->use_fused) return enqueue_schedule_level_bound(c, p, mode == ELLC_MODE_ICA);
   for (int level = c->L - 1; level >= 0; level--) {
-    GnArgs a = make_gn_args(c, level, B, (save_weights && mode == ELLC_MODE_FCA) ? 1 : 0, nullptr);
+    GnArgs a = make_gn_args(c, p, level, (save_weights && mode == ELLC_MODE_FCA) ? 1 : 0, nullptr);
     const dim3 grd(a.nblk, B), blk(ELLC_GN_THREADS);
     for (int it = 0; it < c->cfg.max_iter[level]; it++) {
       if (mode == ELLC_MODE_FCA) {
@@ -1693,71 +1637,75 @@ static int need_of(const ellc_ctx* c, int mode) {
   return mode == ELLC_MODE_ICA ? (c->use_fused ? (c->fast ? 20 : 4) : 1) : (c->fast ? 8 : 2);
 }
 
-// nu: keyframe slots whose compact lists are (re)built — all the unique slots of the batch, or with cfg.cache_records only
-// those whose lists are stale (possibly none)
-static ellc_status enqueue_align_body(ellc_ctx* c, int B, int nu, int mode, int save_weights) {
-  enqueue_stage_in(c, B);   // also initialises the B alignment states
-  // mask / count per level (updationOnPyrChange, ImageFunc.cpp:158) and the pose-independent per-pixel records. (Folding the
-  // staging into the count launch — its tile blocks then read their keyframe slot from the pinned record, one PCIe round trip
-  // per block — was measured in r02: the count launch went from 10 to 29 us at 32 keyframes; the separate 8 us launch stays.)
-  const int need = c->cur_need ? c->cur_need : need_of(c, mode);   // (cur_need: launch_group's choice — 16 instead of 20 when every rebuilt slot's H^-1 is current)
-  ellc_status s = ELLC_OK;
-  if (nu > 0) {
-    s = run_prep(c, nu, need);
-    if (s != ELLC_OK) return s;
-    if (need & 4) enqueue_ica_hinv(c, nu);
-  }
-  s = enqueue_schedule(c, B, mode, save_weights);
-  if (s != ELLC_OK) return s;
-  if (!c->use_fused)   // the fused schedules export from their finish kernel
-    hipLaunchKernelGGL(gn_export_results, dim3((B + 63) / 64), dim3(64), 0, c->stream, c->state_d, c->result_dev_alias, B);
-  return ELLC_OK;
-}
-
 // may a batch of B alignments run the list-free schedule (gn_fca_dense)? The tolerance-mode FCA schedule in its level-bound form,
-// without saved weights (they are kept per list entry); launch_group adds: every keyframe slot carries the dense hint
+// without saved weights (they are kept per list entry) ...
 static bool runs_dense(const ellc_ctx* c, int mode, int B, int save_weights) {
   // (r06: the exact mode too — gn_fca_dense_x over the planes and the slot's 1 / Z plane in double)
   return !c->dense_maps_off && c->use_fused && c->pipe && mode == ELLC_MODE_FCA && !save_weights && !schedule_is_adaptive(c, mode, B);
 }
+// ... whose n keyframe slots all carry the dense hint
+static bool group_is_dense(const ellc_ctx* c, int mode, int B, int save_weights, const int* slots, int n) {
+  bool dense = runs_dense(c, mode, B, save_weights);
+  for (int i = 0; i < n; i++) dense = dense && c->kf_dense[slots[i]];
+  return dense;
+}
 
+// The plan of a launch sequence over B alignments that rebuilds the lists of nu slots, as far as the context's settings and the
+// call's shape decide it: the record set, kernel by kernel or captured, the first part of a state-driven schedule. The callers add
+// what they alone know (skip_count, a kept H^-1's record set, pollable, the tracking request, continuation).
+static LaunchPlan make_plan(const ellc_ctx* c, int B, int nu, int mode, int save_weights, int set, bool dense, bool resident) {
+  LaunchPlan p;
+  p.B = B;
+  p.nu = dense ? 0 : nu;   // (no slot's lists are built or read)
+  p.mode = mode;
+  p.save_weights = save_weights;
+  p.set = set;
+  p.dense = dense;
+  p.need = need_of(c, mode);
+  p.resident = resident;
+  p.adaptive_first = schedule_is_adaptive(c, mode, B) ? adaptive_first_launches(c, resident) : 0;   // (it varies with the context's hint)
+  p.direct = launches_directly(c, mode, B);
+  return p;
+}
 
-// Enqueues the launch sequence of one batch on c->stream — replayed from a hipGraph captured on first use, keyed by
-// (B, unique keyframes, mode, save_weights, batch set, part). continuation: the rest of a state-driven schedule whose first
-// graph ended before every alignment had (enqueue_schedule_adaptive), for the batch set selected in the context.
+// p.nu: keyframe slots whose compact lists are (re)built — all the unique slots of the batch, or with cfg.cache_records only
+// those whose lists are stale (possibly none)
+static ellc_status enqueue_align_body(ellc_ctx* c, const LaunchPlan& p) {
+  enqueue_stage_in(c, p, p.B);   // also initialises the B alignment states
+  // mask / count per level (updationOnPyrChange, ImageFunc.cpp:158) and the pose-independent per-pixel records. (Folding the
+  // staging into the count launch — its tile blocks then read their keyframe slot from the pinned record, one PCIe round trip
+  // per block — was measured in r02: the count launch went from 10 to 29 us at 32 keyframes; the separate 8 us launch stays.)
+  ellc_status s = ELLC_OK;
+  if (p.nu > 0) {
+    s = run_prep(c, p);
+    if (s != ELLC_OK) return s;
+    if (p.need & 4) enqueue_ica_hinv(c, p.nu);
+  }
+  s = enqueue_schedule(c, p);
+  if (s != ELLC_OK) return s;
+  if (!c->use_fused)   // the fused schedules export from their finish kernel
+    hipLaunchKernelGGL(gn_export_results, dim3((p.B + 63) / 64), dim3(64), 0, c->stream, c->state_d, c->result_dev_alias, p.B);
+  return ELLC_OK;
+}
+
+// Enqueues the launch sequence of plan p on c->stream, for the batch set selected in the context — kernel by kernel (p.direct), or
+// replayed from a hipGraph captured on first use and kept under graph_key(p). p.continuation: the rest of a state-driven schedule
+// whose first part ended before every alignment had (enqueue_schedule_adaptive).
 // count_twin (launch_group, level-bound schedules that compact): a sequence captured for the first time is captured in both forms,
 // with and without the count launch — which of the two a later call replays depends on what was written to its slots in between,
 // and a caller that has rehearsed a call shape once must not meet a capture when the other form's turn comes.
-static ellc_status launch_align_graph(ellc_ctx* c, int B, int nu, int mode, int save_weights, int set, bool continuation, bool count_twin = false) {
-  auto body = [&]() -> ellc_status {
-    if (continuation) return enqueue_schedule_adaptive(c, B, save_weights, schedule_total_iters(c) - c->cur_adaptive_first, true);
-    return enqueue_align_body(c, B, nu, mode, save_weights);
-  };
+static ellc_status launch_align_graph(ellc_ctx* c, const LaunchPlan& p, bool count_twin = false) {
+  auto body = [&](const LaunchPlan& q) -> ellc_status { return q.continuation ? enqueue_schedule_adaptive(c, q) : enqueue_align_body(c, q); };
   // The state-driven schedule (the tracking call: one or two alignments) is launched kernel by kernel: its launches are ~6 us
   // each and dependent, so the host stays ahead of the device without a graph, the depth stages that follow start without the
   // ~14 us a graph's end costs the next launch on the stream (r03 timeline: tracked frame 0.252 -> 0.245 ms), and a first graph
   // whose length follows the previous frame's iteration count (adaptive_hint) needs no re-capture when that count changes.
-  if (launches_directly(c, mode, B)) {
-    c->direct_launch = !continuation;   // (a continuation has no staging)
-    c->direct_nu = nu;
-    const ellc_status s = body();
-    c->direct_launch = false;
-    return s;
-  }
-  // (cur_adaptive_first: launches of the first graph of a state-driven schedule; it varies with the context's hint)
-  const int first = schedule_is_adaptive(c, mode, B) ? c->cur_adaptive_first : 0;
-  // (every choice in a field of its own: packed into one word, grid_batch << 12 reached the bits of the flags above it — a
-  // grid_batch of 65536 made a kept-H^-1 ICA graph the twin of the one that rebuilds H^-1)
-  auto key_of = [&]() {
-    return std::make_tuple(B, continuation ? 0 : nu, mode,
-                           (save_weights ? 1 : 0) | (continuation ? 2 : 0) | (c->track_call ? 4 : 0) | (c->cur_pollable ? 8 : 0), first,
-                           c->cfg.grid_batch, c->cur_dense ? 1 : 0, c->cur_need, c->cur_skip_count ? 1 : 0, set);
-  };
-  auto capture = [&]() -> ellc_status {   // the sequence of key_of() as it is now, into c->graphs
+  if (p.direct) return body(p);
+  auto capture = [&](const LaunchPlan& q) -> ellc_status {   // the sequence of q, into c->graphs
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     ELLC_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    const ellc_status s = body();
+    const ellc_status s = body(q);
     hipError_t e = hipStreamEndCapture(c->stream, &graph);
     if (s != ELLC_OK || e != hipSuccess) {
       if (graph) (void)hipGraphDestroy(graph);
@@ -1767,21 +1715,23 @@ static ellc_status launch_align_graph(ellc_ctx* c, int B, int nu, int mode, int 
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(c, ELLC_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    c->graphs.emplace(key_of(), exec);
+    c->graphs.emplace(graph_key(q, c->cfg.grid_batch), exec);
     return ELLC_OK;
   };
-  const auto key = key_of();
-  if (c->graphs.find(key) == c->graphs.end()) {
-    ellc_status s = capture();
+  const GraphKey key = graph_key(p, c->cfg.grid_batch);
+  auto it = c->graphs.find(key);
+  if (it == c->graphs.end()) {
+    ellc_status s = capture(p);
     if (s != ELLC_OK) return s;
-    if (count_twin && c->count_cache && nu > 0 && !continuation) {
-      c->cur_skip_count = !c->cur_skip_count;
-      if (c->graphs.find(key_of()) == c->graphs.end()) s = capture();
-      c->cur_skip_count = !c->cur_skip_count;
+    if (count_twin && c->count_cache && p.nu > 0 && !p.continuation) {
+      LaunchPlan twin = p;
+      twin.skip_count = !p.skip_count;
+      if (c->graphs.find(graph_key(twin, c->cfg.grid_batch)) == c->graphs.end()) s = capture(twin);
       if (s != ELLC_OK) return s;
     }
+    it = c->graphs.find(key);
   }
-  ELLC_HIP(c, hipGraphLaunch(c->graphs.find(key)->second, c->stream));
+  ELLC_HIP(c, hipGraphLaunch(it->second, c->stream));
   return ELLC_OK;
 }
 
@@ -1851,12 +1801,13 @@ static ellc_status resolve_batch(ellc_ctx* c, int set) {
   }
   const int selected = c->cur_set;
   select_batch_set(c, set);
-  c->cur_adaptive_first = bs.adaptive_first;
-  c->cur_resident = false;   // (a continuation is launches)
+  LaunchPlan plan = make_plan(c, bs.B, 0, bs.mode, bs.save_weights, set, false, false);   // (a continuation is launches, not resident)
+  plan.continuation = true;
+  plan.adaptive_first = bs.adaptive_first;
   ellc_status s = ELLC_OK;
   {
     StreamScope scope(c, c->batch_stream[bs.stream_idx]);
-    s = launch_align_graph(c, bs.B, 0, bs.mode, bs.save_weights, set, true);
+    s = launch_align_graph(c, plan);
     if (s == ELLC_OK && hipEventRecord(bs.done, c->stream) != hipSuccess) s = fail(c, ELLC_ERR_HIP, "hipEventRecord failed");
   }
   select_batch_set(c, selected);
@@ -1892,8 +1843,7 @@ static ellc_status launch_group(ellc_ctx* c, int set) {
   for (int v : bs.kf_slots)
     if (!(c->cache_records || c->kf_rec_eager[v]) || c->kf_rec_tag[v] != need) bs.built_slots.push_back(v);   // (kf_rec_eager: built behind the map's export)
   // dense maps (every keyframe of the launch carries the hint): the list-free schedule — no slot's lists are built or read
-  bool dense = runs_dense(c, bs.mode, B, bs.save_weights);
-  for (int v : bs.kf_slots) dense = dense && c->kf_dense[v];
+  const bool dense = group_is_dense(c, bs.mode, B, bs.save_weights, bs.kf_slots.data(), (int)bs.kf_slots.size());
   if (dense) bs.built_slots.clear();
   const int nu = (int)bs.built_slots.size();
   for (int u = 0; u < nu; u++) c->uniq_slot_h[u] = bs.built_slots[u];
@@ -1966,36 +1916,35 @@ static ellc_status launch_group(ellc_ctx* c, int set) {
   // flight, exact mode: one abandoned launch in 2 000; ordered one behind the other instead they lose the overlap of the three
   // streams: 0.189 against 0.102 ms per batch). Same bits either way. Launches of other contexts or processes are not known here:
   // against those the abandoned launch and its continuation are the safety net.
-  c->cur_resident = false;
+  bs.resident = false;
   if (may_run_resident(c, bs.mode, B)) {
     bool alone = true;
     for (int p = 0; p < ellc_ctx::SETS; p++)
       if (p != set && c->batch_set[p].launched && !c->batch_set[p].resolved) alone = false;
-    c->cur_resident = alone && persist_blocks(c, B) <= c->persist_capacity;
+    bs.resident = alone && persist_blocks(c, B) <= c->persist_capacity;
   }
-  bs.resident = c->cur_resident;
-  c->cur_adaptive_first = adaptive_first_launches(c, B);
-  bs.adaptive_first = c->cur_adaptive_first;
   {
     StreamScope scope(c, run_stream);
-    bs.pollable = polls_results(c, B, si);
-    c->cur_pollable = bs.pollable;
-    c->cur_dense = dense;
-    c->cur_need = (need_run != need) ? need_run : 0;
-    c->cur_skip_count = skip_count;
-    const ellc_status s = launch_align_graph(c, B, nu, bs.mode, bs.save_weights, set, false, !dense);
-    c->cur_skip_count = false;
-    c->cur_need = 0;
-    c->cur_dense = false;
-    c->cur_pollable = false;
+    LaunchPlan plan = make_plan(c, B, nu, bs.mode, bs.save_weights, set, dense, bs.resident);
+    plan.need = need_run;
+    plan.skip_count = skip_count;
+    plan.pollable = bs.pollable = polls_results(c, B, si);
+    plan.track = bs.track;
+    plan.count_valid = bs.count_valid;
+    plan.count_n = bs.count_n;
+    bs.adaptive_first = plan.adaptive_first;
+    const ellc_status s = launch_align_graph(c, plan, !dense);
     if (s != ELLC_OK) {
       for (int v : bs.built_slots) invalidate_records(c, v);
       return s;
     }
+    // what ellc_track_frame reads back: did a launch take its count along; do the saved weights wait for its selection launch
+    bs.count_rode = count_rides(plan);
+    bs.ride_weights = weights_ride(c, plan);
     // (ellc_track_frame, whose host side polls the result record: the event goes behind the depth stages it enqueues next — in
     // front of them the record would hold their first launch back ~6 us)
-    c->done_deferred = c->track_call && bs.pollable;
-    if (!c->done_deferred) ELLC_HIP(c, hipEventRecord(bs.done, c->stream));
+    bs.done_by_caller = bs.track && bs.pollable;
+    if (!bs.done_by_caller) ELLC_HIP(c, hipEventRecord(bs.done, c->stream));
   }
   for (int v : bs.built_slots) c->kf_rec_tag[v] = need;
   for (int v : bs.built_slots) c->kf_counts_ok[v] = count_free ? 0 : 1;   // (left by this launch's prep_count, or already current)
@@ -2030,8 +1979,10 @@ static void free_set(ellc_ctx* c, int set) {
 
 // track: the batch is staged in a set (joining the open group when it can, see ellc_ctx::BatchSet) and enters the in-flight
 // queue ellc_align_fetch drains; untracked use (the timing hooks, nothing in flight) runs set 0 on the main stream at once.
+// tracking: ellc_track_frame's alignment (null: any other) and the count it asks the staging to take along; the set the batch is
+// staged in holds the answers once its group is launched (BatchSet::count_rode, done_by_caller, ride_weights).
 static ellc_status align_enqueue_impl(ellc_ctx* c, int B, const int* kf_slots, const int* frame_slots, const float* init_pose, int mode,
-                                      int save_weights, bool track) {
+                                      int save_weights, bool track, const TrackRequest* tracking = nullptr) {
   if (!c) return ELLC_ERR_BAD_ARG;
   if (mode != ELLC_MODE_FCA && mode != ELLC_MODE_ICA) return fail(c, ELLC_ERR_BAD_ARG, "unknown mode");
   const int MB = c->cfg.max_batch;
@@ -2042,14 +1993,8 @@ static ellc_status align_enqueue_impl(ellc_ctx* c, int B, const int* kf_slots, c
     ellc_status s = stage_batch(c, B, kf_slots, frame_slots, init_pose, &nu);
     if (s != ELLC_OK) return s;
     for (int b = 0; b < B; b++) invalidate_records(c, kf_slots[b]);   // rebuilt here, outside the cache's bookkeeping
-    c->cur_resident = may_run_resident(c, mode, B) && persist_blocks(c, B) <= c->persist_capacity;   // (nothing in flight)
-    c->cur_adaptive_first = adaptive_first_launches(c, B);
-    bool dense = runs_dense(c, mode, B, save_weights);
-    for (int b = 0; b < B; b++) dense = dense && c->kf_dense[kf_slots[b]];
-    c->cur_dense = dense;
-    s = launch_align_graph(c, B, dense ? 0 : nu, mode, save_weights, 0, false);
-    c->cur_dense = false;
-    return s;
+    const bool resident = may_run_resident(c, mode, B) && persist_blocks(c, B) <= c->persist_capacity;   // (nothing in flight)
+    return launch_align_graph(c, make_plan(c, B, nu, mode, save_weights, 0, group_is_dense(c, mode, B, save_weights, kf_slots, B), resident));
   }
   // may this batch share a launch with others? full batches of one mode, nothing per-slot written (saved weights), not the
   // state-driven tracking schedule
@@ -2087,6 +2032,10 @@ static ellc_status align_enqueue_impl(ellc_ctx* c, int B, const int* kf_slots, c
     bs.save_weights = save_weights ? 1 : 0;
     bs.fetched = 0;
     bs.launched = false;
+    bs.track = tracking != nullptr;
+    bs.count_valid = tracking ? tracking->count_valid : nullptr;
+    bs.count_n = tracking ? tracking->count_n : 0;
+    bs.count_rode = bs.done_by_caller = bs.ride_weights = false;
   }
   bs.slice_B[slice] = B;
   bs.fill = slice + 1;
@@ -2184,13 +2133,18 @@ ellc_status ellc_gn_iterate(ellc_ctx* c, int kf_slot, int frame_slot, int level,
   invalidate_records(c, kf_slot);   // the single-step API builds its own record set
   ellc_status s = stage_batch(c, 1, &kf_slot, &frame_slot, pose, &nu);
   if (s != ELLC_OK) return s;
-  enqueue_stage_in(c, 0);   // staging only: the state keeps the level's H^-1 (gn_set_pose0)
-  s = run_prep(c, nu, mode == ELLC_MODE_ICA ? 1 : (c->fast ? 8 : 2));
+  LaunchPlan plan;   // (not a production sequence: staged through the pinned record, with a count launch)
+  plan.B = 1;
+  plan.nu = nu;
+  plan.mode = mode;
+  plan.need = mode == ELLC_MODE_ICA ? 1 : (c->fast ? 8 : 2);   // the single-step API builds its own record set
+  enqueue_stage_in(c, plan, 0);   // staging only: the state keeps the level's H^-1 (gn_set_pose0)
+  s = run_prep(c, plan);
   if (s != ELLC_OK) return s;
   hipLaunchKernelGGL(gn_set_pose0, dim3(1), dim3(1), 0, c->stream, c->state_d, c->init_pose_d);
   const size_t n = (size_t)c->geom_h[level].n;
   if (planes) ELLC_HIP(c, hipMemsetAsync(c->planes_d, 0, 10 * n * 4, c->stream));
-  GnArgs a = make_gn_args(c, level, 1, 0, planes ? c->planes_d : nullptr);
+  GnArgs a = make_gn_args(c, plan, level, 0, planes ? c->planes_d : nullptr);
   const dim3 grd(a.nblk, 1), blk(ELLC_GN_THREADS);
   if (mode == ELLC_MODE_FCA) {
     if (planes && c->fast) hipLaunchKernelGGL((gn_fca_accumulate<true, false, true>), grd, blk, 0, c->stream, a);
@@ -2232,7 +2186,9 @@ ellc_status ellc_gn_display_planes(ellc_ctx* c, int kf_slot, int frame_slot, int
   select_batch_set(c, 0);
   ellc_status s = stage_batch(c, 1, &kf_slot, &frame_slot, pose, &nu);
   if (s != ELLC_OK) return s;
-  enqueue_stage_in(c, 0);   // staging only
+  LaunchPlan plan;
+  plan.B = 1;
+  enqueue_stage_in(c, plan, 0);   // staging only
   hipLaunchKernelGGL(gn_set_pose0, dim3(1), dim3(1), 0, c->stream, c->state_d, c->init_pose_d);
   const LevelGeom& g = c->geom_h[level];
   const size_t n = (size_t)g.n;
@@ -2240,7 +2196,7 @@ ellc_status ellc_gn_display_planes(ellc_ctx* c, int kf_slot, int frame_slot, int
   float* orig_d = c->planes_d + n;
   uint8_t* tmpl_d = (uint8_t*)(c->planes_d + 2 * n);
   uint8_t* tbw_d = tmpl_d + n;
-  GnArgs a = make_gn_args(c, level, 1, 0, nullptr);
+  GnArgs a = make_gn_args(c, plan, level, 0, nullptr);
   dim3 blk(32, 8);
   hipLaunchKernelGGL(gn_display_planes, grid2d(g.cols, g.rows, blk), blk, 0, c->stream, a, tmpl_d, tbw_d, warped_d, orig_d);
   ELLC_HIP(c, hipGetLastError());
@@ -2288,38 +2244,31 @@ ellc_status ellc_profile_gn_kernel(ellc_ctx* c, int B, const int* kf_slots, cons
     for (int b = 0; b < B; b++) invalidate_records(c, kf_slots[b]);
   ellc_status s = stage_batch(c, B, kf_slots, frame_slots, nullptr, &nu, nullptr, true);   // up to a whole launch group (cfg.coalesce batches)
   if (s != ELLC_OK) return s;
-  bool dense = runs_dense(c, ELLC_MODE_FCA, B, 0);   // the kernel the production schedule would launch for these keyframes
-  for (int b = 0; b < B; b++) dense = dense && c->kf_dense[kf_slots[b]];
-  enqueue_stage_in(c, 0);
+  // the kernel the production schedule would launch for these keyframes (the grids of list-free launches are sized for their kernel)
+  const bool dense = group_is_dense(c, ELLC_MODE_FCA, B, 0, kf_slots, B);
+  LaunchPlan plan;   // (staged through the pinned record, with a count launch, whatever the production sequence would do)
+  plan.B = B;
+  plan.nu = dense ? 0 : nu;
+  plan.dense = dense;
+  plan.need = c->fast ? 8 : 2;
+  enqueue_stage_in(c, plan, 0);
   if (!dense) {
-    s = run_prep(c, nu, c->fast ? 8 : 2);
+    s = run_prep(c, plan);
     if (s != ELLC_OK) return s;
   }
   hipLaunchKernelGGL(gn_init_state, dim3((B + 63) / 64), dim3(64), 0, c->stream, c->state_d, c->init_pose_d, B, c->L - 1);
-  c->cur_dense = dense;   // (the grids of list-free launches are sized for their kernel: choose_nblk)
-  GnArgs a = make_gn_args(c, level, B, 0, nullptr);
-  c->cur_dense = false;
+  const GnArgs a = make_gn_args(c, plan, level, 0, nullptr);
   const dim3 grd(a.nblk, B), blk(ELLC_GN_THREADS);
   if (c->use_fused) {
     // the production kernel of the FCA path: every launch first solves the previous launch's partial sums
-    FusedArgs fa;
-    fa.continuation = 0;
-    set_track_fields(c, fa, false);
-  set_track_fields(c, fa, false);
-    fa.g = a;
+    FusedArgs fa = fused_args(c, plan, false, (B % 8 == 0) ? 1 : 0, false);
+    level_bound_level(c, plan, fa, level);
     fa.res = nullptr;
-    fa.ica = 0;
-    fa.xcd_map = (B % 8 == 0) ? 1 : 0;
-    set_age_split(c, fa, B);
-    fa.seq = 0;
     fa.prev_level = level;
     fa.prev_nblk = a.nblk;
     fa.early_exit = 0;
-    fa.stride_state = c->group_cap;
-    fa.stride_part = (size_t)c->group_cap * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
-    c->cur_dense = dense;
     auto launch = [&]() {
-      launch_level_bound(c, grd, blk, fa, c->stream);
+      launch_level_bound(c, plan, grd, blk, fa, c->stream);
       fa.seq++;
     };
     for (int i = 0; i < 3; i++) launch();
@@ -2332,14 +2281,14 @@ ellc_status ellc_profile_gn_kernel(ellc_ctx* c, int B, const int* kf_slots, cons
       hipError_t e = hipStreamEndCapture(c->stream, &graph);
       if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
       if (graph) (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) { c->cur_dense = false; return fail(c, ELLC_ERR_HIP, std::string("profile graph capture: ") + hipGetErrorString(e)); }
+      if (e != hipSuccess) return fail(c, ELLC_ERR_HIP, std::string("profile graph capture: ") + hipGetErrorString(e));
       e = hipGraphLaunch(exec, c->stream);   // warm
       if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
       if (e == hipSuccess) e = hipGraphLaunch(exec, c->stream);
       if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
       if (e == hipSuccess) e = hipEventSynchronize(c->ev1);
       (void)hipGraphExecDestroy(exec);
-      if (e != hipSuccess) { c->cur_dense = false; return fail(c, ELLC_ERR_HIP, std::string("profile graph: ") + hipGetErrorString(e)); }
+      if (e != hipSuccess) return fail(c, ELLC_ERR_HIP, std::string("profile graph: ") + hipGetErrorString(e));
     } else {
       ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
       for (int i = 0; i < reps; i++) launch();
@@ -2351,7 +2300,6 @@ ellc_status ellc_profile_gn_kernel(ellc_ctx* c, int B, const int* kf_slots, cons
     for (int i = 0; i < reps; i++) launch_fca(c, grd, blk, a);
     ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
   }
-  c->cur_dense = false;
   ELLC_HIP(c, hipEventSynchronize(c->ev1));
   float ms = 0;
   ELLC_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
@@ -2384,24 +2332,22 @@ ellc_status ellc_debug_schedule_sums(ellc_ctx* c, int B, const int* kf_slots, co
   if (s != ELLC_OK) return s;
   for (int b = 0; b < B; b++) invalidate_records(c, kf_slots[b]);   // rebuilt here, outside the cache's bookkeeping
   // the lists, or none (dense maps), and the record set as launch_group chooses them
-  bool dense = runs_dense(c, mode, B, 0);
-  for (int b = 0; b < B; b++) dense = dense && c->kf_dense[kf_slots[b]];
-  enqueue_stage_in(c, B);
-  if (!dense) {
-    const int need = need_of(c, mode);
-    s = run_prep(c, nu, need);
+  LaunchPlan plan = make_plan(c, B, nu, mode, 0, 0, group_is_dense(c, mode, B, 0, kf_slots, B), false);
+  plan.direct = false;   // (staged through the pinned record, with a count launch, whatever the production sequence would do)
+  enqueue_stage_in(c, plan, B);
+  if (plan.nu > 0) {
+    s = run_prep(c, plan);
     if (s != ELLC_OK) return s;
-    if (need & 4) enqueue_ica_hinv(c, nu);
+    if (plan.need & 4) enqueue_ica_hinv(c, plan.nu);
   }
   // a record that no block writes stays NaN (all bits set) and shows in its alignment's sums
   const size_t part_floats = (size_t)B * ELLC_NBLK_MAX * ELLC_PART_STRIDE;
   ELLC_HIP(c, hipMemsetAsync(c->partials_d, 0xff, part_floats * 4, c->stream));
-  c->cur_dense = dense;
-  FusedArgs fa = level_bound_args(c, B, 0, mode == ELLC_MODE_ICA);
+  const bool ica = mode == ELLC_MODE_ICA;
+  FusedArgs fa = fused_args(c, plan, ica, (!ica && B % 8 == 0) ? 1 : 0, false);
   fa.res = nullptr;
-  level_bound_level(c, fa, level, B);
-  const char* name = launch_level_bound(c, dim3(fa.g.nblk, B), dim3(ELLC_GN_THREADS), fa, c->stream);
-  c->cur_dense = false;
+  level_bound_level(c, plan, fa, level);
+  const char* name = launch_level_bound(c, plan, dim3(fa.g.nblk, B), dim3(ELLC_GN_THREADS), fa, c->stream);
   // the finish kernel solves the launch's sums (state buffer 1, partial buffer 0) into state buffer 0
   fa.prev_level = level;
   fa.prev_nblk = fa.g.nblk;
