@@ -17,7 +17,7 @@ ABI_SYMBOLS = [
     "ellc_frame_upload", "ellc_keyframe_upload", "ellc_keyframe_from_frame", "ellc_get_image_level", "ellc_get_gradient",
     "ellc_get_max_gradient", "ellc_keyframe_set_depth", "ellc_keyframe_set_depth_level", "ellc_keyframe_get_depth_level",
     "ellc_keyframe_set_weights", "ellc_keyframe_get_weights", "ellc_keyframe_finalise_weights", "ellc_align", "ellc_align_enqueue",
-    "ellc_align_fetch", "ellc_gn_iterate", "ellc_gn_display_planes", "ellc_concatenate_relative_pose", "ellc_concatenate_origin_pose", "ellc_se3_exp",
+    "ellc_align_fetch", "ellc_align_quality_at", "ellc_gn_iterate", "ellc_gn_display_planes", "ellc_concatenate_relative_pose", "ellc_concatenate_origin_pose", "ellc_se3_exp",
     "ellc_se3_log", "ellc_depth_set_state", "ellc_depth_get_state", "ellc_depth_set_keyframe", "ellc_depth_propagate",
     "ellc_depth_observe", "ellc_depth_fill_holes", "ellc_depth_regularize", "ellc_depth_make_inv_depth_one", "ellc_depth_regularize_fill_regularize", "ellc_depth_do_regularization",
     "ellc_depth_update_depth_image", "ellc_depth_create_keyframe", "ellc_depth_seeds", "ellc_track_frame",
@@ -48,6 +48,13 @@ class EllcConfig(C.Structure):
 class EllcHypotheses(C.Structure):
     _fields_ = [("invDepth", C.c_void_p), ("invDepthSmoothed", C.c_void_p), ("variance", C.c_void_p), ("varianceSmoothed", C.c_void_p),
                 ("validity_counter", C.c_void_p), ("blacklisted", C.c_void_p), ("isValid", C.c_void_p)]
+
+
+class EllcAlignQuality(C.Structure):
+    """ellc_align_quality: what ellc_align_quality_at returns per evaluation."""
+    _fields_ = [("n_depth", C.c_int32), ("n_used", C.c_int32),
+                ("sum_r2", C.c_double), ("sum_abs_r", C.c_double), ("sum_w", C.c_double), ("sum_wr2", C.c_double),
+                ("H", C.c_float * 36), ("b", C.c_float * 6), ("Hinv", C.c_float * 36)]
 
 
 class EllcError(RuntimeError):

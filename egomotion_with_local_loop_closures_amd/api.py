@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -182,6 +182,28 @@ class Context:
         pose = np.zeros((B, 6), np.float32); iters = np.zeros((B, self.levels), np.int32); wgt = np.zeros(B, np.float32)
         self._ck(self._l.ellc_align_fetch(self.h, B, _p(pose), _p(iters), _p(wgt)), "ellc_align_fetch")
         return pose, iters, wgt
+
+    def align_quality(self, kf_slots, frame_slots, pose, level=0):
+        """ellc_align_quality_at: one forward-compositional pixel pass per (keyframe slot, frame slot, pose) at `level`, no update.
+        Returns a dict of arrays over the B evaluations: n_depth, n_used (int32), sum_r2, sum_abs_r, sum_w, sum_wr2 (f64), H [B][6][6],
+        b [B][6], Hinv [B][6][6] (f32), and the derived rms = sqrt(sum_r2 / n_used), wrms = sqrt(sum_wr2 / sum_w),
+        overlap = n_used / n_depth (0 where the denominator is 0)."""
+        B, kf, fr, ps = self._batch(kf_slots, frame_slots, pose)
+        rec = (EllcAlignQuality * B)()
+        self._ck(self._l.ellc_align_quality_at(self.h, B, _p(kf), _p(fr), _p(ps), int(level), rec), "ellc_align_quality_at")
+        raw = np.frombuffer(rec, dtype=np.dtype(EllcAlignQuality)).copy()
+        out = {k: raw[k].copy() for k in ("n_depth", "n_used", "sum_r2", "sum_abs_r", "sum_w", "sum_wr2")}
+        out["H"] = raw["H"].reshape(B, 6, 6).copy()
+        out["b"] = raw["b"].reshape(B, 6).copy()
+        out["Hinv"] = raw["Hinv"].reshape(B, 6, 6).copy()
+
+        def ratio(num, den):
+            den = np.asarray(den, np.float64)
+            return np.divide(np.asarray(num, np.float64), den, out=np.zeros(B, np.float64), where=den != 0)
+        out["rms"] = np.sqrt(ratio(out["sum_r2"], out["n_used"]))
+        out["wrms"] = np.sqrt(ratio(out["sum_wr2"], out["sum_w"]))
+        out["overlap"] = ratio(out["n_used"], out["n_depth"])
+        return out
 
     def gn_iterate(self, kf_slot, frame_slot, level, pose, mode=MODE_FCA, it=0, planes=False):
         pose = np.ascontiguousarray(pose, np.float32)

@@ -213,6 +213,12 @@ struct ellc_ctx {
   int persist_capacity = 0;                         // blocks of gn_fca_persist the device holds at once (occupancy x CUs)
   bool use_persist = true;                          // the state-driven schedule as one resident launch (gn_fca_persist)
   float* planes_d = nullptr;
+  // ellc_align_quality_at: scratch of its own, allocated by the first call (a context that never calls it holds none)
+  int* quality_stage_h = nullptr;                               // [max_batch] keyframe slots, [max_batch] frame slots, [max_batch][6] poses; pinned,
+  const int* quality_stage_dev_alias = nullptr;                 //   read by the kernel through its device-side address
+  float* quality_partials_d = nullptr;                          // [max_batch][blocks of level 0][ELLC_PART_STRIDE]
+  int* quality_counts_d = nullptr;                              // [max_batch][blocks of level 0][2]
+  ellc_align_quality *quality_out_h = nullptr, *quality_out_dev_alias = nullptr;   // pinned: the finish kernel writes the records
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

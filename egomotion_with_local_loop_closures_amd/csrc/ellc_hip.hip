@@ -2177,6 +2177,80 @@ ellc_status ellc_gn_iterate(ellc_ctx* c, int kf_slot, int frame_slot, int level,
   return ELLC_OK;
 }
 
+// ellc_align_quality_at: blocks per evaluation — a function of the level's size ALONE (sixteen pixels of the plane a thread, so that a
+// wave of a semi-dense map fills its queue a few times; at most the accumulate kernels' block limit), so that an evaluation's sums
+// are chunked the same way whatever the call's B or the context's grid_batch
+#ifndef ELLC_QUALITY_PX
+#define ELLC_QUALITY_PX 16   // (A/B builds: make variant DEFS=-DELLC_QUALITY_PX=8)
+#endif
+static int quality_nblk(const ellc_ctx* c, int level) {
+  return std::max(1, std::min(ELLC_NBLK_MAX, (c->geom_h[level].n + ELLC_QUALITY_PX * ELLC_GN_THREADS - 1) / (ELLC_QUALITY_PX * ELLC_GN_THREADS)));
+}
+static_assert(sizeof(QualityRec) == sizeof(ellc_align_quality) && offsetof(QualityRec, sum_r2) == offsetof(ellc_align_quality, sum_r2) &&
+                  offsetof(QualityRec, H) == offsetof(ellc_align_quality, H) && offsetof(QualityRec, b) == offsetof(ellc_align_quality, b) &&
+                  offsetof(QualityRec, Hinv) == offsetof(ellc_align_quality, Hinv),
+              "QualityRec mirrors ellc_align_quality");
+
+ellc_status ellc_align_quality_at(ellc_ctx* c, int B, const int* kf_slots, const int* frame_slots, const float* pose, int level,
+                                  ellc_align_quality* out) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  // validated first: a refused call leaves the context as it was
+  if (!kf_slots || !frame_slots || !pose || !out) return fail(c, ELLC_ERR_BAD_ARG, "ellc_align_quality_at: null pointer");
+  if (B < 1 || B > c->cfg.max_batch) return fail(c, ELLC_ERR_BAD_ARG, "ellc_align_quality_at: B out of range");
+  if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, "ellc_align_quality_at: level out of range");
+  for (int b = 0; b < B; b++)
+    if (!slot_ok(kf_slots[b], c->cfg.max_keyframes) || !slot_ok(frame_slots[b], c->cfg.max_frames))
+      return fail(c, ELLC_ERR_BAD_ARG, "ellc_align_quality_at: slot index out of range");
+  for (int b = 0; b < B; b++) {
+    if (!c->kf_has_image[kf_slots[b]] || !c->kf_has_depth[kf_slots[b]]) return fail(c, ELLC_ERR_NOT_READY, "ellc_align_quality_at: keyframe slot lacks image or depth");
+    if (!c->fr_has_image[frame_slots[b]]) return fail(c, ELLC_ERR_NOT_READY, "ellc_align_quality_at: frame slot lacks image");
+  }
+  ELLC_ENTER(c);   // behind the batches in flight, on the main stream
+  const int MB = c->cfg.max_batch;
+  if (!c->quality_out_h) {
+    const size_t nb0 = (size_t)quality_nblk(c, 0);   // level 0 has the most blocks
+    ellc_status s = host_alloc(c, &c->quality_stage_h, (size_t)8 * MB);
+    if (s == ELLC_OK) s = dev_alloc(c, &c->quality_partials_d, (size_t)MB * nb0 * ELLC_PART_STRIDE);
+    if (s == ELLC_OK) s = dev_alloc(c, &c->quality_counts_d, (size_t)MB * nb0 * 2);
+    ellc_align_quality* oh = nullptr;
+    if (s == ELLC_OK) s = host_alloc(c, &oh, (size_t)MB);
+    if (s != ELLC_OK) return s;
+    void *da = nullptr, *ds = nullptr;
+    ELLC_HIP(c, hipHostGetDevicePointer(&da, oh, 0));
+    ELLC_HIP(c, hipHostGetDevicePointer(&ds, c->quality_stage_h, 0));
+    c->quality_out_dev_alias = (ellc_align_quality*)da;
+    c->quality_stage_dev_alias = (const int*)ds;
+    c->quality_out_h = oh;
+  }
+  for (int b = 0; b < B; b++) {
+    c->quality_stage_h[b] = kf_slots[b];
+    c->quality_stage_h[MB + b] = frame_slots[b];
+  }
+  std::memcpy(c->quality_stage_h + 2 * MB, pose, (size_t)B * 6 * sizeof(float));   // pinned: the kernel reads it where it lies (the call is synchronous)
+  QualityArgs qa;
+  qa.geom = c->geom_d;
+  qa.kf_tab = c->kf_tab_d;
+  qa.fr_tab = c->fr_tab_d;
+  qa.stage = c->quality_stage_dev_alias;
+  qa.partials = c->quality_partials_d;
+  qa.counts = c->quality_counts_d;
+  qa.out = (QualityRec*)c->quality_out_dev_alias;
+  qa.level = level;
+  qa.max_kf = c->cfg.max_keyframes;
+  qa.max_fr = c->cfg.max_frames;
+  qa.nblk = quality_nblk(c, level);
+  qa.max_batch = MB;
+  const dim3 grd(qa.nblk, B), blk(ELLC_GN_THREADS);
+  if (c->fast) hipLaunchKernelGGL((gn_fca_quality<true, false>), grd, blk, 0, c->stream, qa);
+  else if (c->geom_h[0].divc_ok) hipLaunchKernelGGL((gn_fca_quality<false, true>), grd, blk, 0, c->stream, qa);
+  else hipLaunchKernelGGL((gn_fca_quality<false, false>), grd, blk, 0, c->stream, qa);
+  hipLaunchKernelGGL(gn_quality_finish, dim3(B), dim3(ELLC_SOLVE_THREADS), 0, c->stream, qa);
+  ELLC_HIP(c, hipGetLastError());
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  std::memcpy(out, c->quality_out_h, (size_t)B * sizeof(ellc_align_quality));
+  return ELLC_OK;
+}
+
 ellc_status ellc_gn_display_planes(ellc_ctx* c, int kf_slot, int frame_slot, int level, const float* pose, uint8_t* templateimg,
                                    uint8_t* tobewarpedimg, float* warpedimg, float* origres) {
   ELLC_ENTER(c);

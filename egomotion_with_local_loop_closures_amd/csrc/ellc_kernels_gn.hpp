@@ -3071,4 +3071,270 @@ struct RideWeights {
   int max_kf = 0, fast_records = 0;
 };
 
+// ---------------------------------------------------------------------------------------------------
+// ellc_align_quality_at: how well a frame fits a keyframe at a pose the caller names. ONE forward-compositional pixel pass at one
+// level, outside every schedule: no state record, no compact list (the planes are walked directly — plane_walk, as gn_fca_dense
+// does — so the pass works on a slot whatever the state of its records), nothing written that belongs to a slot. Per pixel the values are those of the
+// single-step kernels (fca_pixel_in with the compaction's 1.0 / (double)depth; dense_form + fcaf_stage_a / _b in the tolerance
+// mode); beside the 27 sums of H and b a block leaves the four scalar sums of ellc_align_quality and, as integers, the two counts.
+// The grid is (nblk, B) with nblk a function of the level's size alone and an even split of the plane: an alignment's record does
+// not depend on B, on its place in the batch or on anything else in flight.
+struct QualityRec {   // ellc_align_quality (include/ellc_abi.h), field for field
+  int32_t n_depth, n_used;
+  double sum_r2, sum_abs_r, sum_w, sum_wr2;
+  float H[36], b[6], Hinv[36];
+};
+struct QualityArgs {
+  const LevelGeom* geom;
+  const KfLevelDev* kf_tab;
+  const FrLevelDev* fr_tab;
+  const int* stage;     // the call's description (pinned host memory): [max_batch] keyframe slots, [max_batch] frame slots, [max_batch][6] poses (f32)
+  float* partials;      // [B][nblk][ELLC_PART_STRIDE]: 27 sums of H and b, then sum r^2, sum |r|, sum w, sum w r^2
+  int* counts;          // [B][nblk][2]: pixels with depth, of which used
+  QualityRec* out;      // [B], pinned host memory
+  int level, max_kf, max_fr, nblk, max_batch;
+};
+
+// Does the warped point (x1, y1) get no intensity (Taps::I == -1)? tap_general's test: not a number, or all four taps outside.
+// (The interior paths of the taps imply !oob: their floor(x1), floor(y1) are in range.)
+__device__ __forceinline__ bool tap_oob(int cols, int rows, float x1, float y1) {
+  if (x1 != x1 || y1 != y1) return true;
+  const float fx0 = floorf(x1), fy0 = floorf(y1);
+  const float nC = (float)(cols - 1), nR = (float)(rows - 1);
+  const bool xf_bad = (fx0 < 0.0f) || (fx0 > nC);
+  const bool xc_bad = (x1 < 0.0f) || (x1 > nC);
+  const bool yf_bad = (fy0 < 0.0f) || (fy0 > nR);
+  const bool yc_bad = (y1 < 0.0f) || (y1 > nR);
+  return (xf_bad && xc_bad) || (yf_bad && yc_bad);   // = !(v00 || v01 || v10 || v11)
+}
+
+// The walk: thread t of a block takes the pixels begin + t, begin + t + 256, ... of the block's chunk of the plane and reads their
+// DEPTH, one step ahead (coalesced, 4 bytes a pixel). A semi-dense map holds a depth at a quarter of its pixels, scattered: a wave
+// that ran the pixel step wherever one of its 64 pixels holds one would run it almost everywhere, three lanes in four on a stand-in
+// (measured so first: 120 us for 32 alignments at 640x480 in the tolerance mode, against 16 us of the list kernel's launch). So the
+// pixels with a depth go, in ballot order, into a queue of the WAVE in LDS (position only: x | y << 16), and whenever 64 are queued
+// the wave runs them through the pixel step, every lane busy, reading variance, intensity and depth at the queued positions; the
+// rest at the end of the chunk. The queue is wave-private scratch, not a list of the slot; its order is fixed by the chunk alone.
+#define ELLC_QUALITY_QCAP 128   // drained below 64 after every step, a step appends at most 64
+template <bool FAST, bool DIVC>
+__global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_quality(QualityArgs qa) {
+  const int b = blockIdx.y, sub = blockIdx.x, t = threadIdx.x;
+  const LevelGeom g = qa.geom[qa.level];
+  const KfLevelDev K = qa.kf_tab[qa.level * qa.max_kf + qa.stage[b]];   // by value: uniform, lives in SGPRs
+  const FrLevelDev& F = qa.fr_tab[qa.level * qa.max_fr + qa.stage[qa.max_batch + b]];
+  g_u8 cur = as_global(F.img);
+  Chunk c;   // even split of the PLANE
+  {
+    const int n = (g.n + qa.nblk - 1) / qa.nblk;
+    c.begin = sub * n;
+    c.end = min(g.n, c.begin + n);
+  }
+  const int sw = g.sw, cols = g.cols;
+  const PlaneWalk w = plane_walk(cols);
+  PlanePos p = plane_first(w, c, t);
+  float z = 0.0f;
+  if (c.begin < c.end) z = as_global(K.depth)[(unsigned)min(p.i, c.end - 1)];   // block-uniform
+  // exp(pose) as gn_set_pose0 forms it (exp_se3_f32), its nine entries on nine lanes (exp_se3_entry: the same operations per value)
+  __shared__ float Ssh[12];
+  __shared__ uint32_t qbuf[ELLC_GN_THREADS / 64][ELLC_QUALITY_QCAP];
+  if (t < 64) {
+    const float* pose = (const float*)(qa.stage + 2 * qa.max_batch) + 6 * b;
+    const int l9 = min(t, 8);
+    const int r3 = l9 / 3, k3 = l9 - 3 * r3;
+    double Rrk, Vv;
+    exp_se3_entry((double)pose[0], (double)pose[1], (double)pose[2], (double)pose[3], (double)pose[4], (double)pose[5], r3, k3, Rrk, Vv);
+    const double trow = (Vv + __shfl_down(Vv, 1)) + __shfl_down(Vv, 2);   // t[r] in lanes 0, 3, 6
+    if (t < 9) {
+      Ssh[r3 * 4 + k3] = (float)Rrk;
+      if (k3 == 0) Ssh[r3 * 4 + 3] = (float)trow;
+    }
+  }
+  __syncthreads();
+  float S[12];
+#pragma unroll
+  for (int i = 0; i < 12; i++) S[i] = Ssh[i];
+  GnArgs a;   // what the pixel functions read of it: nothing is saved, no planes
+  a.geom = qa.geom; a.kf_tab = qa.kf_tab; a.fr_tab = qa.fr_tab; a.kf_slot = nullptr; a.fr_slot = nullptr; a.state = nullptr;
+  a.partials = nullptr; a.planes = nullptr; a.level = qa.level; a.max_kf = qa.max_kf; a.max_fr = qa.max_fr; a.nblk = qa.nblk; a.save_w = 0;
+  FcaAcc acc;
+  fca_acc_zero(acc);
+  float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  int n_depth = 0, n_used = 0;   // wave-uniform: ballots, counted as integers
+  if (c.begin < c.end) {   // block-uniform
+    const TapRows tr = tap_rows(cur, sw);
+    const FcafConst fc = fcaf_const(g, S);
+    const int lane = t & 63;
+    uint32_t* const q = qbuf[t >> 6];
+    int qn = 0;   // wave-uniform: positions queued
+    // A batch of queued pixels on its way through the pixel step: pop() takes the last n (<= 64) positions off the queue and requests
+    // their planes; run() — called a step later, or at the end of the chunk, so that the request is in flight while the walk goes
+    // on — forms the pixels and accumulates. (A lane without an entry runs on a copy of the batch's last one and accumulates nothing.)
+    uint32_t bxy = 0u;
+    int bn = 0;   // wave-uniform: pixels of the batch in flight (0: none)
+    DensePix bpx;
+    bpx.Z = 1.0f; bpx.var = 0.0f; bpx.I = 0u;
+    auto pop = [&](int n) {
+      __builtin_amdgcn_wave_barrier();
+      bxy = q[qn - n + min(lane, n - 1)];
+      __builtin_amdgcn_wave_barrier();
+      qn -= n;
+      bn = n;
+      const unsigned x = bxy & 0xffffu, y = bxy >> 16;
+      bpx = dense_request(K, __umul24(y, (unsigned)cols) + x, __umul24(y, (unsigned)sw) + x);
+    };
+    auto run = [&]() {
+      const uint32_t xy = bxy;
+      const DensePix px = bpx;
+      const bool live = lane < bn;
+      bn = 0;
+      const int x = (int)(xy & 0xffffu), y = (int)(xy >> 16);
+      const unsigned i = __umul24((unsigned)y, (unsigned)cols) + (unsigned)x;
+      FcaPix o;
+      bool oob;
+      if constexpr (FAST) {
+        bool valid;
+        const FcaInF rec = dense_form(g, px, x, y, valid);
+        const FcafStage st = fcaf_stage_a(g, tr, fc, rec);
+        o = fcaf_stage_b<false, -1>(a, K, g, cur, fc, i, st);   // (a.save_w = 0: nothing is stored; the weight reads 0 out of bounds)
+        oob = tap_oob(cols, g.rows, st.x1, st.y1);
+      } else {
+        FcaIn in;   // fca_load's values, from the planes
+        in.xy = xy;
+        in.Ikf = (float)px.I;
+        in.Z = px.Z;
+        in.var = px.var;
+        in.invZ = 1.0 / (double)px.Z;   // the compaction's expression (prep_scatter)
+        const float aX = ((float)x - g.cx) * in.Z, aY = ((float)y - g.cy) * in.Z;
+        in.X = DIVC ? div_const(aX, g.fx, g.rfx) : aX / g.fx;
+        in.Y = DIVC ? div_const(aY, g.fy, g.rfy) : aY / g.fy;
+        o = fca_pixel_in<false, DIVC>(a, K, g, cur, S, i, in);
+        const Warp wp = warp_point<true>(in.X, in.Y, in.Z, g, S);   // the point fca_pixel_in tapped (the same expressions)
+        oob = tap_oob(cols, g.rows, wp.wx, wp.wy);
+      }
+      const bool used = live && !oob;
+      n_used += __builtin_popcountll(__builtin_amdgcn_ballot_w64(used));
+      if (live) fca_accumulate_pixel(acc, o);
+      if (used) {
+        const float r2 = o.residual * o.residual;
+        sc[0] += r2;
+        sc[1] += fabsf(o.residual);
+        sc[2] += o.wgt;
+        sc[3] += o.wgt * r2;
+      }
+    };
+    // the depths of four steps are requested together, a group ahead (they depend on nothing but the walk)
+    const TripCount tc = trip_count(c.begin, c.end);
+    const int last = c.end - 1;
+    PlanePos pp[4], pn[4];
+    float zz[4], zn[4];
+    pp[0] = p;
+#pragma unroll
+    for (int j = 1; j < 4; j++) pp[j] = plane_next(w, pp[j - 1], last);
+    zz[0] = z;
+#pragma unroll
+    for (int j = 1; j < 4; j++) zz[j] = as_global(K.depth)[(unsigned)min(pp[j].i, last)];
+    for (int k = 0; k < tc.n_steps; k += 4) {
+      pn[0] = plane_next(w, pp[3], last);
+#pragma unroll
+      for (int j = 1; j < 4; j++) pn[j] = plane_next(w, pn[j - 1], last);
+#pragma unroll
+      for (int j = 0; j < 4; j++) zn[j] = as_global(K.depth)[(unsigned)min(pn[j].i, last)];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        if (k + j < tc.n_steps) {   // block-uniform
+          const bool push = tc.active(k + j) && zz[j] > 0.0f;
+          const unsigned long long m = __builtin_amdgcn_ballot_w64(push);
+          if (push) q[qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = (uint32_t)pp[j].x | ((uint32_t)pp[j].y << 16);
+          const int np = __builtin_popcountll(m);
+          qn += np;
+          n_depth += np;
+          if (qn >= 64) {
+            if (bn > 0) run();
+            pop(64);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) { pp[j] = pn[j]; zz[j] = zn[j]; }
+    }
+    if (bn > 0) run();
+    if (qn > 0) { pop(qn); run(); }
+  }
+  float sums[27];
+  fca_acc_unpack<FAST>(acc, sums);
+  float* rec = qa.partials + ((size_t)b * qa.nblk + sub) * ELLC_PART_STRIDE;
+  block_reduce_store<27>(sums, rec);
+  block_reduce_store<4>(sc, rec + 27);
+  __shared__ int cnt[ELLC_GN_THREADS / 64][2];
+  if ((t & 63) == 0) { cnt[t >> 6][0] = n_depth; cnt[t >> 6][1] = n_used; }
+  __syncthreads();
+  if (t < 2) {
+    int s = 0;
+#pragma unroll
+    for (int wv = 0; wv < ELLC_GN_THREADS / 64; wv++) s += cnt[wv][t];
+    qa.counts[((size_t)b * qa.nblk + sub) * 2 + t] = s;
+  }
+}
+
+// One block per alignment: the fixed-order f64 combine of the blocks' sums (partial_group_sum, then the eight groups in ascending
+// order, as solve_step does), H mirrored, the f32 LU of the exact solve (lu_inverse6_lanes) in both modes, the counts summed as
+// integers, and the record written to pinned host memory.
+__global__ __launch_bounds__(ELLC_SOLVE_THREADS) void gn_quality_finish(QualityArgs qa) {
+  const int b = blockIdx.x, t = threadIdx.x;
+  __shared__ double part[ELLC_SOLVE_THREADS / 32][32];
+  __shared__ double sums[32];
+  __shared__ int cnt[2];
+  const int comp = t & 31, grp = t >> 5;
+  part[grp][comp] = partial_group_sum(qa.partials + (size_t)b * qa.nblk * ELLC_PART_STRIDE, qa.nblk);
+  if (t < 2) cnt[t] = 0;
+  __syncthreads();
+  if (t < 31) {
+    double s = part[0][t];
+#pragma unroll
+    for (int gq = 1; gq < ELLC_SOLVE_THREADS / 32; gq++) s += part[gq][t];
+    sums[t] = s;
+  }
+  {   // integers: any order gives the same total
+    const int* cb = qa.counts + (size_t)b * qa.nblk * 2;
+    int d = 0, u = 0;
+    for (int k = t; k < qa.nblk; k += ELLC_SOLVE_THREADS) { d += cb[2 * k]; u += cb[2 * k + 1]; }
+    if (d) atomicAdd(&cnt[0], d);
+    if (u) atomicAdd(&cnt[1], u);
+  }
+  __syncthreads();
+  QualityRec* out = qa.out + b;
+  if (t < 64) {
+    float Hm[36];
+    {
+      int q = 0;
+#pragma unroll
+      for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int cc = r; cc < 6; cc++) {
+          const float v = (float)sums[q++];
+          Hm[r * 6 + cc] = v;
+          Hm[cc * 6 + r] = v;
+        }
+    }
+    if (t == 0) {
+#pragma unroll
+      for (int i = 0; i < 36; i++) out->H[i] = Hm[i];
+#pragma unroll
+      for (int i = 0; i < 6; i++) out->b[i] = (float)sums[21 + i];
+      out->n_depth = cnt[0];
+      out->n_used = cnt[1];
+      out->sum_r2 = sums[27];
+      out->sum_abs_r = sums[28];
+      out->sum_w = sums[29];
+      out->sum_wr2 = sums[30];
+    }
+    float x[6];
+    lu_inverse6_lanes(Hm, t < 6 ? t : 0, x);
+    if (t < 6) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) out->Hinv[i * 6 + t] = x[i];
+    }
+  }
+}
+
 }  // namespace ellc

@@ -20,6 +20,9 @@
 //                    sequence, the loop-closure batch (GlobalOptimize.cpp:480-610) is sharded over the ranks by
 //                    ellc_shard_range and its poses are gathered once per batch (ellc_gather_results); every rank writes
 //                    the same files into its own out_dir
+// --match-quality PATH  (LC mode) one line per line of matchframes_globalopt.txt: "frameId kfId n_depth n_used rms wrms" — how well the
+//                    candidate fits at the pose the batch returned (ellc_align_quality_at, level 0); every other file is unchanged.
+//                    Single process only: refused with --world > 1 (the gather record stays 8 floats)
 // Input is otherwise a header-less file of W*H u8 grey frames (the decode itself always stays outside).
 // In LC mode finished keyframes go through the loop-closure ring (facade class globalOptimize): matching and the batched
 // alignment of a pushed keyframe run on a second thread and a second context beside tracking, joined at the next push
@@ -36,7 +39,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -46,7 +49,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file;
+  std::string comm_id_file, match_quality;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -62,8 +65,13 @@ int main(int argc, char** argv) {
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (a == "--comm-id" && i + 1 < argc) comm_id_file = argv[++i];
     else if (a == "--comm-tcp" && i + 1 < argc) comm_port = std::atoi(argv[++i]);
+    else if (a == "--match-quality" && i + 1 < argc) match_quality = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return -1; }
+  }
+  if (!match_quality.empty() && world > 1) {
+    std::fprintf(stderr, "--match-quality is for a single process: with --world > 1 the ranks exchange poses only (8 floats per alignment)\n");
+    return -1;
   }
   const int KEYFRAME_PROPAGATE_INTERVAL = 8;   // ExternVariable.h:39
   std::ifstream f(in, std::ios::binary);
@@ -120,6 +128,11 @@ int main(int argc, char** argv) {
     depthMap currentDepthMap(rt);
     std::unique_ptr<globalOptimize> globalOptimizeLoop;
     if (lc) globalOptimizeLoop.reset(new globalOptimize(rt, outdir + "/matchframes_globalopt.txt"));
+    if (lc && !match_quality.empty()) {
+      globalOptimizeLoop->match_quality_file.open(match_quality.c_str());
+      if (!globalOptimizeLoop->match_quality_file) { std::fprintf(stderr, "cannot open %s\n", match_quality.c_str()); return -1; }
+      globalOptimizeLoop->collectMatchQuality = true;
+    }
     std::vector<std::unique_ptr<frame>> frameptr_vector;
     frame* activeKeyFrame = nullptr;
     std::vector<uint8_t> buf(bgr ? (size_t)W * H * 48 : (size_t)W * H);

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 10   /* r06: measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 11   /* ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -223,6 +223,33 @@ ellc_status ellc_align_fetch(ellc_ctx* ctx, int B, float* out_pose, int* out_ite
  * warpedX, warpedY, J0..J5 (display_iterationres, display_weightimg, savedWarpedPointsX/Y, steepest descent). */
 ellc_status ellc_gn_iterate(ellc_ctx* ctx, int kf_slot, int frame_slot, int level, int mode, int iter, const float* pose,
                             float* H36, float* b6, float* delta6, float* new_pose6, float* weighted, float* planes);
+
+/* How well a frame fits a keyframe at a pose the caller names (v11): ONE forward-compositional pixel pass at `level`, no update. The
+ * reference computes all of this in its pixel loop and keeps none of it: its own sum of the weighted squared residuals stands
+ * commented out at PixelWisePyramid.cpp:357 (//sumRes += wh * w_p * rp*rp;). */
+typedef struct {
+  int32_t n_depth;    /* pixels of the level with depth > 0 (the mask, Frame.cpp:295-301) */
+  int32_t n_used;     /* of those, pixels whose warped point gets an intensity (warpedintensity != -1, PixelWisePyramid.cpp:273) */
+  double  sum_r2;     /* sum of residual^2 over the used pixels (residual: :330) */
+  double  sum_abs_r;  /* sum of |residual| */
+  double  sum_w;      /* sum of res_weight (:358) */
+  double  sum_wr2;    /* sum of res_weight * residual^2: the reference's commented-out sumRes (:357) */
+  float   H[36];      /* sum of w J^T J, row-major, exactly symmetric (:373) */
+  float   b[6];       /* sum of w r J (:374) */
+  float   Hinv[36];   /* cv::Mat::inv(DECOMP_LU) of H as the solve restates it; all zeros when singular (:451) */
+} ellc_align_quality;
+/* B evaluations: record b describes frame slot frame_slots[b] against keyframe slot kf_slots[b] at pose[b] (B*6 f32) on pyramid level
+ * `level`. The quantities are always the forward-compositional ones (the per-iteration robust weight, :341-358), whatever mode the pose
+ * came from, in the arithmetic of cfg.arith: per pixel the values of ellc_gn_iterate's planes. Hinv is the f32 LU in both modes. A
+ * record is a function of the configuration, the level, the two slots and the pose ALONE: the grid per evaluation follows from the
+ * level's size, the block sums are combined in double in a fixed order, so B, the position in the batch, cfg.grid_batch and whatever
+ * else is in flight do not enter it, and a shard of a batch gives the bits of the whole batch. Evaluations of one call may share
+ * slots. Synchronous, ordered like every other non-batch entry point (behind the batches in flight, before later ones); reads the
+ * slots' planes only and writes nothing that belongs to a slot (no compact list, tile count, weight plane or validity mark).
+ * ELLC_ERR_BAD_ARG: B < 1, B > max_batch, a slot or the level out of range, a NULL pointer; ELLC_ERR_NOT_READY: a slot never
+ * uploaded, a keyframe without depth. */
+ellc_status ellc_align_quality_at(ellc_ctx* ctx, int B, const int* kf_slots, const int* frame_slots, const float* pose, int level,
+                                  ellc_align_quality* out);
 
 /* The display planes PixelWisePyramid fills beside the residual and the weights in a pass at `level` with `pose`
  * (PixelWisePyramid.cpp:209-225, :275-284; the reference shows display_warpedimg, ImageFunc.cpp:277): where the keyframe has a

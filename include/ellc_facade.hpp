@@ -397,6 +397,13 @@ class globalOptimize {
   int currentArrayId = 0, nextArrayId = 1;
   int match_window_beg = 0, match_window_end = MAX_LOOP_ARRAY_LENGTH - 1;
   float matchValue = 0, rms_error = 0, relative_view_angle = 0;
+  // How well each candidate of a loop-closure batch fits at the pose the batch returned (ellc_align_quality_at, level 0): the match
+  // file carries the histogram distance but no photometric figure (GlobalOptimize.cpp:566-582 accepts every candidate). Off by
+  // default: nothing changes. On: lastMatchQuality holds one record per line the batch wrote to the match file, in that order, and
+  // match_quality_file (when open) gets "frameId kfId n_depth n_used rms wrms" per line. What to do with the figures is the caller's.
+  bool collectMatchQuality = false;
+  std::vector<ellc_align_quality> lastMatchQuality;
+  std::ofstream match_quality_file;
 
   static ellc_config ring_config(const ellc_config& tracking, bool fixed_grids) {
     ellc_config c = tracking;
@@ -620,6 +627,10 @@ class globalOptimize {
       } else {
         ring.check(ellc_align(ring.ctx, B, kf.data(), fr.data(), init.data(), ELLC_MODE_ICA, 0, out.data(), nullptr, nullptr), "ellc_align");
       }
+      if (collectMatchQuality) {   // the call site beside GlobalOptimize.cpp:566: one pixel pass per candidate at the pose it came back with
+        lastMatchQuality.assign((size_t)B, ellc_align_quality());
+        ring.check(ellc_align_quality_at(ring.ctx, B, kf.data(), fr.data(), out.data(), 0, lastMatchQuality.data()), "ellc_align_quality_at");
+      }
       for (int b = 0; b < B; b++) {
         const loopFrame& m = loopFrameArray[matches[b].arrayId];
         float poseWrtOrigin[6];
@@ -631,8 +642,15 @@ class globalOptimize {
                      << " " << m.rescaleFactor << " " << seeds_num << " " << matches[b].matchValue << " " << matches[b].rms << " "
                      << matches[b].angle << "\n";
         }
+        if (collectMatchQuality && match_quality_file.is_open()) {
+          const ellc_align_quality& q = lastMatchQuality[(size_t)b];
+          const double rms = q.n_used > 0 ? std::sqrt(q.sum_r2 / (double)q.n_used) : 0.0, wrms = q.sum_w != 0.0 ? std::sqrt(q.sum_wr2 / q.sum_w) : 0.0;
+          match_quality_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << (m.frameId + rt->BATCH_START_ID - 1) << " " << q.n_depth << " "
+                             << q.n_used << " " << rms << " " << wrms << "\n";
+        }
       }
       match_file.flush();
+      if (match_quality_file.is_open()) match_quality_file.flush();
     }
     // :614-641
     currentArrayId++;

@@ -20,7 +20,8 @@ def kernels(path):
             out[name] = (res, body); name = None
             continue
         s = line.split(";")[0].strip()
-        if s and not s.startswith(".") and not s.endswith(":"): body.append(re.sub(r"\s+", " ", s))
+        # (a local label carries the index of its function in the module, which moves when a kernel is added in front: .LBB12_3 -> .LBB_3)
+        if s and not s.startswith(".") and not s.endswith(":"): body.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", s)))
     return out
 
 
