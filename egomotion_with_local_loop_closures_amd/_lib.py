@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
 DIAG_SYMBOLS = [
     "ellc_profile_gn_kernel", "ellc_profile_align", "ellc_profile_depth_stage", "ellc_profile_calibrate_read", "ellc_profile_stream_read",
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
-    "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters",
+    "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
     "ellc_debug_schedule_sums",
 ]
 

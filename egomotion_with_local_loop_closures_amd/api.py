@@ -355,6 +355,27 @@ class Context:
         self._need_diag("ellc_debug_set_count_cache")
         self._ck(self._l.ellc_debug_set_count_cache(self.h, int(bool(on))), "ellc_debug_set_count_cache")
 
+    def debug_set_packed_taps(self, on):
+        """Tolerance mode: 1 (default) the interior taps as one load from the row-packed plane, 0 as four row loads."""
+        self._need_diag("ellc_debug_set_packed_taps")
+        self._ck(self._l.ellc_debug_set_packed_taps(self.h, int(bool(on))), "ellc_debug_set_packed_taps")
+
+    def debug_row_tap_launches(self):
+        """Kernel argument records this context has built with the row loads selected (debug_set_packed_taps(False))."""
+        self._need_diag("ellc_debug_row_tap_launches")
+        n = C.c_longlong(0)
+        self._ck(self._l.ellc_debug_row_tap_launches(self.h, C.byref(n)), "ellc_debug_row_tap_launches")
+        return n.value
+
+    def debug_get_packed_level(self, frame_slot, level):
+        """The row-packed plane of a frame slot at `level` as a (stored_h, stored_w) uint32 array."""
+        self._need_diag("ellc_debug_get_packed_level")
+        sw = C.c_int(0); sh = C.c_int(0)
+        self._ck(self._l.ellc_get_image_level(self.h, 0, int(frame_slot), int(level), None, C.byref(sw), C.byref(sh), None, None), "ellc_get_image_level")
+        out = np.empty((sh.value, sw.value), np.uint32)
+        self._ck(self._l.ellc_debug_get_packed_level(self.h, int(frame_slot), int(level), out.ctypes.data_as(C.c_void_p)), "ellc_debug_get_packed_level")
+        return out
+
     def debug_count_cache_counters(self):
         """(groups that compacted with a count launch, groups that compacted without one) so far."""
         self._need_diag("ellc_debug_count_cache_counters")

@@ -45,6 +45,8 @@ struct LaunchPlan {
   bool track = false;         // the alignment belongs to ellc_track_frame (set_track_fields)
   const void* count_valid = nullptr;   // ... whose count of the valid hypotheses the launch that stages the batch takes along
   int count_n = 0;                     //     (the plane's size; 0: none)
+  bool row_taps = false;      // diagnostic library only (ellc_debug_set_packed_taps): the tolerance mode's interior taps as four row loads from
+                              // FrLevelDev::img, not one load from the row-packed plane (GnArgs::row_taps)
 };
 
 // ellc_track_frame's request to align_enqueue_impl: the alignment is its own (LaunchPlan::track), and the count it would like taken along
@@ -56,16 +58,16 @@ struct TrackRequest {
 // What tells one captured launch sequence from another: the plan's members that change what is captured, and cfg.grid_batch (the
 // grids). resident, direct and the count request are absent: such sequences are never captured.
 struct GraphKey {
-  int B, nu, mode, save_weights, continuation, track, pollable, adaptive_first, grid_batch, dense, need, skip_count, set;
+  int B, nu, mode, save_weights, continuation, track, pollable, adaptive_first, grid_batch, dense, need, skip_count, set, row_taps;
   bool operator<(const GraphKey& o) const {
     auto t = [](const GraphKey& k) {
-      return std::tie(k.B, k.nu, k.mode, k.save_weights, k.continuation, k.track, k.pollable, k.adaptive_first, k.grid_batch, k.dense, k.need, k.skip_count, k.set);
+      return std::tie(k.B, k.nu, k.mode, k.save_weights, k.continuation, k.track, k.pollable, k.adaptive_first, k.grid_batch, k.dense, k.need, k.skip_count, k.set, k.row_taps);
     };
     return t(*this) < t(o);
   }
 };
 inline GraphKey graph_key(const LaunchPlan& p, int grid_batch) {
-  return GraphKey{p.B, p.nu, p.mode, p.save_weights ? 1 : 0, p.continuation, p.track, p.pollable, p.adaptive_first, grid_batch, p.dense, p.need, p.skip_count, p.set};
+  return GraphKey{p.B, p.nu, p.mode, p.save_weights ? 1 : 0, p.continuation, p.track, p.pollable, p.adaptive_first, grid_batch, p.dense, p.need, p.skip_count, p.set, p.row_taps};
 }
 
 }  // namespace ellc
@@ -81,6 +83,8 @@ struct ellc_ctx {
   char* arena_base = nullptr;                // current chunk: device buffers are carved out of a few large allocations
   size_t arena_size = 0, arena_used = 0;
   bool fast = false;                         // cfg.arith == ELLC_ARITH_FAST
+  bool row_taps = false;                     // ellc_debug_set_packed_taps(0), diagnostic library only: see LaunchPlan::row_taps
+  long long row_tap_args = 0;                //   kernel argument records built with the row loads selected (ellc_debug_row_tap_launches)
   std::vector<void*> host_allocs;            // hipHostMalloc'ed
   std::vector<ellc::KfLevelDev> kf_tab_h;    // [L][max_kf]
   std::vector<ellc::FrLevelDev> fr_tab_h;    // [L][max_fr]
@@ -311,5 +315,6 @@ ellc_status build_depth_pyramid(ellc_ctx* c, int slot);
 ellc_status build_depth_pyramid_from(ellc_ctx* c, int slot, int first_level);
 ellc_status build_maxgrad(ellc_ctx* c, bool is_kf, int slot);
 ellc_status build_image_pyramid(ellc_ctx* c, uint8_t* const* img, hipStream_t st);
+ellc_status pack_frame_taps(ellc_ctx* c, int slot, hipStream_t st);
 ellc_status mark_frame_use(ellc_ctx* c, int slot);
 }  // namespace ellc

@@ -84,6 +84,8 @@ struct KfLevelDev {
 
 struct FrLevelDev {
   uint8_t* img;               // sw*sh
+  uint32_t* img4;             // sw*sh words, contexts of the tolerance mode only (else null): word (y, x) holds column x of rows y - 1 .. y + 2,
+                              // I(y-1,x) | I(y,x) << 8 | I(y+1,x) << 16 | I(y+2,x) << 24, a zero byte for a row outside the image (pack_tap_rows)
 };
 
 // Per-alignment state that persists across the launches of one ellc_align.

@@ -174,6 +174,27 @@ ellc_status build_image_pyramid(ellc_ctx* c, uint8_t* const* img, hipStream_t st
   return ELLC_OK;
 }
 
+// The row-packed planes (FrLevelDev::img4) of frame slot `slot` from its image planes, all levels in one launch. Every writer of a
+// frame slot's image planes calls this behind its last write, on the stream that wrote them: ellc_frame_upload (upload_pyramid),
+// ellc_frame_ingest_bgr, copy_slot_planes. Contexts of the exact mode keep no such planes.
+ellc_status pack_frame_taps(ellc_ctx* c, int slot, hipStream_t st) {
+  if (!c->fast) return ELLC_OK;
+  PackRowsArgs a;
+  a.levels = c->L;
+  a.begin[0] = 0;
+  for (int l = 0; l < ELLC_MAX_LEVELS; l++) {
+    const int q = std::min(l, c->L - 1);
+    const FrLevelDev& f = c->fr_tab_h[(size_t)q * c->cfg.max_frames + slot];
+    const LevelGeom& g = c->geom_h[q];
+    a.img[l] = f.img; a.img4[l] = f.img4;
+    a.sw[l] = g.sw; a.rows[l] = g.rows;
+    a.begin[l + 1] = a.begin[l] + (l < c->L ? ((g.sw + 3) / 4) * g.sh : 0);
+  }
+  hipLaunchKernelGGL(pack_tap_rows, dim3((a.begin[c->L] + 255) / 256), dim3(256), 0, st, a);
+  ELLC_HIP(c, hipGetLastError());
+  return ELLC_OK;
+}
+
 // Upload + pyramid without stalling the caller: the image is copied into one of a ring of pinned staging buffers (so the
 // caller's buffer is free when this returns, as with the blocking copy it replaces), and the host-to-device copy and the
 // pyramid launch are only enqueued. A staging buffer is reused once the copy that read it has completed (event).
@@ -181,7 +202,8 @@ ellc_status build_image_pyramid(ellc_ctx* c, uint8_t* const* img, hipStream_t st
 // is already enqueued on the main stream (in a tracking loop: the previous frame's depth stages, which read the OTHER frame
 // slot). Ordered on the device: behind the readers of this slot that are already enqueued (mark_frame_use, batches in flight),
 // and everything enqueued later on the main stream waits for it.
-static ellc_status upload_pyramid(ellc_ctx* c, uint8_t* const* img, const uint8_t* host, int frame_slot = -1) {
+// pack_slot >= 0: the planes are a frame slot's, whose row-packed planes follow the pyramid (pack_frame_taps).
+static ellc_status upload_pyramid(ellc_ctx* c, uint8_t* const* img, const uint8_t* host, int frame_slot = -1, int pack_slot = -1) {
   const LevelGeom* g = c->geom_h;
   hipStream_t st = c->stream;
   if (frame_slot >= 0) {
@@ -218,7 +240,8 @@ static ellc_status upload_pyramid(ellc_ctx* c, uint8_t* const* img, const uint8_
     const int blocks = (int)std::min<size_t>(1024, ((bytes >> 4) + 255) / 256 + 1);
     hipLaunchKernelGGL(ingest_copy_u8, dim3(blocks), dim3(256), 0, st, img[0], (const uint8_t*)stage_dev, bytes);
   }
-  const ellc_status s = build_image_pyramid(c, img, st);
+  ellc_status s = build_image_pyramid(c, img, st);
+  if (s == ELLC_OK && pack_slot >= 0) s = pack_frame_taps(c, pack_slot, st);
   // (behind the pyramid launch, not between the two kernels: an event record there held the pyramid back ~7 us; the staging buffer is
   // one of a ring of four and is free by the time its turn comes again either way)
   ELLC_HIP(c, hipEventRecord(c->upload_done[k], st));
@@ -346,6 +369,10 @@ static GnArgs make_gn_args(ellc_ctx* c, const LaunchPlan& p, int level, int save
   a.max_fr = c->cfg.max_frames;
   a.nblk = choose_nblk(c, level, grid_batch(c, p.B), p.dense);
   a.save_w = save_w;
+#ifdef ELLC_ROW_TAPS
+  a.row_taps = p.row_taps ? 1 : 0;
+  if (p.row_taps) c->row_tap_args++;
+#endif
   return a;
 }
 
@@ -999,7 +1026,12 @@ ellc_status ellc_ctx_create(const ellc_config* cfg, ellc_ctx** out) {
       TRY(dev_alloc(c, &k.irec, n)); TRY(dev_alloc(c, &k.hpart, (size_t)(tiles + 1) * ELLC_PART_STRIDE)); TRY(dev_alloc(c, &k.hinv, 36));
     }
     // (+ one row: the fifth row of gn_fca_dense4's tap windows may be the one below the image)
-    for (int s = 0; s < MF; s++) TRY(dev_alloc(c, &c->fr_tab_h[(size_t)l * MF + s].img, ni + (size_t)g.sw + 32));
+    for (int s = 0; s < MF; s++) {
+      FrLevelDev& f = c->fr_tab_h[(size_t)l * MF + s];
+      TRY(dev_alloc(c, &f.img, ni + (size_t)g.sw + 32));
+      f.img4 = nullptr;
+      if (c->fast) TRY(dev_alloc(c, &f.img4, ni + (size_t)g.sw + 32));   // (words; the same slack rule as img)
+    }
   }
   TRY(dev_alloc(c, &c->kf_tab_d, c->kf_tab_h.size()));
   TRY(dev_alloc(c, &c->fr_tab_d, c->fr_tab_h.size()));
@@ -1263,6 +1295,31 @@ ellc_status ellc_debug_set_count_cache(ellc_ctx* c, int on) {
   c->count_cache = on != 0;
   return ELLC_OK;
 }
+ellc_status ellc_debug_set_packed_taps(ellc_ctx* c, int on) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  ELLC_ENTER(c);
+#ifndef ELLC_ROW_TAPS
+  if (!on) return fail(c, ELLC_ERR_BAD_ARG, "ellc_debug_set_packed_taps: this build was compiled without the row loads (ELLC_NO_ROW_TAPS)");
+#endif
+  c->row_taps = !on;   // (read by make_plan and the diagnostic plans: LaunchPlan::row_taps; ellc_align_quality_at reads it directly)
+  return ELLC_OK;
+}
+ellc_status ellc_debug_row_tap_launches(ellc_ctx* c, long long* n) {
+  if (!c || !n) return ELLC_ERR_BAD_ARG;
+  ELLC_ENTER(c);
+  *n = c->row_tap_args;
+  return ELLC_OK;
+}
+ellc_status ellc_debug_get_packed_level(ellc_ctx* c, int frame_slot, int level, uint32_t* out) {
+  if (!c || !out || level < 0 || level >= c->L || !slot_ok(frame_slot, c->cfg.max_frames)) return fail(c, ELLC_ERR_BAD_ARG, "bad argument");
+  ELLC_ENTER(c);
+  if (!c->fast) return fail(c, ELLC_ERR_NOT_READY, "ellc_debug_get_packed_level: contexts of the exact mode keep no packed planes");
+  if (!c->fr_has_image[frame_slot]) return fail(c, ELLC_ERR_NOT_READY, "slot empty");
+  const LevelGeom& g = c->geom_h[level];
+  ELLC_HIP(c, hipMemcpyAsync(out, c->fr_tab_h[(size_t)level * c->cfg.max_frames + frame_slot].img4, (size_t)g.sw * g.sh * 4, hipMemcpyDeviceToHost, c->stream));
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  return ELLC_OK;
+}
 ellc_status ellc_debug_count_cache_counters(ellc_ctx* c, long long* groups_counted, long long* groups_skipped) {
   if (!c) return ELLC_ERR_BAD_ARG;
   ELLC_ENTER(c);
@@ -1316,7 +1373,7 @@ ellc_status ellc_frame_upload(ellc_ctx* c, int slot, const uint8_t* image) {
   // queues that run concurrently, and a context with batches in flight needs them for its batch streams; r03: with the fourth
   // stream the pipeline of sixteen batches fell from 7.7 to 6.3 M iterations/s)
   const bool own_stream = c->cfg.concurrent_batches <= 1 && c->coalesce <= 1;
-  ellc_status s = upload_pyramid(c, img, image, own_stream ? slot : -1);
+  ellc_status s = upload_pyramid(c, img, image, own_stream ? slot : -1, slot);
   if (s != ELLC_OK) return s;
   c->fr_has_image[slot] = 1;
   c->fr_maxgrad_valid[slot] = 0;
@@ -1576,6 +1633,7 @@ static ellc_status copy_slot_planes(ellc_ctx* dc, int dst_is_kf, int dst, ellc_c
   } else {
     dc->fr_has_image[dst] = 1;
     dc->fr_maxgrad_valid[dst] = 0;
+    return pack_frame_taps(dc, dst, dc->stream);   // (from the copied image planes: the source context may be of the exact mode and keep none)
   }
   return ELLC_OK;
 }
@@ -1665,6 +1723,7 @@ static LaunchPlan make_plan(const ellc_ctx* c, int B, int nu, int mode, int save
   p.resident = resident;
   p.adaptive_first = schedule_is_adaptive(c, mode, B) ? adaptive_first_launches(c, resident) : 0;   // (it varies with the context's hint)
   p.direct = launches_directly(c, mode, B);
+  p.row_taps = c->row_taps;
   return p;
 }
 
@@ -2134,6 +2193,7 @@ ellc_status ellc_gn_iterate(ellc_ctx* c, int kf_slot, int frame_slot, int level,
   ellc_status s = stage_batch(c, 1, &kf_slot, &frame_slot, pose, &nu);
   if (s != ELLC_OK) return s;
   LaunchPlan plan;   // (not a production sequence: staged through the pinned record, with a count launch)
+  plan.row_taps = c->row_taps;
   plan.B = 1;
   plan.nu = nu;
   plan.mode = mode;
@@ -2240,6 +2300,10 @@ ellc_status ellc_align_quality_at(ellc_ctx* c, int B, const int* kf_slots, const
   qa.max_fr = c->cfg.max_frames;
   qa.nblk = quality_nblk(c, level);
   qa.max_batch = MB;
+#ifdef ELLC_ROW_TAPS
+  qa.row_taps = c->row_taps ? 1 : 0;
+  if (c->row_taps) c->row_tap_args++;
+#endif
   const dim3 grd(qa.nblk, B), blk(ELLC_GN_THREADS);
   if (c->fast) hipLaunchKernelGGL((gn_fca_quality<true, false>), grd, blk, 0, c->stream, qa);
   else if (c->geom_h[0].divc_ok) hipLaunchKernelGGL((gn_fca_quality<false, true>), grd, blk, 0, c->stream, qa);
@@ -2261,6 +2325,7 @@ ellc_status ellc_gn_display_planes(ellc_ctx* c, int kf_slot, int frame_slot, int
   ellc_status s = stage_batch(c, 1, &kf_slot, &frame_slot, pose, &nu);
   if (s != ELLC_OK) return s;
   LaunchPlan plan;
+  plan.row_taps = c->row_taps;
   plan.B = 1;
   enqueue_stage_in(c, plan, 0);   // staging only
   hipLaunchKernelGGL(gn_set_pose0, dim3(1), dim3(1), 0, c->stream, c->state_d, c->init_pose_d);
@@ -2321,6 +2386,7 @@ ellc_status ellc_profile_gn_kernel(ellc_ctx* c, int B, const int* kf_slots, cons
   // the kernel the production schedule would launch for these keyframes (the grids of list-free launches are sized for their kernel)
   const bool dense = group_is_dense(c, ELLC_MODE_FCA, B, 0, kf_slots, B);
   LaunchPlan plan;   // (staged through the pinned record, with a count launch, whatever the production sequence would do)
+  plan.row_taps = c->row_taps;
   plan.B = B;
   plan.nu = dense ? 0 : nu;
   plan.dense = dense;

@@ -214,6 +214,7 @@ ellc_status ellc_frame_ingest_bgr(ellc_ctx* c, int slot, const uint8_t* bgr, uin
                      g[0].sw, gd, ud);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && build_image_pyramid(c, img, c->stream) != ELLC_OK) e = hipErrorUnknown;
+  if (e == hipSuccess && pack_frame_taps(c, slot, c->stream) != ELLC_OK) e = hipErrorUnknown;
   if (e == hipSuccess && gd) e = hipMemcpyAsync(gray_probe, gd, (size_t)ow * oh, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess && ud) e = hipMemcpyAsync(undistorted_probe, ud, (size_t)ow * oh * 4, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host frame buffer may be pageable

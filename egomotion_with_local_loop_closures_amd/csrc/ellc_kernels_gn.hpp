@@ -115,6 +115,18 @@ typedef uint32_t u32_align1 __attribute__((aligned(1)));
 __device__ __forceinline__ uint32_t load_u32_unaligned(g_u8 base, unsigned byte_off) {
   return *(const ELLC_GLOBAL u32_align1*)(base + byte_off);
 }
+// two / four dwords in one load: at any byte (a1), at a 4-aligned address (a4)
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef u32x2_t u32x2_a1 __attribute__((aligned(1)));
+typedef u32x2_t u32x2_a4 __attribute__((aligned(4)));
+typedef u32x4_t u32x4_a4 __attribute__((aligned(4)));
+// The row loads of the tolerance mode's taps (r04-r07) are compiled into the diagnostic library only, as the other side of the packed
+// taps' A/B (ellc_debug_set_packed_taps); -DELLC_NO_ROW_TAPS leaves them out of a diagnostic-ABI build too, so that a variant build
+// carries the shipping kernels under the measurement hooks (tools/ab_level0.sh, tools/ab_c4.sh).
+#if defined(ELLC_DIAG_ABI) && !defined(ELLC_NO_ROW_TAPS)
+#define ELLC_ROW_TAPS 1
+#endif
 template <int N>
 __device__ __forceinline__ float byte_f32(uint32_t w) { return (float)((w >> (8 * N)) & 0xffu); }   // v_cvt_f32_ubyteN
 
@@ -262,8 +274,13 @@ template <class F> struct LatPF { F f; __device__ __forceinline__ void operator(
 template <class T> struct is_lat_pf { static constexpr bool value = false; };
 template <class F> struct is_lat_pf<LatPF<F>> { static constexpr bool value = true; };
 template <class F> __device__ __forceinline__ LatPF<F> lat_pf(F f) { return LatPF<F>{f}; }
-template <bool WANT_GRAD, bool FAST = false, class AfterIssue = NoPrefetch>
-__device__ __forceinline__ Taps tap_point(g_u8 img, int sw, int cols, int rows, float x1, float y1, AfterIssue after_issue = AfterIssue()) {
+// PACKED (tolerance mode without gradients, the constant-weight path; r08): columns x0 and x0 + 1 come as ONE 8-byte load from the
+// frame's row-packed plane img4 (FrLevelDev::img4), rows y0 and y0 + 1 in bytes 1 and 2 of each word; row_taps (diagnostic library
+// only, block-uniform): the two row loads all the same.
+template <bool WANT_GRAD, bool FAST = false, class AfterIssue = NoPrefetch, bool PACKED = false>
+__device__ __forceinline__ Taps tap_point(g_u8 img, int sw, int cols, int rows, float x1, float y1, AfterIssue after_issue = AfterIssue(),
+                                          g_u8 img4 = nullptr, bool row_taps = false) {
+  static_assert(!PACKED || (FAST && !WANT_GRAD), "the packed form serves the tolerance mode's intensity-only taps");
   Taps o;
   const float fx0 = floorf(x1), fy0 = floorf(y1);
   const float wx = x1 - fx0, wy = y1 - fy0;
@@ -275,13 +292,19 @@ __device__ __forceinline__ Taps tap_point(g_u8 img, int sw, int cols, int rows, 
     const int x0 = (int)fx0, y0 = (int)fy0;
     uint32_t wa = 0, wb, wc, wd = 0;
     const unsigned ob = __umul24((unsigned)y0, (unsigned)sw) + (unsigned)x0 - 1u, oc = ob + (unsigned)sw;   // y0 >= 1, sw < 2^24: full-rate v_mad_u32_u24
-    wb = load_u32_unaligned(img, ob);
-    wc = load_u32_unaligned(img, oc);
-    if (WANT_GRAD) { wa = load_u32_unaligned(img, ob - (unsigned)sw); wd = load_u32_unaligned(img, oc + (unsigned)sw); }
+    const bool packed = PACKED && !row_taps;
+    if (packed) {   // wb, wc: columns x0, x0 + 1 (rows y0, y0 + 1 in bytes 1, 2) in place of rows y0, y0 + 1 (columns x0, x0 + 1 in bytes 1, 2)
+      const u32x2_t v = *(const ELLC_GLOBAL u32x2_a4*)(img4 + ((ob + 1u) << 2));
+      wb = v.x; wc = v.y;
+    } else {
+      wb = load_u32_unaligned(img, ob);
+      wc = load_u32_unaligned(img, oc);
+      if (WANT_GRAD) { wa = load_u32_unaligned(img, ob - (unsigned)sw); wd = load_u32_unaligned(img, oc + (unsigned)sw); }
+    }
     __builtin_amdgcn_sched_barrier(0);
     after_issue();
     __builtin_amdgcn_sched_barrier(0);
-    const float Pbb = byte_f32<1>(wb), Pbc = byte_f32<2>(wb), Pcb = byte_f32<1>(wc), Pcc = byte_f32<2>(wc);
+    const float Pbb = byte_f32<1>(wb), Pbc = packed ? byte_f32<1>(wc) : byte_f32<2>(wb), Pcb = packed ? byte_f32<2>(wb) : byte_f32<1>(wc), Pcc = byte_f32<2>(wc);
     if (FAST) {
       const float top = __builtin_fmaf(wx, Pbc - Pbb, Pbb);
       const float btm = __builtin_fmaf(wx, Pcc - Pcb, Pcb);
@@ -336,8 +359,8 @@ __device__ __forceinline__ Taps tap_point(g_u8 img, int sw, int cols, int rows, 
 //         integer forms, v_lshlrev, SDWA and DPP forms, f64, the packed f32 forms (v_pk_fma_f32 does two fmas for the price of 1.8) —
 //         AND any instruction of the first group that names an SGPR;
 //   ~8.5  v_rcp / v_rsq_f32.
-// Hence: the per-block constants live in VGPRs (FcafConst); the four rows of the 4 x 4 neighbourhood are four uniform base
-// pointers with ONE lane offset (no per-row address arithmetic in the vector ALU); floor and fraction come from v_cvt_flr_i32_f32
+// Hence: the per-block constants live in VGPRs (FcafConst); the 4 x 4 neighbourhood is ONE uniform base pointer with ONE
+// lane offset (r08: one 16-byte load of the row-packed plane, see TapRows; r04-r07: four uniform row pointers with one offset); floor and fraction come from v_cvt_flr_i32_f32
 // and v_fract_f32 (the interior test is two unsigned compares on the integers); the twelve bytes are converted by twelve
 // v_cvt_f32_ubyteN and differenced in f32 (left to itself the compiler subtracts the bytes with SDWA integer instructions and
 // converts the differences: 26 slow instructions for these 12 + 8 fast ones).
@@ -345,13 +368,39 @@ __device__ __forceinline__ Taps tap_point(g_u8 img, int sw, int cols, int rows, 
 // 460 -> 396 cycles of modelled issue (tools/isa_cost.py); the level-0 launch over 128 alignments 45.8 -> 43.6 us, the batch
 // pipeline 0.1331 -> 0.1312 ms per step. Far less than the instructions saved: the pass is bound by the CU's memory pipeline as much
 // as by its vector ALU (the same loop without its loads: 214 of 389 us at 1280x960 dense, 33 of 44 us at 640x480).
-struct TapRows { g_u8 ra, rb, rc, rd; };   // image - 1 + (-1, 0, 1, 2) * pitch: column x0 - 1 of rows y0 - 1 .. y0 + 2 sits at row pointer + y0 * pitch + x0
-__device__ __forceinline__ TapRows tap_rows(g_u8 img, int sw) {
-  TapRows r;
+// r08: the 4 x 4 neighbourhood comes as ONE 16-byte load at a 4-aligned address from the frame's row-packed plane (FrLevelDev::img4:
+// word (y, x) = column x of rows y - 1 .. y + 2): word k of the load is column x0 - 1 + k, byte r of a word is row y0 - 1 + r. The same
+// twelve bytes reach the same twelve v_cvt_f32_ubyteN from transposed places; nothing behind the conversions knows. What the vector
+// cache is asked per wave-step (tools/micro/quad_window.hip, 64 valid pixels among 256 consecutive): 30 cycles against 64 for the four
+// rows. The row loads remain in the diagnostic library (ELLC_DIAG_ABI) as the A/B's other side: GnArgs::row_taps.
+struct TapRows {
+  g_u8 p4;   // img4 less one word: the load for (y0, x0) starts at p4 + 4 (y0 * pitch + x0)
+#ifdef ELLC_ROW_TAPS
+  g_u8 ra, rb, rc, rd;   // image - 1 + (-1, 0, 1, 2) * pitch: column x0 - 1 of rows y0 - 1 .. y0 + 2 sits at row pointer + y0 * pitch + x0
+  bool rows;             // block-uniform: the four row loads
+#endif
+};
+struct RowPtrs { g_u8 ra, rb, rc, rd; };   // image - 1 + (-1, 0, 1, 2) * pitch (gn_fca_dense4's row windows)
+__device__ __forceinline__ RowPtrs row_ptrs(g_u8 img, int sw) {
+  RowPtrs r;
   r.rb = img - 1;
   r.ra = r.rb - sw;
   r.rc = r.rb + sw;
   r.rd = r.rc + sw;
+  return r;
+}
+struct GnArgs;
+__device__ __forceinline__ bool row_taps_of(const GnArgs& a);
+__device__ __forceinline__ TapRows tap_rows(const GnArgs& a, g_u8 img, g_u8 img4, int sw) {
+  TapRows r;
+  r.p4 = img4 - 4;
+#ifdef ELLC_ROW_TAPS
+  r.rb = img - 1;
+  r.ra = r.rb - sw;
+  r.rc = r.rb + sw;
+  r.rd = r.rc + sw;
+  r.rows = row_taps_of(a);
+#endif
   return r;
 }
 template <int N>
@@ -372,8 +421,11 @@ __device__ __forceinline__ int cvt_floor_i32(float x) {   // floor, then the sat
 // general path, the synchronous per-tap loads) into the taps. (r04 put the next pixel's request in front of the current pixel's
 // finish — a software pipeline over pixels: 1280x960 dense 387 against 389 us, 640x480 5 % slower, 125 registers: not kept.)
 struct TapReq {
-  uint32_t wa, wb, wc, wd;   // rows y0 - 1 .. y0 + 2, columns x0 - 1 .. x0 + 2 (valid when interior)
+  uint32_t wa, wb, wc, wd;   // columns x0 - 1 .. x0 + 2, each rows y0 - 1 .. y0 + 2 (valid when interior); `rows`: the transpose
   bool interior;             // wave-uniform: every lane that was active at the request samples the interior
+#ifdef ELLC_ROW_TAPS
+  bool rows;
+#endif
 };
 template <bool WANT_GRAD, class AfterIssue = NoPrefetch>
 __device__ __forceinline__ TapReq tap_request_f(const TapRows& tr, int sw, int cols, int rows, float x1, float y1, AfterIssue after_issue = AfterIssue()) {
@@ -388,9 +440,13 @@ __device__ __forceinline__ TapReq tap_request_f(const TapRows& tr, int sw, int c
   // first bytes — which a software pipeline over pixels needs: 5 % slower on the batch pipeline, the coarse levels' waves on the
   // image border pay for four requests they do not use)
   q.wb = 0; q.wc = 0;
+#ifdef ELLC_ROW_TAPS
+  q.rows = tr.rows;
+#endif
   if (q.interior) {
     const unsigned off = __umul24((unsigned)y0, (unsigned)sw) + (unsigned)x0;
-#ifdef ELLC_X_LDSTAPS   // variant builds only (tools/pmc_ldstaps.sh; WRONG values): what the four rows would cost as reads of an LDS
+#ifdef ELLC_X_LDSTAPS   // variant builds only (tools/pmc_ldstaps.sh; WRONG values, and since r08 the words are in ROW layout while tap_finish_f
+                        // decodes the packed, transposed one: a cost model only): what the four rows would cost as reads of an LDS
                         // window that is already there — two aligned dwords + v_alignbit per row, no staging, no window arithmetic
     __shared__ uint32_t xl[4 * 1024 + 4];
     const unsigned o = (off >> 2) & 1023u, shb = (off & 3u) * 8u;
@@ -398,9 +454,21 @@ __device__ __forceinline__ TapReq tap_request_f(const TapRows& tr, int sw, int c
     q.wc = __builtin_amdgcn_alignbit(xl[1024 + o + 1], xl[1024 + o], shb);
     if (WANT_GRAD) { q.wa = __builtin_amdgcn_alignbit(xl[2048 + o + 1], xl[2048 + o], shb); q.wd = __builtin_amdgcn_alignbit(xl[3072 + o + 1], xl[3072 + o], shb); }
 #else
-    q.wb = load_u32_unaligned(tr.rb, off);
-    q.wc = load_u32_unaligned(tr.rc, off);
-    if (WANT_GRAD) { q.wa = load_u32_unaligned(tr.ra, off); q.wd = load_u32_unaligned(tr.rd, off); }
+#ifdef ELLC_ROW_TAPS
+    if (tr.rows) {
+      q.wb = load_u32_unaligned(tr.rb, off);
+      q.wc = load_u32_unaligned(tr.rc, off);
+      if (WANT_GRAD) { q.wa = load_u32_unaligned(tr.ra, off); q.wd = load_u32_unaligned(tr.rd, off); }
+    } else
+#endif
+    {
+      // off < 2^24: no carry out of the 32-bit offset. The shift is the pixel step's one new vector instruction (v_lshlrev_b32). Tried:
+      // x0 * 4 + y0 * (4 pitch) as two 24-bit multiply-adds compiles to the same shift in front of the v_mad_u32_u24, plus a scalar
+      // multiply per block (115 instructions against 114); an index scaled by a buffer descriptor's stride needs the struct buffer
+      // load, for which this compiler has no builtin (the raw form takes a byte offset) - NOTEBOOK 6.14
+      const u32x4_t v = *(const ELLC_GLOBAL u32x4_a4*)(tr.p4 + (off << 2));
+      q.wa = v.x; q.wb = v.y; q.wc = v.z; q.wd = v.w;
+    }
 #endif
     __builtin_amdgcn_sched_barrier(0);
     after_issue();   // behind the row requests: vector loads return in issue order
@@ -415,13 +483,23 @@ __device__ __forceinline__ Taps tap_finish_f(const TapReq& q, g_u8 img, int sw, 
   if (q.interior) {
     Taps o;
     const float wx = __builtin_amdgcn_fractf(x1), wy = __builtin_amdgcn_fractf(y1);   // x - floor(x), exact for x >= 1
-    const float Pbb = cvt_ubyte<1>(q.wb), Pbc = cvt_ubyte<2>(q.wb), Pcb = cvt_ubyte<1>(q.wc), Pcc = cvt_ubyte<2>(q.wc);
+    // P<row><column>, a .. d = y0 - 1 .. y0 + 2 and x0 - 1 .. x0 + 2: byte <row> of word <column>
+    float Pbb = cvt_ubyte<1>(q.wb), Pbc = cvt_ubyte<1>(q.wc), Pcb = cvt_ubyte<2>(q.wb), Pcc = cvt_ubyte<2>(q.wc);
+#ifdef ELLC_ROW_TAPS
+    if (q.rows) { Pbb = cvt_ubyte<1>(q.wb); Pbc = cvt_ubyte<2>(q.wb); Pcb = cvt_ubyte<1>(q.wc); Pcc = cvt_ubyte<2>(q.wc); }
+#endif
     const float top = __builtin_fmaf(wx, Pbc - Pbb, Pbb);
     const float btm = __builtin_fmaf(wx, Pcc - Pcb, Pcb);
     o.I = __builtin_fmaf(wy, btm - top, top);
     if (WANT_GRAD) {
-      const float Pba = cvt_ubyte<0>(q.wb), Pbd = cvt_ubyte<3>(q.wb), Pca = cvt_ubyte<0>(q.wc), Pcd = cvt_ubyte<3>(q.wc);
-      const float Pab = cvt_ubyte<1>(q.wa), Pac = cvt_ubyte<2>(q.wa), Pdb = cvt_ubyte<1>(q.wd), Pdc = cvt_ubyte<2>(q.wd);
+      float Pba = cvt_ubyte<1>(q.wa), Pbd = cvt_ubyte<1>(q.wd), Pca = cvt_ubyte<2>(q.wa), Pcd = cvt_ubyte<2>(q.wd);
+      float Pab = cvt_ubyte<0>(q.wb), Pac = cvt_ubyte<0>(q.wc), Pdb = cvt_ubyte<3>(q.wb), Pdc = cvt_ubyte<3>(q.wc);
+#ifdef ELLC_ROW_TAPS
+      if (q.rows) {
+        Pba = cvt_ubyte<0>(q.wb); Pbd = cvt_ubyte<3>(q.wb); Pca = cvt_ubyte<0>(q.wc); Pcd = cvt_ubyte<3>(q.wc);
+        Pab = cvt_ubyte<1>(q.wa); Pac = cvt_ubyte<2>(q.wa); Pdb = cvt_ubyte<1>(q.wd); Pdc = cvt_ubyte<2>(q.wd);
+      }
+#endif
       const float g00 = Pbc - Pba, g01 = Pbd - Pbb, g10 = Pcc - Pca, g11 = Pcd - Pcb;   // twice the central differences
       float t2 = __builtin_fmaf(wx, g01 - g00, g00);
       float b2 = __builtin_fmaf(wx, g11 - g10, g10);
@@ -548,7 +626,17 @@ struct GnArgs {
   float* planes;                // debug: 10 planes of n floats (B must be 1), else null
   int level, max_kf, max_fr, nblk;
   int save_w;                   // write per-pixel weights of this iteration into kf.wlast
+#ifdef ELLC_ROW_TAPS
+  int row_taps;                 // LaunchPlan::row_taps
+#endif
 };
+__device__ __forceinline__ bool row_taps_of(const GnArgs& a) {
+#ifdef ELLC_ROW_TAPS
+  return a.row_taps != 0;
+#else
+  return false;
+#endif
+}
 
 // Wave-wide sums of NV values by a halving transpose: v_permlane32_swap exchanges the upper half of one register with the
 // lower half of another, so ONE swap and ONE add turn two values into one register whose halves carry one value each (summed
@@ -737,7 +825,6 @@ __device__ __forceinline__ FcaPix fca_pixel(const GnArgs& a, const KfLevelDev& K
 // 12-byte records (FcaRecF, ellc_device.hpp; r05); r04: written for the issue classes of the vector ALU (see tap_request_f).
 // (a record slot is kept as ONE vector value: it is carried around the pixel loop while its load is in flight, and a slot made of
 // scalars makes the register allocator copy them at the loop's back edge — copies that wait for the load)
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 struct FcaInF { u32x4_t v; };   // FcaRecF in registers: x | y << 12 | I << 24, variance, d = 1 / Z (the fourth word is unused)
 __device__ __forceinline__ FcaInF fcaf_empty() { FcaInF in; in.v = (u32x4_t){0u, 0u, 0x3f800000u, 0u}; return in; }   // x = y = 0, I = 0, var = 0, d = 1
 
@@ -941,9 +1028,10 @@ __global__ __launch_bounds__(ELLC_GN_THREADS) void gn_fca_accumulate(GnArgs a) {
 #pragma unroll
   for (int i = 0; i < 12; i++) S[i] = st.S[i];
   g_u8 cur = as_global(F.img);
+  g_u8 cur4 = (g_u8)as_global(F.img4);
   FcaAcc acc;
   fca_acc_zero(acc);
-  const TapRows tr = tap_rows(cur, g.sw);
+  const TapRows tr = tap_rows(a, cur, cur4, g.sw);
   const FcafConst fc = fcaf_const(g, S);
   for (int i = begin + (int)threadIdx.x; i < end; i += ELLC_GN_THREADS) {
     FcaPix p;
@@ -1742,7 +1830,7 @@ __device__ __forceinline__ PlanePos plane_next(const PlaneWalk& w, const PlanePo
 // entries begin + t, begin + t + 256, ...; the thread's first record (and, in the exact mode, its pose-independent products)
 // was requested by the caller before the solve. newS: exp(pose) of this iteration (LDS). Leaves the thread's 27 sums.
 template <bool DIVC, bool PIPE, bool FAST, int SAVEW, bool LAT = false>   // LAT: the latency regime (tap_general)
-__device__ __forceinline__ void fca_chunk_pass(const GnArgs& a, const KfLevelDev& K, const LevelGeom& g, g_u8 cur, const float* newS, int begin,
+__device__ __forceinline__ void fca_chunk_pass(const GnArgs& a, const KfLevelDev& K, const LevelGeom& g, g_u8 cur, g_u8 cur4, const float* newS, int begin,
                                                int end, const FcaIn& first, const FcaInF& firstf, const FcaPre& first_pre, float (&sums)[27]) {
   constexpr int stride = ELLC_GN_THREADS;
   const int t = threadIdx.x;
@@ -1754,7 +1842,7 @@ __device__ __forceinline__ void fca_chunk_pass(const GnArgs& a, const KfLevelDev
   int i = begin + t;
   if constexpr (FAST) {
     if (begin < end) {   // block-uniform
-      const TapRows tr = tap_rows(cur, g.sw);
+      const TapRows tr = tap_rows(a, cur, cur4, g.sw);
       const FcafConst fc = fcaf_const(g, S);
       ELLC_PTRACE(4, 0);
       // One pixel per step: the rows are requested and used in the same step; the next pixel's record is requested behind them. The
@@ -1845,6 +1933,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_fused(const AlignSt
   const double group_sum = partial_group_sum(pending_partials(prev_part, b), prev_nblk);
   const Chunk c = m.chunk(fa.age_cum, V, nblk);
   g_u8 cur = as_global(F.img);
+  g_u8 cur4 = (g_u8)as_global(F.img4);
   FirstRec first = no_record();
   request_first<DIVC, FAST, true>(first, K, g, c, t, true);
   advance_pose<FAST>(sh, pending, group_sum, 0, fa.prev_level, fa.early_exit, src);
@@ -1852,7 +1941,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_fused(const AlignSt
   ELLC_BSTAMP(1);
   if (publish_level_bound(sh, src, next_state(fa, b), sub == 0, pending, fa.prev_level, a.level)) return;
   float sums[27];
-  fca_chunk_pass<DIVC, PIPE, FAST, SAVEW>(a, K, g, cur, sh.newS, c.begin, c.end, first.in, first.inf, first.pre, sums);
+  fca_chunk_pass<DIVC, PIPE, FAST, SAVEW>(a, K, g, cur, cur4, sh.newS, c.begin, c.end, first.in, first.inf, first.pre, sums);
   ELLC_STAMP(7);
   ELLC_BSTAMP(2);
   block_reduce_store<27>(sums, partial_record(fa, fa.seq, b, sub));
@@ -1918,6 +2007,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_dense(const AlignSt
   const double group_sum = partial_group_sum(pending_partials(prev_part, b), prev_nblk);
   const Chunk c = m.chunk(fa.age_cum, g.n, nblk);   // the "list" is the plane
   g_u8 cur = as_global(F.img);
+  g_u8 cur4 = (g_u8)as_global(F.img4);
   // this thread's first pixel: position and planes, requested before the solve
   const int sw = g.sw;
   const PlaneWalk w = plane_walk(g.cols);
@@ -1935,7 +2025,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_dense(const AlignSt
     FcaAcc acc;
     fca_acc_zero(acc);
     if (c.begin < c.end) {   // block-uniform
-      const TapRows tr = tap_rows(cur, sw);
+      const TapRows tr = tap_rows(a, cur, cur4, sw);
       const FcafConst fc = fcaf_const(g, S);
       dense_plane_pass(c, w, sw, p0, pix, [&](unsigned i, unsigned img_off) { return dense_request(K, i, img_off); },
                        [&](const DensePix& px, const PlanePos& p, bool active, auto refill) {
@@ -2035,8 +2125,6 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_dense_x(const Align
 // gn_fca_dense's step (dense_form + fcaf_stage_a / _b: the per-pixel values of that kernel), all lanes busy; the rest at the end of
 // the chunk. The queue's order is fixed by ballots: same inputs, same bits. Chunks are split in units of four pixels.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef u32x2_t u32x2_a1 __attribute__((aligned(1)));
 struct QuadPlanes { f32x4_t Z, var; uint32_t I; };
 __device__ __forceinline__ QuadPlanes quad_request(const KfLevelDev& K, unsigned i4, unsigned img_off) {
   QuadPlanes p;
@@ -2076,6 +2164,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
   const Chunk c = m.chunk(fa.age_cum, g.n >> 2, nblk);   // the "list" is the plane, in quads
   const int begin = c.begin, end = c.end;
   g_u8 cur = as_global(F.img);
+  g_u8 cur4 = (g_u8)as_global(F.img4);
   // this thread's first quad: position (quad column, row) and planes, requested before the solve
   const PlaneWalk w = plane_walk(cols4);
   PlanePos p = plane_first(w, c, t);
@@ -2096,8 +2185,9 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
     FcaAcc acc;
     fca_acc_zero(acc);
     if (begin < end) {   // block-uniform
-      const TapRows tr = tap_rows(cur, sw);
-      const g_u8 row_e = tr.rd + sw;   // the fifth row of a window: y0 + 3
+      const TapRows tr = tap_rows(a, cur, cur4, sw);   // (the single-pixel step of the quads the windows do not serve)
+      const RowPtrs rw = row_ptrs(cur, sw);
+      const g_u8 row_e = rw.rd + sw;   // the fifth row of a window: y0 + 3
       // P = K exp(pose) (fcaf_const), in scalar registers
       float P[12];
       {
@@ -2160,10 +2250,10 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, ELLC_QUAD_BLOCKS_PER_CU) void gn_f
                            ((unsigned)(ys - 1) <= (unsigned)(g.rows - 4)) & ((unsigned)(ym - 1) <= (unsigned)(g.rows - 4)) &
                            (xm - xs <= 4) & (ym - ys <= 1);
           const unsigned off = fit ? __umul24((unsigned)ys, (unsigned)sw) + (unsigned)xs : (unsigned)sw + 1u;
-          const u32x2_t wA = *(const ELLC_GLOBAL u32x2_a1*)(tr.ra + off);
-          const u32x2_t wB = *(const ELLC_GLOBAL u32x2_a1*)(tr.rb + off);
-          const u32x2_t wC = *(const ELLC_GLOBAL u32x2_a1*)(tr.rc + off);
-          const u32x2_t wD = *(const ELLC_GLOBAL u32x2_a1*)(tr.rd + off);
+          const u32x2_t wA = *(const ELLC_GLOBAL u32x2_a1*)(rw.ra + off);
+          const u32x2_t wB = *(const ELLC_GLOBAL u32x2_a1*)(rw.rb + off);
+          const u32x2_t wC = *(const ELLC_GLOBAL u32x2_a1*)(rw.rc + off);
+          const u32x2_t wD = *(const ELLC_GLOBAL u32x2_a1*)(rw.rd + off);
           const u32x2_t wE = *(const ELLC_GLOBAL u32x2_a1*)(row_e + off);
           __builtin_amdgcn_sched_barrier(0);
           // the next quad's planes, behind the row requests (vector loads return in issue order)
@@ -2347,8 +2437,9 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, FAST ? 4 : 3) void gn_fca_adaptive
     return;
   }
   g_u8 cur = as_global(L.F->img);
+  g_u8 cur4 = (g_u8)as_global(L.F->img4);
   float sums[27];
-  fca_chunk_pass<DIVC, true, FAST, SAVEW>(a, L.K, L.g, cur, sh.newS, L.c.begin, L.c.end, first.in, first.inf, first.pre, sums);
+  fca_chunk_pass<DIVC, true, FAST, SAVEW>(a, L.K, L.g, cur, cur4, sh.newS, L.c.begin, L.c.end, first.in, first.inf, first.pre, sums);
   block_reduce_store<27>(sums, partial_record(fa, fa.seq, b, sub));
 }
 
@@ -2670,8 +2761,9 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, FAST ? 3 : 2) void gn_fca_persist(
     }
     if (work) {   // block-uniform
       g_u8 cur = as_global(L.F->img);
+      g_u8 cur4 = (g_u8)as_global(L.F->img4);
       float sums[27];
-      fca_chunk_pass<DIVC, true, FAST, SAVEW, true>(a, L.K, L.g, cur, sh.newS, L.c.begin, L.c.end, first.in, first.inf, first.pre, sums);
+      fca_chunk_pass<DIVC, true, FAST, SAVEW, true>(a, L.K, L.g, cur, cur4, sh.newS, L.c.begin, L.c.end, first.in, first.inf, first.pre, sums);
       ELLC_PTRACE(7, 0);
       unsigned* out = (unsigned*)partial_record(fa, seq, b, sub);
       persist_store_record(sums, out, (epoch << 8) | (unsigned)(seq + 1));
@@ -2743,7 +2835,7 @@ __device__ __forceinline__ typename IcaInOf<FAST>::type ica_in_empty() {
 
 template <bool FAST>
 __device__ __forceinline__ void ica_accumulate_pixel(float (&acc)[6], const typename IcaInOf<FAST>::type& in, const LevelGeom& g, g_u8 cur,
-                                                     const float* S) {
+                                                     const float* S, g_u8 cur4 = nullptr, bool row_taps = false) {
   if constexpr (FAST) {
     // the point divided by Z, (p, q, 1) + t d, projects to the same pixel (see fcaf_pixel): fused multiply-adds, hardware reciprocal
     const float p = __builtin_fmaf((float)(in.xyI & 0xfffu), g.rfx, -(g.cx * g.rfx));
@@ -2755,7 +2847,7 @@ __device__ __forceinline__ void ica_accumulate_pixel(float (&acc)[6], const type
     const float rz = __builtin_amdgcn_rcpf(pz);
     const float wx = __builtin_fmaf(px * rz, g.fx, g.cx);
     const float wy = __builtin_fmaf(py * rz, g.fy, g.cy);
-    const Taps t = tap_point<false, true>(cur, g.sw, g.cols, g.rows, wx, wy);
+    const Taps t = tap_point<false, true, NoPrefetch, true>(cur, g.sw, g.cols, g.rows, wx, wy, NoPrefetch(), cur4, row_taps);
     const bool oob = (t.I == -1.0f);
     const float residual = oob ? 0.0f : (t.I - byte_f32<3>(in.xyI));
     const float rw = residual * in.W;
@@ -2796,6 +2888,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS) void gn_ica_fused(const AlignState
   const Chunk c = m.chunk(fa.age_cum, V, a.nblk);
   const int begin = c.begin, end = c.end;
   g_u8 cur = as_global(F.img);
+  g_u8 cur4 = (g_u8)as_global(F.img4);
   typename IcaInOf<FAST>::type first = ica_in_empty<FAST>();
   if (begin + t < end) first = ica_load_any<FAST>(K, (unsigned)(begin + t));
   advance_pose<FAST>(sh, pending, group_sum, 2, fa.prev_level, fa.early_exit, src, &a.kf_tab[fa.prev_level * a.max_kf + slot].hinv);
@@ -2808,8 +2901,8 @@ __global__ __launch_bounds__(ELLC_GN_THREADS) void gn_ica_fused(const AlignState
   for (int i = 0; i < 6; i++) acc[i] = 0.0f;
   int i = begin + t;
   if (i < end) {
-    ica_accumulate_pixel<FAST>(acc, first, g, cur, S);
-    for (i += ELLC_GN_THREADS; i < end; i += ELLC_GN_THREADS) ica_accumulate_pixel<FAST>(acc, ica_load_any<FAST>(K, (unsigned)i), g, cur, S);
+    ica_accumulate_pixel<FAST>(acc, first, g, cur, S, cur4, row_taps_of(a));
+    for (i += ELLC_GN_THREADS; i < end; i += ELLC_GN_THREADS) ica_accumulate_pixel<FAST>(acc, ica_load_any<FAST>(K, (unsigned)i), g, cur, S, cur4, row_taps_of(a));
   }
   block_reduce_store<6>(acc, partial_record(fa, fa.seq, b, sub) + 21);   // the b slots of the partial record; the H slots are not read by a mode-2 solve
 }
@@ -3093,6 +3186,9 @@ struct QualityArgs {
   int* counts;          // [B][nblk][2]: pixels with depth, of which used
   QualityRec* out;      // [B], pinned host memory
   int level, max_kf, max_fr, nblk, max_batch;
+#ifdef ELLC_ROW_TAPS
+  int row_taps;         // LaunchPlan::row_taps
+#endif
 };
 
 // Does the warped point (x1, y1) get no intensity (Taps::I == -1)? tap_general's test: not a number, or all four taps outside.
@@ -3123,6 +3219,7 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_quality(QualityArgs
   const KfLevelDev K = qa.kf_tab[qa.level * qa.max_kf + qa.stage[b]];   // by value: uniform, lives in SGPRs
   const FrLevelDev& F = qa.fr_tab[qa.level * qa.max_fr + qa.stage[qa.max_batch + b]];
   g_u8 cur = as_global(F.img);
+  g_u8 cur4 = (g_u8)as_global(F.img4);
   Chunk c;   // even split of the PLANE
   {
     const int n = (g.n + qa.nblk - 1) / qa.nblk;
@@ -3156,12 +3253,15 @@ __global__ __launch_bounds__(ELLC_GN_THREADS, 4) void gn_fca_quality(QualityArgs
   GnArgs a;   // what the pixel functions read of it: nothing is saved, no planes
   a.geom = qa.geom; a.kf_tab = qa.kf_tab; a.fr_tab = qa.fr_tab; a.kf_slot = nullptr; a.fr_slot = nullptr; a.state = nullptr;
   a.partials = nullptr; a.planes = nullptr; a.level = qa.level; a.max_kf = qa.max_kf; a.max_fr = qa.max_fr; a.nblk = qa.nblk; a.save_w = 0;
+#ifdef ELLC_ROW_TAPS
+  a.row_taps = qa.row_taps;
+#endif
   FcaAcc acc;
   fca_acc_zero(acc);
   float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   int n_depth = 0, n_used = 0;   // wave-uniform: ballots, counted as integers
   if (c.begin < c.end) {   // block-uniform
-    const TapRows tr = tap_rows(cur, sw);
+    const TapRows tr = tap_rows(a, cur, cur4, sw);
     const FcafConst fc = fcaf_const(g, S);
     const int lane = t & 63;
     uint32_t* const q = qbuf[t >> 6];

@@ -42,6 +42,40 @@ __global__ void gradient_planes(const uint8_t* __restrict__ img, int sw, int col
   gy[(size_t)y * cols + x] = b;
 }
 
+// The row-packed plane of a frame slot (FrLevelDev::img4), all levels in one launch: a thread turns four adjacent columns of rows
+// y - 1 .. y + 2 (one dword per row, at any byte) into four words. The tolerance mode's taps read a 4 x 4 neighbourhood as ONE
+// 16-byte load of four such words (tap_request_f). A function of the image alone: written whenever the slot's image planes are.
+struct PackRowsArgs {
+  const uint8_t* img[ELLC_MAX_LEVELS];
+  uint32_t* img4[ELLC_MAX_LEVELS];
+  int sw[ELLC_MAX_LEVELS], rows[ELLC_MAX_LEVELS];   // stored pitch, image rows
+  int begin[ELLC_MAX_LEVELS + 1];   // first thread of each level; a level has ceil(sw / 4) * (stored rows) of them
+  int levels;
+};
+__global__ __launch_bounds__(256) void pack_tap_rows(PackRowsArgs a) {
+  typedef uint32_t u32_a1 __attribute__((aligned(1)));
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.begin[a.levels]) return;
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < ELLC_MAX_LEVELS; k++) if (k < a.levels && t >= a.begin[k]) l = k;
+  const int sw = a.sw[l], rows = a.rows[l], q = (sw + 3) >> 2;
+  const int i = t - a.begin[l], y = i / q, x = (i - y * q) * 4;
+  const ELLC_GLOBAL uint8_t* img = gptr(a.img[l]);
+  uint32_t r[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {   // (a dword at columns x .. x + 3 may reach past the row's end: into the next row, or the slack behind the plane)
+    const int yy = y - 1 + k;
+    r[k] = (yy >= 0 && yy < rows) ? *(const ELLC_GLOBAL u32_a1*)(img + (size_t)yy * sw + x) : 0u;
+  }
+  ELLC_GLOBAL uint32_t* out = gptr_rw(a.img4[l]) + (size_t)y * sw + x;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t w = ((r[0] >> (8 * k)) & 0xffu) | (((r[1] >> (8 * k)) & 0xffu) << 8) | (((r[2] >> (8 * k)) & 0xffu) << 16) | (((r[3] >> (8 * k)) & 0xffu) << 24);
+    if (x + k < sw) out[k] = w;
+  }
+}
+
 // The whole u8 pyramid below one source level in ONE launch (up to three pyrDown steps): a block owns a PT x PT tile of the
 // deepest level it produces and computes, through LDS, everything above it that the tile depends on — the (2PT+3)^2 region of
 // the level above, the (4PT+9)^2 region two above, from the (8PT+21)^2 region of the source — writing the part of each level

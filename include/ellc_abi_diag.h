@@ -84,6 +84,17 @@ ellc_status ellc_debug_set_count_cache(ellc_ctx* ctx, int on);
 /* Groups of this context that compacted with a count launch, and without one because the kept counts were current. (A tracking
  * call's count-free compaction and groups that build no lists are in neither.) Either pointer may be NULL. */
 ellc_status ellc_debug_count_cache_counters(ellc_ctx* ctx, long long* groups_counted, long long* groups_skipped);
+/* Tolerance mode: the interior taps of a warped point come as ONE 16-byte load from the frame slot's row-packed plane (default on).
+ * 0: as four unaligned row loads from the image plane, as up to r07 (kept in this library only) - the same twelve bytes reach the
+ * same arithmetic, so the results must not change by a bit (tests). A plan-time choice: sequences captured under either are kept apart. */
+ellc_status ellc_debug_set_packed_taps(ellc_ctx* ctx, int on);
+/* How many kernel argument records (one per enqueued or captured pixel-pass launch, one per ellc_align_quality_at call) this context
+ * has built with the row loads selected: 0 for a context that never switched the packed taps off, and rising with every kind of call
+ * of one that did - the tests' evidence that the other side of their comparison ran the other path. */
+ellc_status ellc_debug_row_tap_launches(ellc_ctx* ctx, long long* n);
+/* The row-packed plane of a frame slot at `level`: stored_w * stored_h words (ellc_get_image_level's sizes), word (y, x) =
+ * I(y-1,x) | I(y,x) << 8 | I(y+1,x) << 16 | I(y+2,x) << 24 with a zero byte for rows outside [0, rows). Tolerance-mode contexts only. */
+ellc_status ellc_debug_get_packed_level(ellc_ctx* ctx, int frame_slot, int level, uint32_t* out);
 /* Resident launches of this context so far, how many of them the host had to finish with launches (abandoned), and — device-wide,
  * since the library was loaded — how many blocks were lapped and re-joined through the state line. Any pointer may be NULL. */
 ellc_status ellc_debug_persist_counters(ellc_ctx* ctx, long long* resident_launches, long long* abandoned_launches, long long* rejoined_blocks);

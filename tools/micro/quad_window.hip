@@ -16,7 +16,8 @@ typedef u32x3 u32x3a1 __attribute__((aligned(1)));
 typedef u32x2 u32x2a4 __attribute__((aligned(4)));
 typedef u32x3 u32x3a4 __attribute__((aligned(4)));
 typedef u32x4 u32x4a4 __attribute__((aligned(4)));
-enum { P_PIX_DWORD, P_QUAD_X2_U, P_QUAD_X2_U5, P_QUAD_X3_U, P_QUAD_X3_U5, P_QUAD_X2_A, P_QUAD_X3_A, P_QUAD_X3_A5, P_QUAD_X4_A, P_COLPACK_X4, P_PIX_DWORD_JIT, P_QUAD_X3_JIT, P_N };
+enum { P_PIX_DWORD, P_QUAD_X2_U, P_QUAD_X2_U5, P_QUAD_X3_U, P_QUAD_X3_U5, P_QUAD_X2_A, P_QUAD_X3_A, P_QUAD_X3_A5, P_QUAD_X4_A, P_COLPACK_X4, P_PIX_DWORD_JIT, P_QUAD_X3_JIT,
+       P_COLPACK_X4_JIT, P_PIX_DWORD_SCAT, P_COLPACK_X4_SCAT, P_PIX_DWORD_SCAT_JIT, P_COLPACK_X4_SCAT_JIT, P_N };
 template <int PAT>
 __global__ __launch_bounds__(1024) void k(const uint8_t* __restrict__ img, int pitch, int rows, uint32_t* out) {
   const int lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -24,8 +25,28 @@ __global__ __launch_bounds__(1024) void k(const uint8_t* __restrict__ img, int p
   unsigned y = (wave * 7) % (rows - 8) + 2;
   unsigned xb = 3;   // first pixel of the wave's 256
   const unsigned jit = (lane * 2654435761u >> 28) & 1u;   // a per-lane row jitter of 0 / 1 (depth noise moves a point across a row boundary)
+  // r08: the semi-dense wave. A list kernel's 64 lanes hold 64 VALID pixels, which lie among about 256 consecutive pixels of a row
+  // (one in four has depth): lane l sits at 4 l + (0..3), the choice changing from step to step.
+  constexpr bool SCAT = (PAT == P_PIX_DWORD_SCAT || PAT == P_COLPACK_X4_SCAT || PAT == P_PIX_DWORD_SCAT_JIT || PAT == P_COLPACK_X4_SCAT_JIT);
+  constexpr bool SJIT = (PAT == P_PIX_DWORD_SCAT_JIT || PAT == P_COLPACK_X4_SCAT_JIT || PAT == P_COLPACK_X4_JIT);
+  constexpr bool SPACK = (PAT == P_COLPACK_X4_SCAT || PAT == P_COLPACK_X4_SCAT_JIT || PAT == P_COLPACK_X4_JIT);
   for (int it = 0; it < ITER; it++) {
-    if (PAT == P_PIX_DWORD || PAT == P_PIX_DWORD_JIT) {   // the product's taps: lane = pixel, 4 rows of one unaligned dword, 4 wave-steps
+    if (SCAT || PAT == P_COLPACK_X4_JIT) {   // four wave-steps of 64 pixels each, as in the dense patterns: the figure stays "per 256 pixels"
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const unsigned h = ((unsigned)lane * 2654435761u + (unsigned)(it * 4 + q) * 40503u) >> 13;
+        const unsigned x = SCAT ? xb + 256u * q + 4u * lane + (h & 3u) : xb + 64u * q + lane;
+        const unsigned yy = y + (SJIT ? jit : 0u);
+        if (SPACK) {
+          const size_t o = ((size_t)yy * pitch + x) * 4 % ((size_t)pitch * rows * 4);
+          const u32x4 a = *(const u32x4a4*)(img + o);
+          acc ^= a.x ^ a.y ^ a.z ^ a.w;
+        } else {
+          const unsigned o = yy * pitch + x;
+          acc ^= *(const u32a1*)(img + o - 1 - pitch) ^ *(const u32a1*)(img + o - 1) ^ *(const u32a1*)(img + o - 1 + pitch) ^ *(const u32a1*)(img + o - 1 + 2 * pitch);
+        }
+      }
+    } else if (PAT == P_PIX_DWORD || PAT == P_PIX_DWORD_JIT) {   // the product's taps: lane = pixel, 4 rows of one unaligned dword, 4 wave-steps
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         const unsigned o = (y + (PAT == P_PIX_DWORD_JIT ? jit : 0u)) * pitch + xb + 64 * q + lane;
@@ -51,8 +72,9 @@ __global__ __launch_bounds__(1024) void k(const uint8_t* __restrict__ img, int p
         else if (PAT == P_QUAD_X4_A) { const u32x4 a = *(const u32x4a4*)((uintptr_t)p & ~(uintptr_t)3); acc ^= a.x ^ a.y ^ a.z ^ a.w; }
       }
     }
-    xb += 256;
-    if (xb + 256 + 16 >= (unsigned)pitch) { xb = 3; y += 1; if (y >= (unsigned)rows - 6) y = 2; }
+    const unsigned span = SCAT ? 1024u : 256u;
+    xb += span;
+    if (xb + span + 16 >= (unsigned)pitch) { xb = 3; y += 1; if (y >= (unsigned)rows - 6) y = 2; }
   }
   if (acc == 0x12345678u) out[0] = acc;
 }
@@ -94,5 +116,10 @@ int main() {
   run<P_QUAD_X3_A5>("lane = 4 pixels: 5 rows, 12 bytes 4-aligned", img, pitch, rows, out);
   run<P_QUAD_X4_A>("lane = 4 pixels: 4 rows, 16 bytes 4-aligned", img, pitch, rows, out);
   run<P_COLPACK_X4>("lane = pixel: 4 x (one 16-byte load, column-packed image)", img, pitch, rows, out);
+  run<P_COLPACK_X4_JIT>("lane = pixel: 4 x (16-byte column-packed), lanes on two rows at random", img, pitch, rows, out);
+  run<P_PIX_DWORD_SCAT>("semi-dense (64 of 256 px): 4 x (4 rows, unaligned dword)", img, pitch, rows, out);
+  run<P_COLPACK_X4_SCAT>("semi-dense (64 of 256 px): 4 x (16-byte column-packed)", img, pitch, rows, out);
+  run<P_PIX_DWORD_SCAT_JIT>("semi-dense, two rows at random: 4 x (4 rows, unaligned dword)", img, pitch, rows, out);
+  run<P_COLPACK_X4_SCAT_JIT>("semi-dense, two rows at random: 4 x (16-byte column-packed)", img, pitch, rows, out);
   return 0;
 }
