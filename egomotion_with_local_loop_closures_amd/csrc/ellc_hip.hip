@@ -931,7 +931,7 @@ ellc_status ellc_ctx_create(const ellc_config* cfg, ellc_ctx** out) {
   if (cfg->arith != ELLC_ARITH_EXACT && cfg->arith != ELLC_ARITH_FAST) return ELLC_ERR_BAD_ARG;
   if (cfg->width > 4096 || cfg->height > 4096) return ELLC_ERR_BAD_ARG;   // 12-bit x / y in the compact records (FcaRec, FcaRecF)
   if (cfg->levels < 1 || cfg->levels > ELLC_MAX_LEVELS) return ELLC_ERR_BAD_ARG;
-  if ((cfg->width >> (cfg->levels - 1)) < 4 || (cfg->height >> (cfg->levels - 1)) < 4) return ELLC_ERR_BAD_ARG;
+  if ((cfg->width >> (cfg->levels - 1)) < 4 || (cfg->height >> (cfg->levels - 1)) < 4) return ELLC_ERR_BAD_ARG;   // (the packed border taps' 4 x 4 window relies on it, ellc_border_taps.hpp)
   if (cfg->max_keyframes < 1 || cfg->max_frames < 1 || cfg->max_batch < 1) return ELLC_ERR_BAD_ARG;
   if (cfg->coalesce < 0 || cfg->coalesce > ellc_ctx::MAX_COALESCE) return ELLC_ERR_BAD_ARG;   // 0: as 1
   if (cfg->concurrent_batches < 0 || cfg->concurrent_batches > (ellc_ctx::STREAMS + 1) * ellc_ctx::MAX_COALESCE) return ELLC_ERR_BAD_ARG;   // 0: as 1

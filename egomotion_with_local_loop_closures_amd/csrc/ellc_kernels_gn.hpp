@@ -10,6 +10,7 @@
 #pragma once
 #include "ellc_device.hpp"
 #include "ellc_se3.hpp"
+#include "ellc_border_taps.hpp"
 
 namespace ellc {
 
@@ -139,85 +140,79 @@ struct Taps {
   float gx, gy; // gradient taps (Frame.h:283-394) on frame::calculateGradient's planes (Frame.cpp:185-285)
 };
 
-// The general path of the taps: per-tap bounds tests of the reference (Frame.h:211-275). FAST: the gradients are returned twice
-// their value, as the interior branches of that mode return them.
-template <bool WANT_GRAD, bool FAST, bool LAT = false>
-__device__ __forceinline__ Taps tap_general(g_u8 img, int sw, int cols, int rows, float x1, float y1) {
-  Taps o;
-  const float fx0 = floorf(x1), fy0 = floorf(y1);
-  const float wx = x1 - fx0, wy = y1 - fy0;
-  const float omx = 1.0f - wx, omy = 1.0f - wy;
-  if (x1 != x1 || y1 != y1) {  // NaN: reference behaviour undefined; treated as out of bounds
-    o.I = -1.0f; o.gx = 0.0f; o.gy = 0.0f;
-    return o;
-  }
-  const float nC = (float)(cols - 1), nR = (float)(rows - 1);
-  const bool xf_bad = (fx0 < 0.0f) || (fx0 > nC);
-  const bool xc_bad = (x1 < 0.0f) || (x1 > nC);
-  const bool yf_bad = (fy0 < 0.0f) || (fy0 > nR);
-  const bool yc_bad = (y1 < 0.0f) || (y1 > nR);
-  const bool v00 = !(xf_bad || yf_bad), v01 = !(xc_bad || yf_bad), v10 = !(xf_bad || yc_bad), v11 = !(xc_bad || yc_bad);
-  if (!(v00 || v01 || v10 || v11)) {
-    o.I = -1.0f; o.gx = 0.0f; o.gy = 0.0f;   // gradient taps: four zero samples interpolate to 0
-    return o;
-  }
-  const int x0 = (int)fminf(fmaxf(fx0, -4.0f), nC + 4.0f);
-  const int y0 = (int)fminf(fmaxf(fy0, -4.0f), nR + 4.0f);
-  const int xb = clampi(x0, 0, cols - 1), xc = clampi(x0 + 1, 0, cols - 1);
-  const int yb = clampi(y0, 0, rows - 1), yc = clampi(y0 + 1, 0, rows - 1);
-  // uniform base pointer + unsigned 32-bit lane offsets (SGPR-base global loads, no 64-bit lane arithmetic)
-  const unsigned rb = __umul24((unsigned)yb, (unsigned)sw), rc = __umul24((unsigned)yc, (unsigned)sw);   // rows are clamped to >= 0
-  if constexpr (LAT) {
-    // The latency regime (gn_fca_persist: one pixel per thread and round, nothing else in flight): all the samples are requested
-    // TOGETHER, whatever the register allocator would like (the barrier) — in the 168-register resident kernel it had turned the
-    // first four into load, wait, load, wait, and a wave on the image border, i.e. every wave of the two coarse levels (the depth
-    // pyramid's border shrinks with the level), took 0.65 us longer per pixel than an interior one (tools/dbg/persist_trace.py,
-    // r06). The same loads and the same arithmetic as below: the same taps. NOT for the batch pipeline's kernels: with the
-    // barrier their coarse-level launches were 12 % slower (and 4.5 % of a whole step), NOTEBOOK 6.8.
-    const int xa = clampi(x0 - 1, 0, cols - 1), xd = clampi(x0 + 2, 0, cols - 1);
-    const int ya = clampi(y0 - 1, 0, rows - 1), yd = clampi(y0 + 2, 0, rows - 1);
-    const unsigned ra = __umul24((unsigned)ya, (unsigned)sw), rd = __umul24((unsigned)yd, (unsigned)sw);
-    const uint32_t bbb = img[rb + (unsigned)xb], bbc = img[rb + (unsigned)xc], bcb = img[rc + (unsigned)xb], bcc = img[rc + (unsigned)xc];
-    uint32_t bba = 0, bbd = 0, bca = 0, bcd = 0, bab = 0, bac = 0, bdb = 0, bdc = 0;
-    if (WANT_GRAD) {
-      bba = img[rb + (unsigned)xa]; bbd = img[rb + (unsigned)xd];
-      bca = img[rc + (unsigned)xa]; bcd = img[rc + (unsigned)xd];
-      bab = img[ra + (unsigned)xb]; bac = img[ra + (unsigned)xc];
-      bdb = img[rd + (unsigned)xb]; bdc = img[rd + (unsigned)xc];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const float Pbb = (float)bbb, Pbc = (float)bbc, Pcb = (float)bcb, Pcc = (float)bcc;
-    {
-      const float p00 = v00 ? Pbb : 0.0f, p01 = v01 ? Pbc : 0.0f, p10 = v10 ? Pcb : 0.0f, p11 = v11 ? Pcc : 0.0f;
-      const float top = (omx * p00) + (wx * p01);
-      const float btm = (omx * p10) + (wx * p11);
-      o.I = (omy * top) + (wy * btm);
-    }
-    if (WANT_GRAD) {
-      const float Pba = (float)bba, Pbd = (float)bbd, Pca = (float)bca, Pcd = (float)bcd;
-      const float Pab = (float)bab, Pac = (float)bac, Pdb = (float)bdb, Pdc = (float)bdc;
-      const float sx0 = (x0 <= 0 || x0 >= cols - 1) ? 1.0f : 0.5f;
-      const float sx1 = (x0 + 1 <= 0 || x0 + 1 >= cols - 1) ? 1.0f : 0.5f;
-      const float sy0 = (y0 <= 0 || y0 >= rows - 1) ? 1.0f : 0.5f;
-      const float sy1 = (y0 + 1 <= 0 || y0 + 1 >= rows - 1) ? 1.0f : 0.5f;
-      float g00 = sx0 * (Pbc - Pba), g01 = sx1 * (Pbd - Pbb), g10 = sx0 * (Pcc - Pca), g11 = sx1 * (Pcd - Pcb);
-      g00 = v00 ? g00 : 0.0f; g01 = v01 ? g01 : 0.0f; g10 = v10 ? g10 : 0.0f; g11 = v11 ? g11 : 0.0f;
-      float top = (omx * g00) + (wx * g01);
-      float btm = (omx * g10) + (wx * g11);
-      o.gx = (omy * top) + (wy * btm);
-      float h00 = sy0 * (Pcb - Pab), h01 = sy0 * (Pcc - Pac), h10 = sy1 * (Pdb - Pbb), h11 = sy1 * (Pdc - Pbc);
-      h00 = v00 ? h00 : 0.0f; h01 = v01 ? h01 : 0.0f; h10 = v10 ? h10 : 0.0f; h11 = v11 ? h11 : 0.0f;
-      top = (omx * h00) + (wx * h01);
-      btm = (omx * h10) + (wx * h11);
-      o.gy = (omy * top) + (wy * btm);
-      if (FAST) { o.gx *= 2.0f; o.gy *= 2.0f; }
+// The general path of the taps: per-tap bounds tests of the reference (Frame.h:211-275), in two parts: a source of the twelve
+// samples of the 4 x 4 neighbourhood with clamped indices (TapGather: one byte load each; the tolerance mode's border path has them
+// from one packed load, TapWindow at tap_finish_f) and what is made of them (tap_combine, the one copy).
+// P<row><column>, a .. d = y0 - 1 .. y0 + 2 and x0 - 1 .. x0 + 2, each index clamped into the image; x0, y0: the floor of the position,
+// limited to a few positions around the image. A source hands out the four samples of the intensity tap first, then the eight more
+// of the gradient taps.
+template <bool WANT_GRAD, bool LAT>
+struct TapGather {
+  g_u8 img; int sw, cols, rows, x0, y0;
+  uint32_t bba, bbd, bca, bcd, bab, bac, bdb, bdc;   // LAT: requested with the first four
+  __device__ __forceinline__ void first(float& Pbb, float& Pbc, float& Pcb, float& Pcc) {
+    const int xb = clampi(x0, 0, cols - 1), xc = clampi(x0 + 1, 0, cols - 1);
+    const int yb = clampi(y0, 0, rows - 1), yc = clampi(y0 + 1, 0, rows - 1);
+    // uniform base pointer + unsigned 32-bit lane offsets (SGPR-base global loads, no 64-bit lane arithmetic)
+    const unsigned rb = __umul24((unsigned)yb, (unsigned)sw), rc = __umul24((unsigned)yc, (unsigned)sw);   // rows are clamped to >= 0
+    if constexpr (LAT) {
+      // The latency regime (gn_fca_persist: one pixel per thread and round, nothing else in flight; the exact mode's border waves, and
+      // the tolerance mode's through r08, since r09 under the diagnostic library's row loads): all the samples are requested
+      // TOGETHER, whatever the register allocator would like (the barrier) — in the 168-register resident kernel it had turned the
+      // first four into load, wait, load, wait, and a wave on the image border, i.e. every wave of the two coarse levels (the depth
+      // pyramid's border shrinks with the level), took 0.65 us longer per pixel than an interior one (tools/dbg/persist_trace.py,
+      // r06). The same loads and the same arithmetic as otherwise: the same taps. NOT for the batch pipeline's kernels: with the
+      // barrier their coarse-level launches were 12 % slower (and 4.5 % of a whole step), NOTEBOOK 6.8.
+      const int xa = clampi(x0 - 1, 0, cols - 1), xd = clampi(x0 + 2, 0, cols - 1);
+      const int ya = clampi(y0 - 1, 0, rows - 1), yd = clampi(y0 + 2, 0, rows - 1);
+      const unsigned ra = __umul24((unsigned)ya, (unsigned)sw), rd = __umul24((unsigned)yd, (unsigned)sw);
+      const uint32_t bbb = img[rb + (unsigned)xb], bbc = img[rb + (unsigned)xc], bcb = img[rc + (unsigned)xb], bcc = img[rc + (unsigned)xc];
+      bba = 0; bbd = 0; bca = 0; bcd = 0; bab = 0; bac = 0; bdb = 0; bdc = 0;
+      if (WANT_GRAD) {
+        bba = img[rb + (unsigned)xa]; bbd = img[rb + (unsigned)xd];
+        bca = img[rc + (unsigned)xa]; bcd = img[rc + (unsigned)xd];
+        bab = img[ra + (unsigned)xb]; bac = img[ra + (unsigned)xc];
+        bdb = img[rd + (unsigned)xb]; bdc = img[rd + (unsigned)xc];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      Pbb = (float)bbb; Pbc = (float)bbc; Pcb = (float)bcb; Pcc = (float)bcc;
     } else {
-      o.gx = 0.0f; o.gy = 0.0f;
+      Pbb = (float)img[rb + (unsigned)xb]; Pbc = (float)img[rb + (unsigned)xc];
+      Pcb = (float)img[rc + (unsigned)xb]; Pcc = (float)img[rc + (unsigned)xc];
     }
-    return o;
   }
-  const float Pbb = (float)img[rb + (unsigned)xb], Pbc = (float)img[rb + (unsigned)xc];
-  const float Pcb = (float)img[rc + (unsigned)xb], Pcc = (float)img[rc + (unsigned)xc];
+  __device__ __forceinline__ void rest(float& Pba, float& Pbd, float& Pca, float& Pcd, float& Pab, float& Pac, float& Pdb, float& Pdc) {
+    if constexpr (LAT) {
+      Pba = (float)bba; Pbd = (float)bbd; Pca = (float)bca; Pcd = (float)bcd;
+      Pab = (float)bab; Pac = (float)bac; Pdb = (float)bdb; Pdc = (float)bdc;
+    } else {
+      const int xb = clampi(x0, 0, cols - 1), xc = clampi(x0 + 1, 0, cols - 1);
+      const int yb = clampi(y0, 0, rows - 1), yc = clampi(y0 + 1, 0, rows - 1);
+      const unsigned rb = __umul24((unsigned)yb, (unsigned)sw), rc = __umul24((unsigned)yc, (unsigned)sw);
+      const int xa = clampi(x0 - 1, 0, cols - 1), xd = clampi(x0 + 2, 0, cols - 1);
+      const int ya = clampi(y0 - 1, 0, rows - 1), yd = clampi(y0 + 2, 0, rows - 1);
+      const unsigned ra = __umul24((unsigned)ya, (unsigned)sw), rd = __umul24((unsigned)yd, (unsigned)sw);
+      Pba = (float)img[rb + (unsigned)xa]; Pbd = (float)img[rb + (unsigned)xd];
+      Pca = (float)img[rc + (unsigned)xa]; Pcd = (float)img[rc + (unsigned)xd];
+      Pab = (float)img[ra + (unsigned)xb]; Pac = (float)img[ra + (unsigned)xc];
+      Pdb = (float)img[rd + (unsigned)xb]; Pdc = (float)img[rd + (unsigned)xc];
+    }
+  }
+};
+// The taps from the twelve samples of `src`. FAST: the gradients are returned twice their value, as the interior branches of that
+// mode return them. GUARD: a position that is not a number, or has none of its four taps in bounds, gets I = -1 and no gradient by
+// selects at the end (tap_general has returned for those before it fetches; the packed border path fetches for every lane).
+struct TapWeights {
+  float wx, wy, omx, omy;
+  bool v00, v01, v10, v11;   // the four taps' validities
+};
+template <bool WANT_GRAD, bool FAST, bool GUARD, class Source>
+__device__ __forceinline__ Taps tap_combine(Source& src, const TapWeights& w, int cols, int rows, float x1, float y1, int x0, int y0) {
+  Taps o;
+  const float wx = w.wx, wy = w.wy, omx = w.omx, omy = w.omy;
+  const bool v00 = w.v00, v01 = w.v01, v10 = w.v10, v11 = w.v11;
+  float Pbb, Pbc, Pcb, Pcc;
+  src.first(Pbb, Pbc, Pcb, Pcc);
   {
     const float p00 = v00 ? Pbb : 0.0f, p01 = v01 ? Pbc : 0.0f, p10 = v10 ? Pcb : 0.0f, p11 = v11 ? Pcc : 0.0f;
     const float top = (omx * p00) + (wx * p01);
@@ -225,13 +220,8 @@ __device__ __forceinline__ Taps tap_general(g_u8 img, int sw, int cols, int rows
     o.I = (omy * top) + (wy * btm);
   }
   if (WANT_GRAD) {
-    const int xa = clampi(x0 - 1, 0, cols - 1), xd = clampi(x0 + 2, 0, cols - 1);
-    const int ya = clampi(y0 - 1, 0, rows - 1), yd = clampi(y0 + 2, 0, rows - 1);
-    const unsigned ra = __umul24((unsigned)ya, (unsigned)sw), rd = __umul24((unsigned)yd, (unsigned)sw);
-    const float Pba = (float)img[rb + (unsigned)xa], Pbd = (float)img[rb + (unsigned)xd];
-    const float Pca = (float)img[rc + (unsigned)xa], Pcd = (float)img[rc + (unsigned)xd];
-    const float Pab = (float)img[ra + (unsigned)xb], Pac = (float)img[ra + (unsigned)xc];
-    const float Pdb = (float)img[rd + (unsigned)xb], Pdc = (float)img[rd + (unsigned)xc];
+    float Pba, Pbd, Pca, Pcd, Pab, Pac, Pdb, Pdc;
+    src.rest(Pba, Pbd, Pca, Pcd, Pab, Pac, Pdb, Pdc);
     // scale 1 on the border column/row of the tap itself, 0.5 inside
     const float sx0 = (x0 <= 0 || x0 >= cols - 1) ? 1.0f : 0.5f;
     const float sx1 = (x0 + 1 <= 0 || x0 + 1 >= cols - 1) ? 1.0f : 0.5f;
@@ -253,7 +243,39 @@ __device__ __forceinline__ Taps tap_general(g_u8 img, int sw, int cols, int rows
   } else {
     o.gx = 0.0f; o.gy = 0.0f;
   }
+  if (GUARD) {
+    const bool none = (x1 != x1) || (y1 != y1) || !(v00 || v01 || v10 || v11);
+    o.I = none ? -1.0f : o.I; o.gx = none ? 0.0f : o.gx; o.gy = none ? 0.0f : o.gy;
+  }
   return o;
+}
+template <bool WANT_GRAD, bool FAST, bool LAT = false>
+__device__ __forceinline__ Taps tap_general(g_u8 img, int sw, int cols, int rows, float x1, float y1) {
+  Taps o;
+  TapWeights w;
+  const float fx0 = floorf(x1), fy0 = floorf(y1);
+  w.wx = x1 - fx0; w.wy = y1 - fy0;
+  w.omx = 1.0f - w.wx; w.omy = 1.0f - w.wy;
+  if (x1 != x1 || y1 != y1) {  // NaN: reference behaviour undefined; treated as out of bounds
+    o.I = -1.0f; o.gx = 0.0f; o.gy = 0.0f;
+    return o;
+  }
+  const float nC = (float)(cols - 1), nR = (float)(rows - 1);
+  const bool xf_bad = (fx0 < 0.0f) || (fx0 > nC);
+  const bool xc_bad = (x1 < 0.0f) || (x1 > nC);
+  const bool yf_bad = (fy0 < 0.0f) || (fy0 > nR);
+  const bool yc_bad = (y1 < 0.0f) || (y1 > nR);
+  const bool v00 = !(xf_bad || yf_bad), v01 = !(xc_bad || yf_bad), v10 = !(xf_bad || yc_bad), v11 = !(xc_bad || yc_bad);
+  if (!(v00 || v01 || v10 || v11)) {
+    o.I = -1.0f; o.gx = 0.0f; o.gy = 0.0f;   // gradient taps: four zero samples interpolate to 0
+    return o;
+  }
+  w.v00 = v00; w.v01 = v01; w.v10 = v10; w.v11 = v11;
+  const int x0 = (int)fminf(fmaxf(fx0, -4.0f), nC + 4.0f);
+  const int y0 = (int)fminf(fmaxf(fy0, -4.0f), nR + 4.0f);
+  TapGather<WANT_GRAD, LAT> src;
+  src.img = img; src.sw = sw; src.cols = cols; src.rows = rows; src.x0 = x0; src.y0 = y0;
+  return tap_combine<WANT_GRAD, FAST, false>(src, w, cols, rows, x1, y1, x0, y0);
 }
 
 // The three bilinear taps of one warped point. The gradient planes are never materialised: the four
@@ -264,19 +286,27 @@ __device__ __forceinline__ Taps tap_general(g_u8 img, int sw, int cols, int rows
 // that remains is the same expression, so the results are bit-identical to the general path.
 // FAST (cfg.arith = ELLC_ARITH_FAST): the interior path interpolates in the fused form a + w (b - a) and applies the 0.5 of
 // the central differences once to the interpolated gradient: same values to within a few ulp, 19 instructions fewer.
-// after_issue() is called exactly once, on the interior path right after the tap loads have been issued: the pixel loops
-// request the next pixel's record there. Vector loads return in order, so a record load issued BEFORE the taps would have
+// after_issue() is called exactly once: on the interior path right after the tap loads have been issued (in the tolerance mode's
+// tap_request_f, r09, also behind a border wave's one load at the clamped origin), else in front of the per-tap gathers. The pixel
+// loops request the next pixel's record there. Vector loads return in order, so a record load issued BEFORE the taps would have
 // to come back from HBM before the (cache-resident) taps count as complete; issued behind them it stays in flight while
 // this pixel's arithmetic runs.
 struct NoPrefetch { __device__ __forceinline__ void operator()() const {} };
-// A prefetch functor that also says "latency regime" (tap_general<.., LAT>): how gn_fca_persist's passes mark their taps
+// A prefetch functor that also says "latency regime" (tap_general<.., LAT>): how gn_fca_persist's passes mark their taps. It orders
+// the per-tap gathers only: tap_point's border path, and since r09 for the tolerance mode's tap_finish_f nothing in a shipping build
+// (a border wave has one packed load, with nothing to order; the gathers are its border path under the diagnostic library's row loads)
 template <class F> struct LatPF { F f; __device__ __forceinline__ void operator()() const { f(); } };
 template <class T> struct is_lat_pf { static constexpr bool value = false; };
 template <class F> struct is_lat_pf<LatPF<F>> { static constexpr bool value = true; };
 template <class F> __device__ __forceinline__ LatPF<F> lat_pf(F f) { return LatPF<F>{f}; }
+struct TapPair {   // the four samples of the intensity tap, already fetched (tap_point's packed border path)
+  float Pbb, Pbc, Pcb, Pcc;
+  __device__ __forceinline__ void first(float& bb, float& bc, float& cb, float& cc) { bb = Pbb; bc = Pbc; cb = Pcb; cc = Pcc; }
+  __device__ __forceinline__ void rest(float&, float&, float&, float&, float&, float&, float&, float&) {}
+};
 // PACKED (tolerance mode without gradients, the constant-weight path; r08): columns x0 and x0 + 1 come as ONE 8-byte load from the
 // frame's row-packed plane img4 (FrLevelDev::img4), rows y0 and y0 + 1 in bytes 1 and 2 of each word; row_taps (diagnostic library
-// only, block-uniform): the two row loads all the same.
+// only, block-uniform): the two row loads all the same. r09: a border wave's four samples are one 8-byte load of that plane as well.
 template <bool WANT_GRAD, bool FAST = false, class AfterIssue = NoPrefetch, bool PACKED = false>
 __device__ __forceinline__ Taps tap_point(g_u8 img, int sw, int cols, int rows, float x1, float y1, AfterIssue after_issue = AfterIssue(),
                                           g_u8 img4 = nullptr, bool row_taps = false) {
@@ -346,6 +376,33 @@ __device__ __forceinline__ Taps tap_point(g_u8 img, int sw, int cols, int rows, 
     }
     return o;
   }
+  if constexpr (PACKED) {
+    if (!row_taps) {
+      // r09: a wave with a lane on the border asks for ONE 8-byte load too, the two words at the clamped origin (ellc_border_taps.hpp,
+      // pair_*). The four bytes tap_general gathers, into its own combine; a lane it returns early for loads from its clamped
+      // address all the same.
+      const float nC = (float)(cols - 1), nR = (float)(rows - 1);
+      const int x0 = (int)fminf(fmaxf(fx0, -4.0f), nC + 4.0f), y0 = (int)fminf(fmaxf(fy0, -4.0f), nR + 4.0f);   // (a NaN gives -4)
+      const int xw = pair_origin_col(x0, cols), yw = pair_origin_row(y0, rows);
+      const u32x2_t v = *(const ELLC_GLOBAL u32x2_a4*)(img4 + ((__umul24((unsigned)yw, (unsigned)sw) + (unsigned)xw) << 2));
+      __builtin_amdgcn_sched_barrier(0);
+      after_issue();
+      __builtin_amdgcn_sched_barrier(0);
+      const uint32_t wl = pair_pick_left(v.x, v.y, x0, cols), wr = pair_pick_right(v.x, v.y, x0);
+      const bool two = pair_two_rows(y0, rows);
+      TapPair src;
+      src.Pbb = byte_f32<1>(wl); src.Pbc = byte_f32<1>(wr);
+      src.Pcb = two ? byte_f32<2>(wl) : src.Pbb; src.Pcc = two ? byte_f32<2>(wr) : src.Pbc;
+      TapWeights w;
+      w.wx = wx; w.wy = wy; w.omx = omx; w.omy = omy;
+      const bool xf_bad = (fx0 < 0.0f) || (fx0 > nC);
+      const bool xc_bad = (x1 < 0.0f) || (x1 > nC);
+      const bool yf_bad = (fy0 < 0.0f) || (fy0 > nR);
+      const bool yc_bad = (y1 < 0.0f) || (y1 > nR);
+      w.v00 = !(xf_bad || yf_bad); w.v01 = !(xc_bad || yf_bad); w.v10 = !(xf_bad || yc_bad); w.v11 = !(xc_bad || yc_bad);
+      return tap_combine<false, FAST, true>(src, w, cols, rows, x1, y1, x0, y0);
+    }
+  }
   after_issue();
   return tap_general<WANT_GRAD, FAST, is_lat_pf<AfterIssue>::value>(img, sw, cols, rows, x1, y1);
 }
@@ -403,6 +460,17 @@ __device__ __forceinline__ TapRows tap_rows(const GnArgs& a, g_u8 img, g_u8 img4
 #endif
   return r;
 }
+// Does a wave that is not interior take the packed load at the clamped origin (r09)? Always, but for the diagnostic library's row
+// loads (block-uniform), which keep the per-tap gathers as their border path: the independent second source of the packed one.
+// The window needs a level of at least 4 x 4; a context has no smaller one (ellc_ctx_create refuses width or height >> (levels - 1)
+// under 4), so there is no other border path in the shipping kernels.
+__device__ __forceinline__ bool border_packed(const TapRows& tr) {
+#ifdef ELLC_ROW_TAPS
+  return !tr.rows;
+#else
+  return true;
+#endif
+}
 template <int N>
 __device__ __forceinline__ float cvt_ubyte(uint32_t w) {   // opaque to the optimiser on purpose, see above
   float f;
@@ -417,12 +485,13 @@ __device__ __forceinline__ int cvt_floor_i32(float x) {   // floor, then the sat
   asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(i) : "v"(x));
   return i;
 }
-// Two halves: tap_request_f decides interior / general for the wave and requests the four rows; tap_finish_f turns them (or, on the
-// general path, the synchronous per-tap loads) into the taps. (r04 put the next pixel's request in front of the current pixel's
+// Two halves: tap_request_f decides interior / border for the wave and requests the four words (r09: a border wave's at the clamped
+// origin); tap_finish_f turns them (or, under the diagnostic library's row loads, the synchronous per-tap loads of a border wave) into the taps. (r04 put the next pixel's request in front of the current pixel's
 // finish — a software pipeline over pixels: 1280x960 dense 387 against 389 us, 640x480 5 % slower, 125 registers: not kept.)
 struct TapReq {
   uint32_t wa, wb, wc, wd;   // columns x0 - 1 .. x0 + 2, each rows y0 - 1 .. y0 + 2 (valid when interior); `rows`: the transpose
   bool interior;             // wave-uniform: every lane that was active at the request samples the interior
+  bool clamped;              // wave-uniform, not interior: the words are the window at the CLAMPED origin (ellc_border_taps.hpp)
 #ifdef ELLC_ROW_TAPS
   bool rows;
 #endif
@@ -436,6 +505,7 @@ __device__ __forceinline__ TapReq tap_request_f(const TapRows& tr, int sw, int c
   // NaN coordinate converts to 0 and an infinite one saturates: neither is interior
   const bool interior = ((unsigned)(x0 - 1) <= (unsigned)(cols - 4)) & ((unsigned)(y0 - 1) <= (unsigned)(rows - 4));
   q.interior = (__builtin_amdgcn_ballot_w64(!interior) == 0ull);
+  q.clamped = false;
   // (r04 measured the straight-line form — the rows requested unconditionally, a lane that is not interior asking for the image's
   // first bytes — which a software pipeline over pixels needs: 5 % slower on the batch pipeline, the coarse levels' waves on the
   // image border pay for four requests they do not use)
@@ -443,8 +513,22 @@ __device__ __forceinline__ TapReq tap_request_f(const TapRows& tr, int sw, int c
 #ifdef ELLC_ROW_TAPS
   q.rows = tr.rows;
 #endif
-  if (q.interior) {
-    const unsigned off = __umul24((unsigned)y0, (unsigned)sw) + (unsigned)x0;
+  // r09: a wave with a lane on the border asks for ONE packed load too, the window at the CLAMPED origin: it holds every sample of
+  // the clamped 4 x 4 neighbourhood that TapGather fetches byte by byte (tap_finish_f puts them in their places). A lane without a
+  // tap in bounds (or with a NaN, which converts to 0) loads from its clamped, valid address like any other. One load site for both.
+  int xo = x0, yo = y0;
+  bool window = q.interior;
+  if (!q.interior && border_packed(tr)) {
+    xo = border_origin(x0, cols); yo = border_origin(y0, rows);
+    window = true;
+#ifdef ELLC_X_BORDERCEIL   // variant builds only (WRONG values on the border): the interior arithmetic on the clamped window, the
+    q.interior = true;     // most any border path can give
+#else
+    q.clamped = true;
+#endif
+  }
+  if (window) {
+    const unsigned off = __umul24((unsigned)yo, (unsigned)sw) + (unsigned)xo;
 #ifdef ELLC_X_LDSTAPS   // variant builds only (tools/pmc_ldstaps.sh; WRONG values, and since r08 the words are in ROW layout while tap_finish_f
                         // decodes the packed, transposed one: a cost model only): what the four rows would cost as reads of an LDS
                         // window that is already there — two aligned dwords + v_alignbit per row, no staging, no window arithmetic
@@ -455,7 +539,7 @@ __device__ __forceinline__ TapReq tap_request_f(const TapRows& tr, int sw, int c
     if (WANT_GRAD) { q.wa = __builtin_amdgcn_alignbit(xl[2048 + o + 1], xl[2048 + o], shb); q.wd = __builtin_amdgcn_alignbit(xl[3072 + o + 1], xl[3072 + o], shb); }
 #else
 #ifdef ELLC_ROW_TAPS
-    if (tr.rows) {
+    if (tr.rows) {   // (interior waves only: border_packed)
       q.wb = load_u32_unaligned(tr.rb, off);
       q.wc = load_u32_unaligned(tr.rc, off);
       if (WANT_GRAD) { q.wa = load_u32_unaligned(tr.ra, off); q.wd = load_u32_unaligned(tr.rd, off); }
@@ -478,6 +562,17 @@ __device__ __forceinline__ TapReq tap_request_f(const TapRows& tr, int sw, int c
   }
   return q;
 }
+// The twelve samples from four words in the interior path's places: word = column x0 - 1 .. x0 + 2, byte = row y0 - 1 .. y0 + 2
+struct TapWindow {
+  uint32_t ca, cb, cc, cd;
+  __device__ __forceinline__ void first(float& Pbb, float& Pbc, float& Pcb, float& Pcc) {
+    Pbb = cvt_ubyte<1>(cb); Pbc = cvt_ubyte<1>(cc); Pcb = cvt_ubyte<2>(cb); Pcc = cvt_ubyte<2>(cc);
+  }
+  __device__ __forceinline__ void rest(float& Pba, float& Pbd, float& Pca, float& Pcd, float& Pab, float& Pac, float& Pdb, float& Pdc) {
+    Pba = cvt_ubyte<1>(ca); Pbd = cvt_ubyte<1>(cd); Pca = cvt_ubyte<2>(ca); Pcd = cvt_ubyte<2>(cd);
+    Pab = cvt_ubyte<0>(cb); Pac = cvt_ubyte<0>(cc); Pdb = cvt_ubyte<3>(cb); Pdc = cvt_ubyte<3>(cc);
+  }
+};
 template <bool WANT_GRAD, bool LAT = false>
 __device__ __forceinline__ Taps tap_finish_f(const TapReq& q, g_u8 img, int sw, int cols, int rows, float x1, float y1) {
   if (q.interior) {
@@ -513,7 +608,37 @@ __device__ __forceinline__ Taps tap_finish_f(const TapReq& q, g_u8 img, int sw, 
     }
     return o;
   }
-  return tap_general<WANT_GRAD, true, LAT>(img, sw, cols, rows, x1, y1);
+  if (q.clamped) {
+    // The four words hold columns xw - 1 .. xw + 2 of rows yw - 1 .. yw + 2. Per lane: the word of each clamped column, then its
+    // clamped rows y0 - 1 .. y0 + 2 into bytes 0 .. 3 (one selector, v_perm_b32); from there the interior path's twelve conversions
+    // and tap_general's own combine. The samples and the arithmetic of the per-tap gathers: the same bits.
+    const int x0 = border_limit(cvt_floor_i32(x1), cols), y0 = border_limit(cvt_floor_i32(y1), rows);
+    const int dx = x0 - border_origin(x0, cols), dy = y0 - border_origin(y0, rows);
+    const uint32_t rsel = border_select(dy);
+    const uint32_t ca = border_pick_rows(border_pick_column<-1>(q.wa, q.wb, q.wc, q.wd, dx), rsel);
+    const uint32_t cb = border_pick_rows(border_pick_column<0>(q.wa, q.wb, q.wc, q.wd, dx), rsel);
+    const uint32_t cc = border_pick_rows(border_pick_column<1>(q.wa, q.wb, q.wc, q.wd, dx), rsel);
+    const uint32_t cd = border_pick_rows(border_pick_column<2>(q.wa, q.wb, q.wc, q.wd, dx), rsel);
+    TapWindow src;
+    src.ca = ca; src.cb = cb; src.cc = cc; src.cd = cd;
+    // the weights and validities as tap_general has them (x - floor(x), not v_fract_f32: they differ below zero)
+    TapWeights w;
+    const float fx0 = floorf(x1), fy0 = floorf(y1);
+    w.wx = x1 - fx0; w.wy = y1 - fy0;
+    w.omx = 1.0f - w.wx; w.omy = 1.0f - w.wy;
+    const float nC = (float)(cols - 1), nR = (float)(rows - 1);
+    const bool xf_bad = (fx0 < 0.0f) || (fx0 > nC);
+    const bool xc_bad = (x1 < 0.0f) || (x1 > nC);
+    const bool yf_bad = (fy0 < 0.0f) || (fy0 > nR);
+    const bool yc_bad = (y1 < 0.0f) || (y1 > nR);
+    w.v00 = !(xf_bad || yf_bad); w.v01 = !(xc_bad || yf_bad); w.v10 = !(xf_bad || yc_bad); w.v11 = !(xc_bad || yc_bad);
+    return tap_combine<WANT_GRAD, true, true>(src, w, cols, rows, x1, y1, x0, y0);
+  }
+#ifdef ELLC_ROW_TAPS
+  return tap_general<WANT_GRAD, true, LAT>(img, sw, cols, rows, x1, y1);   // (the row loads' border path)
+#else
+  __builtin_unreachable();   // interior or clamped: border_packed
+#endif
 }
 
 // a / b for a per-level constant b with rb = RN(1/b): q = RN(a rb), e = a - b q (exact, fma), RN(q + e rb).
@@ -1829,7 +1954,7 @@ __device__ __forceinline__ PlanePos plane_next(const PlaneWalk& w, const PlanePo
 // The pixel pass of one block of a fused launch over its chunk [begin, end) of the compact list, thread t taking the
 // entries begin + t, begin + t + 256, ...; the thread's first record (and, in the exact mode, its pose-independent products)
 // was requested by the caller before the solve. newS: exp(pose) of this iteration (LDS). Leaves the thread's 27 sums.
-template <bool DIVC, bool PIPE, bool FAST, int SAVEW, bool LAT = false>   // LAT: the latency regime (tap_general)
+template <bool DIVC, bool PIPE, bool FAST, int SAVEW, bool LAT = false>   // LAT: the latency regime (TapGather: the exact mode's border taps; the tolerance mode's since r09 under the diagnostic library's row loads only)
 __device__ __forceinline__ void fca_chunk_pass(const GnArgs& a, const KfLevelDev& K, const LevelGeom& g, g_u8 cur, g_u8 cur4, const float* newS, int begin,
                                                int end, const FcaIn& first, const FcaInF& firstf, const FcaPre& first_pre, float (&sums)[27]) {
   constexpr int stride = ELLC_GN_THREADS;
