@@ -634,6 +634,31 @@ def F_arr(a):
     return np.asarray(a, np.float32)
 
 
+def inv_var_depth_level(dsrc, vsrc, width, height):
+    """One level of depthMap::buildInvVarDepth (DepthPropagation.cpp:1637-1719): the (height, width) level from the finer level's depth
+    and variance arrays, read flat with the stride 2 * width. Returns (depth, variance, number of valid children per cell); a cell
+    without a valid child gets depth 0, variance -1. Shared by DepthMapStages.build_inv_var_depth and tests/image_reference.py."""
+    sw = 2 * width
+    vsrc = np.asarray(vsrc, np.float32).ravel()
+    dsrc = np.asarray(dsrc, np.float32).ravel()
+    yy, xx = np.meshgrid(np.arange(height), np.arange(width), indexing="ij")
+    idx = 2 * (xx + yy * sw)
+    ivs = np.zeros((height, width), np.float32)
+    ids = np.zeros((height, width), np.float32)
+    num = np.zeros((height, width), np.int32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for off in (0, 1, sw, sw + 1):
+            var = vsrc[idx + off]
+            take = var > 0
+            ivar = F(1.0) / var
+            ivs = _add_if(take, ivs, ivar)
+            ids = _add_if(take, ids, (ivar * F(1.0)) / dsrc[idx + off])    # `ivar * 1.0f/depthSource[..]`: (ivar * 1) / depth
+            num += take.astype(np.int32)
+        depth = ivs / ids
+        vdest = num.astype(np.float32) / ivs                              # int / float
+    return (np.where(num > 0, depth, F(0.0)).astype(np.float32), np.where(num > 0, vdest, F(-1.0)).astype(np.float32), num)
+
+
 class DepthMapStages(DepthSecondSource):
     """DepthSecondSource plus the stencil, rescale and export stages. Extra state, as in depthMap (DepthPropagation.h:47-78):
     validityIntegralBuffer (zeroed by the constructor :26-28 and never cleared again: the rows buildValIntegralBuffer does not write
@@ -835,28 +860,8 @@ class DepthMapStages(DepthSecondSource):
     def build_inv_var_depth(self):
         cells = {}
         for i in range(1, self.levels):
-            width = self.W >> i
-            height = self.H >> i
-            sw = 2 * width
-            vsrc = self.depthvararr[i - 1].ravel()
-            dsrc = self.deptharr[i - 1].ravel()
-            yy, xx = np.meshgrid(np.arange(height), np.arange(width), indexing="ij")
-            idx = 2 * (xx + yy * sw)
-            ivs = np.zeros((height, width), np.float32)
-            ids = np.zeros((height, width), np.float32)
-            num = np.zeros((height, width), np.int32)
-            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-                for off in (0, 1, sw, sw + 1):
-                    var = vsrc[idx + off]
-                    take = var > 0
-                    ivar = F(1.0) / var
-                    ivs = _add_if(take, ivs, ivar)
-                    ids = _add_if(take, ids, (ivar * F(1.0)) / dsrc[idx + off])    # `ivar * 1.0f/depthSource[..]`: (ivar * 1) / depth
-                    num += take.astype(np.int32)
-                depth = ivs / ids
-                vdest = num.astype(np.float32) / ivs                              # int / float
-            self.deptharr[i] = np.where(num > 0, depth, F(0.0)).astype(np.float32)
-            self.depthvararr[i] = np.where(num > 0, vdest, F(-1.0)).astype(np.float32)
+            self.deptharr[i], self.depthvararr[i], num = inv_var_depth_level(self.deptharr[i - 1], self.depthvararr[i - 1],
+                                                                             self.W >> i, self.H >> i)
             cells[i] = np.bincount(num.ravel(), minlength=5)
         self.export_classes["children"] = cells
         self.export_classes["odd_source_width"] = [i for i in range(1, self.levels) if (self.W >> (i - 1)) & 1]
