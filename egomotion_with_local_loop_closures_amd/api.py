@@ -2,12 +2,14 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
 ARITH_EXACT = 0
 ARITH_FAST = 1
+ERR_CAPACITY = -5
+MAP_POINT_DTYPE = np.dtype(EllcMapPoint)   # x y z var (f32), px py (u16), intensity support (u8), source (u16): 24 bytes
 HYP_FIELDS = ("invDepth", "invDepthSmoothed", "variance", "varianceSmoothed", "validity", "blacklisted", "valid")
 
 
@@ -326,6 +328,31 @@ class Context:
     def copy_slot(self, dst_is_kf, dst, src_is_kf, src):
         self._ck(self._l.ellc_copy_slot(self.h, int(dst_is_kf), dst, int(src_is_kf), src), "ellc_copy_slot")
 
+    # ---- the map as points
+    def map_points_raw(self, kf_slots, T12, out, capacity, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1):
+        """ellc_keyframe_map_points with the caller's buffer: `out` is None (the sizing call) or a writable array of at least
+        capacity * 24 bytes. Returns (status, counts, total) — the status is NOT raised, so that ELLC_ERR_CAPACITY can be looked at."""
+        kf = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        B = kf.size
+        T = np.ascontiguousarray(T12, np.float32).reshape(B, 12)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        counts = np.zeros(B, np.int32)
+        total = C.c_int(0)
+        st = self._l.ellc_keyframe_map_points(self.h, B, _p(kf), _p(T), int(level), C.byref(flt), _p(out), int(capacity), _p(counts), C.byref(total))
+        return st, counts, total.value
+
+    def map_points(self, kf_slots, T12, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1):
+        """The keyframe slots' semi-dense maps on `level` as filtered 3-D points (ellc_keyframe_map_points): T12[b] is the row-major
+        3x4 transform of request b. Returns (points, counts): a structured array of MAP_POINT_DTYPE in request-major raster order and
+        the points per request."""
+        kw = dict(level=level, max_var=max_var, min_support=min_support, support_k2=support_k2, stride=stride)
+        st, counts, total = self.map_points_raw(kf_slots, T12, None, 0, **kw)
+        self._ck(st, "ellc_keyframe_map_points")
+        pts = np.zeros(total, MAP_POINT_DTYPE)
+        st, counts, total = self.map_points_raw(kf_slots, T12, pts, total, **kw)
+        self._ck(st, "ellc_keyframe_map_points")
+        return pts, counts
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -429,6 +456,21 @@ class Context:
         out = np.zeros((tri21.shape[0], 6, 6), np.float32)
         self._ck(self._l.ellc_selftest_lu(self.h, int(tri21.shape[0]), _p(tri21), _p(out)), "ellc_selftest_lu")
         return out
+
+    def profile_map_points(self, kf_slots, T12, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1):
+        """map_points through ellc_profile_map_points: (points, counts, device ms of the three launches)."""
+        self._need_diag("ellc_profile_map_points")
+        kf = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        B = kf.size
+        T = np.ascontiguousarray(T12, np.float32).reshape(B, 12)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        counts = np.zeros(B, np.int32); total = C.c_int(0); ms = C.c_float(0)
+        self._ck(self._l.ellc_profile_map_points(self.h, B, _p(kf), _p(T), int(level), C.byref(flt), None, 0, _p(counts), C.byref(total), C.byref(ms)),
+                 "ellc_profile_map_points")
+        pts = np.zeros(total.value, MAP_POINT_DTYPE)
+        self._ck(self._l.ellc_profile_map_points(self.h, B, _p(kf), _p(T), int(level), C.byref(flt), _p(pts), total.value, _p(counts), C.byref(total),
+                                                 C.byref(ms)), "ellc_profile_map_points")
+        return pts, counts, ms.value
 
     def profile_calibrate_read(self, nbytes, reps=10):
         self._need_diag("ellc_profile_calibrate_read")

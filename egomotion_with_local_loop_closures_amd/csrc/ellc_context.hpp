@@ -223,6 +223,14 @@ struct ellc_ctx {
   float* quality_partials_d = nullptr;                          // [max_batch][blocks of level 0][ELLC_PART_STRIDE]
   int* quality_counts_d = nullptr;                              // [max_batch][blocks of level 0][2]
   ellc_align_quality *quality_out_h = nullptr, *quality_out_dev_alias = nullptr;   // pinned: the finish kernel writes the records
+  // ellc_keyframe_map_points: scratch of its own, allocated by the first call
+  int* map_stage_h = nullptr;               // pinned: [max_keyframes] slot of every request, [max_keyframes][12] f32 transforms
+  int* map_stage_d = nullptr;               //   and its device copy
+  int* map_tile_counts_d = nullptr;         // [max_keyframes][tiles of level 0] kept pixels per tile
+  unsigned* map_tile_offsets_d = nullptr;   // [max_keyframes][tiles of level 0] records in front of each tile
+  int *map_totals_h = nullptr, *map_totals_dev_alias = nullptr;   // pinned: [max_keyframes] points per request, then their sum (map_scan writes them)
+  void* map_out_d = nullptr;                // device staging of the records: an allocation of its own that grows with the largest call
+  size_t map_out_cap = 0;                   //   records it holds
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

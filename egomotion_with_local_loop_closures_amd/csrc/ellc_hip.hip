@@ -1208,6 +1208,7 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
     if (c->upload_stage[k]) (void)hipHostFree(c->upload_stage[k]);
     if (c->upload_done[k]) (void)hipEventDestroy(c->upload_done[k]);
   }
+  if (c->map_out_d) (void)hipFree(c->map_out_d);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
   if (c->ingest_bgr) (void)hipFree(c->ingest_bgr);
   for (int p = 0; p < ellc_ctx::SETS; p++)
@@ -2705,3 +2706,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 
 #include "ellc_depth_impl.hpp"
 #include "ellc_ingest_impl.hpp"
+#include "ellc_map_impl.hpp"

@@ -23,6 +23,9 @@
 // --match-quality PATH  (LC mode) one line per line of matchframes_globalopt.txt: "frameId kfId n_depth n_used rms wrms" — how well the
 //                    candidate fits at the pose the batch returned (ellc_align_quality_at, level 0); every other file is unchanged.
 //                    Single process only: refused with --world > 1 (the gather record stays 8 floats)
+// --map FILE         (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
+//                    level 0, no variance test, at least 3 supporting neighbours, support_k2 1, every pixel), written as binary PLY
+//                    (x y z float, intensity uchar, var float); every other file is unchanged
 // Input is otherwise a header-less file of W*H u8 grey frames (the decode itself always stays outside).
 // In LC mode finished keyframes go through the loop-closure ring (facade class globalOptimize): matching and the batched
 // alignment of a pushed keyframe run on a second thread and a second context beside tracking, joined at the next push
@@ -39,7 +42,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--map FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -49,7 +52,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality;
+  std::string comm_id_file, match_quality, map_file;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -66,6 +69,7 @@ int main(int argc, char** argv) {
     else if (a == "--comm-id" && i + 1 < argc) comm_id_file = argv[++i];
     else if (a == "--comm-tcp" && i + 1 < argc) comm_port = std::atoi(argv[++i]);
     else if (a == "--match-quality" && i + 1 < argc) match_quality = argv[++i];
+    else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return -1; }
   }
@@ -194,6 +198,13 @@ int main(int argc, char** argv) {
       }
     }
     if (globalOptimizeLoop) globalOptimizeLoop->join_all();   // the last keyframe's match thread (t_group.join_all)
+    if (globalOptimizeLoop && !map_file.empty()) {
+      ellc_map_filter filter;
+      filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+      std::vector<ellc_map_point> cloud;
+      globalOptimizeLoop->exportLocalMap(filter, 0, cloud);
+      write_ply(map_file, cloud);
+    }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "ellc_main: %s\n", e.what());
     return -2;

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 11   /* ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 12   /* ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -283,6 +283,53 @@ ellc_status ellc_copy_slot(ellc_ctx* ctx, int dst_is_keyframe, int dst_slot, int
  * everything enqueued on src_ctx so far, and src_ctx's later work behind the copy; the host does not wait. The caller
  * serialises it with every other call on either context. */
 ellc_status ellc_copy_slot_across(ellc_ctx* dst_ctx, int dst_is_keyframe, int dst_slot, ellc_ctx* src_ctx, int src_is_keyframe, int src_slot);
+
+/* ---- the semi-dense map as 3-D points (v12) ------------------------------------------------------------------
+ * The map lives on the device: every keyframe slot holds depth and variance pyramids. The reference never hands it out — its only
+ * consumer is the display code (displayColourDepthMap, DepthPropagation.cpp:1160-1250) — so this entry point has no reference
+ * counterpart; the per-pixel arithmetic is the reference's back-projection. */
+typedef struct {
+  float    x, y, z;     /* the point in the caller's frame (T below) */
+  float    var;         /* variance of the INVERSE depth at the pixel: depthMap::depthvararrptr[level] */
+  uint16_t px, py;      /* the pixel on `level` (column, row) */
+  uint8_t  intensity;   /* keyframe grey value at (px, py) of that level's image */
+  uint8_t  support;     /* supporting 8-neighbours, 0..8 (rule below) */
+  uint16_t source;      /* index b of the request inside this call */
+} ellc_map_point;       /* 24 bytes, every field naturally aligned */
+
+typedef struct {
+  float max_var;        /* keep var <= max_var; <= 0: no variance test */
+  int   min_support;    /* 0..8: keep support >= min_support */
+  float support_k2;     /* >= 0, finite: neighbour n supports c iff (1/Zn - 1/Zc)^2 <= support_k2 * (Vc + Vn) */
+  int   stride;         /* >= 1: keep only pixels with px % stride == 0 and py % stride == 0 */
+} ellc_map_filter;
+
+/* B requests: request b exports keyframe slot kf_slots[b] on pyramid level `level` from the slot's depth, variance and image planes of
+ * that level; slots may repeat within a call. T = T12 + 12 * b is a row-major 3x4 f32 that takes the keyframe's camera coordinates
+ * into the caller's frame (a caller folds any scale into the 3x3 block).
+ *   A pixel is OK iff Z > 0 && Z <= FLT_MAX && V >= 0 (NaN fails all three; updateDepthImage writes 1 / invDepthSmoothed for any
+ * invDepthSmoothed >= -0.05, DepthPropagation.cpp:1285-1289, so +inf and negative depths do occur). Its SUPPORT counts the
+ * 8-neighbours that lie inside cols x rows of the level, are ok and satisfy (1/Zn - 1/Zc)^2 <= support_k2 * (Vc + Vn) — always the
+ * level's full-resolution neighbourhood, whatever `stride` is, and always computed. A pixel is KEPT iff it is ok, px % stride == 0 and
+ * py % stride == 0, max_var <= 0 || V <= max_var, and support >= min_support.
+ *   The point of a kept pixel, in the reference's order (PixelWisePyramid.cpp:236-238, :244): X = ((px - cx) * Z) / fx,
+ * Y = ((py - cy) * Z) / fy with the level's intrinsics (float)((double)fx / 2^level), then x = ((T[0]*X + T[1]*Y) + T[2]*Z) + T[3],
+ * rows 1 and 2 likewise. All of it is IEEE f32 with correctly rounded divisions (1/Z too) and no contraction: a record is a function
+ * of the configuration's intrinsics, the level, the slot's three planes, T and the filter ALONE — cfg.arith, cfg.grid_batch, B and
+ * whatever else is in flight do not enter it. Coordinates that overflow f32 are the caller's business.
+ *   Records come request-major, in raster order within a request. counts[b] (may be NULL) receives the number of points of request b,
+ * *total (may be NULL) their sum. out == NULL is the sizing call: only counts and total are produced and capacity is ignored.
+ * Otherwise, if the sum exceeds capacity the call returns ELLC_ERR_CAPACITY, nothing is written to out, counts and total are still
+ * filled; on success exactly *total records are written.
+ *   Synchronous, ordered like every other non-batch entry point (behind the batches in flight, before later ones). Reads the slots'
+ * planes only and writes nothing that belongs to a slot (no tile count, list count, compact list, validity mark or dense hint); its
+ * scratch is its own, allocated by the first call.
+ * ELLC_ERR_BAD_ARG: B < 1, B > max_keyframes (or > 65535, or B x the pixels of the level beyond INT_MAX: the total is an int), a slot
+ * or the level out of range, kf_slots, T12 or filter NULL, capacity < 0 with out non-NULL, min_support outside 0..8, stride < 1,
+ * support_k2 negative or not finite, max_var NaN;
+ * ELLC_ERR_NOT_READY: a slot without image or depth. */
+ellc_status ellc_keyframe_map_points(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, int level,
+                                     const ellc_map_filter* filter, ellc_map_point* out, int capacity, int* counts, int* total);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

@@ -26,6 +26,11 @@ ellc_status ellc_profile_align(ellc_ctx* ctx, int B, const int* kf_slots, const 
  * one launch. */
 ellc_status ellc_profile_depth_stage(ellc_ctx* ctx, int stage, int frame_slot, const float* pose_frame_wrt_kf, int reps, float* avg_ms);
 
+/* ellc_keyframe_map_points with HIP events around its three launches (map_count + map_scan, then map_scatter): launches_ms receives
+ * their device time, without the copy of the records to the host. Everything else as the product call. */
+ellc_status ellc_profile_map_points(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* filter,
+                                    ellc_map_point* out, int capacity, int* counts, int* total, float* launches_ms);
+
 /* Counter calibration: stream `bytes` of device memory once per launch with 4-byte-per-lane loads (the access
  * width of the compacted pixel arrays), `reps` launches, so FETCH_SIZE can be scaled against a known byte count
  * (MI355X_MICROARCH.md, HBM section). Returns average milliseconds per launch. */

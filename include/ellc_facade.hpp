@@ -497,6 +497,44 @@ class globalOptimize {
     }
   }
 
+  // The ring's semi-dense map as 3-D points in world coordinates (ellc_keyframe_map_points; no reference counterpart — the reference
+  // only draws its depth map, DepthPropagation.cpp:1160-1250). Waits for the match thread, then exports every valid, non-stray ring
+  // entry in ring-array order, one request each: out[k].source is the request's number, and the entries' array ids are returned in
+  // that order. exp(poseWrtWorld) takes world coordinates into the keyframe's (Frame.cpp:352-358), so entry i is exported through
+  // T = exp(poseWrtWorld)^-1 (mapTransform); scale (optional, indexed by array id) multiplies its 3x3 block. Chaining the
+  // per-keyframe rescaleFactor into such a scale stays with the caller, as it does for the pose files.
+  static void mapTransform(const float* poseWrtWorld, float scale, float* T12) {
+    float E[16];
+    ellc_se3_exp(poseWrtWorld, E);
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) T12[4 * r + c] = E[4 * c + r] * scale;                      // R^T (scaled)
+      T12[4 * r + 3] = -((E[r] * E[3] + E[4 + r] * E[7]) + E[8 + r] * E[11]);                 // -R^T t
+    }
+  }
+  std::vector<int> exportLocalMap(const ellc_map_filter& filter, int level, std::vector<ellc_map_point>& out, const float* scale = nullptr) {
+    join_all();
+    std::vector<int> ids, slots;
+    std::vector<float> T;
+    for (int i = 0; i < MAX_LOOP_ARRAY_LENGTH_SCALE_AVG; i++) {
+      const loopFrame& e = loopFrameArray[i];
+      if (!e.isValid || e.isStray || e.kf_slot < 0) continue;
+      ids.push_back(i);
+      slots.push_back(e.kf_slot);
+      T.resize(T.size() + 12);
+      mapTransform(e.poseWrtWorld, scale ? scale[i] : 1.0f, &T[T.size() - 12]);
+    }
+    out.clear();
+    if (ids.empty()) return ids;
+    int total = 0;
+    ring.check(ellc_keyframe_map_points(ring.ctx, (int)ids.size(), slots.data(), T.data(), level, &filter, nullptr, 0, nullptr, &total),
+               "ellc_keyframe_map_points");
+    out.resize((size_t)total);
+    ellc_map_point none;
+    ring.check(ellc_keyframe_map_points(ring.ctx, (int)ids.size(), slots.data(), T.data(), level, &filter, total ? out.data() : &none, total, nullptr, &total),
+               "ellc_keyframe_map_points");
+    return ids;
+  }
+
  private:
   // what the matching thread keeps of the pushed keyframe (the reference hands it loopFrameArray[currentArrayId].this_frame, a
   // deep copy: the caller's frame object may be gone before the thread ends)
@@ -663,6 +701,23 @@ class globalOptimize {
     if (match_window_beg == RING) match_window_beg = 0;
   }
 };
+
+// Points as a binary little-endian PLY: x y z float, intensity uchar, var float (17 bytes a vertex). Host-only.
+inline void write_ply(const std::string& path, const std::vector<ellc_map_point>& points) {
+  std::ofstream f(path.c_str(), std::ios::binary);
+  if (!f) throw std::runtime_error("write_ply: cannot open " + path);
+  f << "ply\nformat binary_little_endian 1.0\nelement vertex " << points.size()
+    << "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar intensity\nproperty float var\nend_header\n";
+  std::vector<char> buf(points.size() * 17);
+  for (size_t i = 0; i < points.size(); i++) {   // (the hosts this library runs on are little-endian)
+    char* r = &buf[i * 17];
+    std::memcpy(r, &points[i].x, 12);
+    r[12] = (char)points[i].intensity;
+    std::memcpy(r + 13, &points[i].var, 4);
+  }
+  f.write(buf.data(), (std::streamsize)buf.size());
+  if (!f) throw std::runtime_error("write_ply: cannot write " + path);
+}
 
 }  // namespace ellc
 #endif
