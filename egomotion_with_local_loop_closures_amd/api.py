@@ -353,6 +353,32 @@ class Context:
         self._ck(st, "ellc_keyframe_map_points")
         return pts, counts
 
+    # ---- the map rendered into a view
+    def _render(self, fn, name, extra, kf_slots, T12, level, agree_k2, dst_slot, max_var, min_support, support_k2, stride, out=None):
+        kf = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        B = kf.size
+        T = np.ascontiguousarray(T12, np.float32).reshape(B, 12)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        shp = self.level_shape(level) if 0 <= level < self.levels else (1, 1)   # (a level out of range is the library's to refuse)
+        if out is None:
+            out = dict(depth=np.zeros(shp, np.float32), var=np.zeros(shp, np.float32), source=np.zeros(shp, np.int32),
+                       agree=np.zeros(shp, np.int32), intensity=np.zeros(shp, np.uint8))
+        for k, dt in (("depth", np.float32), ("var", np.float32), ("source", np.int32), ("agree", np.int32), ("intensity", np.uint8)):
+            assert out[k].dtype == dt and out[k].shape == shp and out[k].flags.c_contiguous, k
+        n = C.c_int(0)
+        self._ck(fn(self.h, B, _p(kf), _p(T), int(level), C.byref(flt), C.c_float(agree_k2), int(dst_slot), _p(out["depth"]), _p(out["var"]),
+                    _p(out["source"]), _p(out["agree"]), _p(out["intensity"]), C.byref(n), *extra), name)
+        out["n_valid"] = n.value
+        return out
+
+    def render_depth(self, kf_slots, T12, level=0, agree_k2=1.0, dst_slot=-1, max_var=0.0, min_support=0, support_k2=1.0, stride=1, out=None):
+        """The keyframe slots' maps on `level` splatted into one view (ellc_keyframe_render_depth): T12[b] is the row-major 3x4 transform
+        from keyframe b's camera into the view's. Returns a dict of the planes depth, var (f32), source, agree (int32), intensity
+        (uint8), each (rows, cols) of the level, and n_valid. dst_slot >= 0 (level 0 only) also leaves depth / var in that keyframe
+        slot, as keyframe_set_depth would. out: a dict of such planes from an earlier call, written again instead of new arrays."""
+        return self._render(self._l.ellc_keyframe_render_depth, "ellc_keyframe_render_depth", (), kf_slots, T12, level, agree_k2, dst_slot,
+                            max_var, min_support, support_k2, stride, out)
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -471,6 +497,15 @@ class Context:
         self._ck(self._l.ellc_profile_map_points(self.h, B, _p(kf), _p(T), int(level), C.byref(flt), _p(pts), total.value, _p(counts), C.byref(total),
                                                  C.byref(ms)), "ellc_profile_map_points")
         return pts, counts, ms.value
+
+    def profile_render_depth(self, kf_slots, T12, level=0, agree_k2=1.0, dst_slot=-1, max_var=0.0, min_support=0, support_k2=1.0, stride=1, out=None):
+        """render_depth through ellc_profile_render_depth: its dict plus launches_ms, the device time of the launches."""
+        self._need_diag("ellc_profile_render_depth")
+        ms = C.c_float(0)
+        out = self._render(self._l.ellc_profile_render_depth, "ellc_profile_render_depth", (C.byref(ms),), kf_slots, T12, level, agree_k2,
+                           dst_slot, max_var, min_support, support_k2, stride, out)
+        out["launches_ms"] = ms.value
+        return out
 
     def profile_calibrate_read(self, nbytes, reps=10):
         self._need_diag("ellc_profile_calibrate_read")

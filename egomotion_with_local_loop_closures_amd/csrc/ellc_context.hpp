@@ -231,6 +231,16 @@ struct ellc_ctx {
   int *map_totals_h = nullptr, *map_totals_dev_alias = nullptr;   // pinned: [max_keyframes] points per request, then their sum (map_scan writes them)
   void* map_out_d = nullptr;                // device staging of the records: an allocation of its own that grows with the largest call
   size_t map_out_cap = 0;                   //   records it holds
+  // ellc_keyframe_render_depth: scratch of its own, allocated by the first call
+  int* render_stage_h = nullptr;            // pinned: [max_keyframes] slot of every request, [max_keyframes][12] f32 transforms
+  void* render_block_d = nullptr;           // one device allocation of its own (several MB at 640x480: not carved from the arena) that holds:
+  int* render_stage_d = nullptr;            //   the device copy of the record above
+  unsigned long long* render_keys_d = nullptr;   // [W*H] smallest candidate key per target
+  float *render_depth_d = nullptr, *render_var_d = nullptr;   // [W*H] the view's planes
+  int32_t *render_source_d = nullptr, *render_agree_d = nullptr;
+  uint8_t* render_intensity_d = nullptr;
+  int* render_block_counts_d = nullptr;     // [ceil(W*H / 256)] targets with a winner per block of render_resolve
+  int *render_nvalid_h = nullptr, *render_nvalid_dev_alias = nullptr;   // pinned: their sum (render_finish writes it)
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

@@ -274,6 +274,32 @@ ellc_status build_maxgrad(ellc_ctx* c, bool is_kf, int slot) {
 
 ellc_status build_depth_pyramid(ellc_ctx* c, int slot) { return build_depth_pyramid_from(c, slot, 1); }
 
+// What follows the write of a slot's level-0 depth and variance planes (enqueued on the main stream by the caller, records invalidated
+// before it): levels 1 and up, the validity mark, the dense hint and, for a dense map, the reciprocal planes. count_valid() returns the
+// number of level-0 pixels with depth > 0; it is called while the pyramid kernels are in flight. Shared by ellc_keyframe_set_depth (the
+// planes come from the host) and ellc_keyframe_render_depth (they are rendered on the device).
+template <class CountValid>
+static ellc_status finish_depth_planes(ellc_ctx* c, int slot, CountValid count_valid) {
+  const size_t n0 = (size_t)c->geom_h[0].n;
+  ellc_status s = build_depth_pyramid(c, slot);
+  if (s != ELLC_OK) return s;
+  // dense hint (see gn_fca_dense): a map written (nearly) full is aligned without compact lists; maps the depth stages export are
+  // semi-dense by construction and never are
+  const size_t nvalid = count_valid();
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  c->kf_has_depth[slot] = 1;
+  c->kf_dense[slot] = (nvalid * 10 >= n0 * 9) ? 1 : 0;
+  if (c->kf_dense[slot])   // the reciprocal planes gn_fca_dense4 reads (KfLevelDev::idepth)
+    for (int l = 0; l < c->L; l++) {
+      const KfLevelDev& kl = c->kf_tab_h[(size_t)l * c->cfg.max_keyframes + slot];
+      const int n = c->geom_h[l].n;
+      hipLaunchKernelGGL(idepth_plane, dim3((n + 255) / 256), dim3(256), 0, c->stream, kl.depth, kl.idepth, n);
+      if (kl.invz) hipLaunchKernelGGL(invz_plane, dim3((n + 255) / 256), dim3(256), 0, c->stream, kl.depth, kl.invz, n);
+    }
+  ELLC_HIP(c, hipGetLastError());
+  return ELLC_OK;
+}
+
 ellc_status build_depth_pyramid_from(ellc_ctx* c, int slot, int first_level) {
   for (int l = std::max(1, first_level); l < c->L; l++) {
     const KfLevelDev& s = c->kf_tab_h[(l - 1) * c->cfg.max_keyframes + slot];
@@ -1209,6 +1235,7 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
     if (c->upload_done[k]) (void)hipEventDestroy(c->upload_done[k]);
   }
   if (c->map_out_d) (void)hipFree(c->map_out_d);
+  if (c->render_block_d) (void)hipFree(c->render_block_d);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
   if (c->ingest_bgr) (void)hipFree(c->ingest_bgr);
   for (int p = 0; p < ellc_ctx::SETS; p++)
@@ -1475,24 +1502,12 @@ ellc_status ellc_keyframe_set_depth(ellc_ctx* c, int slot, const float* depth0, 
   invalidate_records(c, slot);
   ELLC_HIP(c, hipMemcpyAsync(k.depth, depth0, n0 * 4, hipMemcpyHostToDevice, c->stream));
   ELLC_HIP(c, hipMemcpyAsync(k.var, var0, n0 * 4, hipMemcpyHostToDevice, c->stream));
-  ellc_status s = build_depth_pyramid(c, slot);
-  if (s != ELLC_OK) return s;
-  // dense hint (see gn_fca_dense): counted here, on the host's copy, while the upload is in flight — a map uploaded (nearly) full is
-  // aligned without compact lists; maps the depth stages export are semi-dense by construction and never are
-  size_t nvalid = 0;
-  for (size_t i = 0; i < n0; i++) nvalid += depth0[i] > 0.0f ? 1 : 0;
-  ELLC_HIP(c, hipStreamSynchronize(c->stream));
-  c->kf_has_depth[slot] = 1;
-  c->kf_dense[slot] = (nvalid * 10 >= n0 * 9) ? 1 : 0;
-  if (c->kf_dense[slot])   // the reciprocal planes gn_fca_dense4 reads (KfLevelDev::idepth)
-    for (int l = 0; l < c->L; l++) {
-      const KfLevelDev& kl = c->kf_tab_h[(size_t)l * c->cfg.max_keyframes + slot];
-      const int n = c->geom_h[l].n;
-      hipLaunchKernelGGL(idepth_plane, dim3((n + 255) / 256), dim3(256), 0, c->stream, kl.depth, kl.idepth, n);
-      if (kl.invz) hipLaunchKernelGGL(invz_plane, dim3((n + 255) / 256), dim3(256), 0, c->stream, kl.depth, kl.invz, n);
-    }
-  ELLC_HIP(c, hipGetLastError());
-  return ELLC_OK;
+  // counted on the host's copy, while the upload is in flight
+  return finish_depth_planes(c, slot, [&]() {
+    size_t nvalid = 0;
+    for (size_t i = 0; i < n0; i++) nvalid += depth0[i] > 0.0f ? 1 : 0;
+    return nvalid;
+  });
 }
 
 ellc_status ellc_keyframe_set_depth_level(ellc_ctx* c, int slot, int level, const float* depth, const float* var) {
@@ -2707,3 +2722,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 #include "ellc_depth_impl.hpp"
 #include "ellc_ingest_impl.hpp"
 #include "ellc_map_impl.hpp"
+#include "ellc_render_impl.hpp"

@@ -26,6 +26,9 @@
 // --map FILE         (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
 //                    level 0, no variance test, at least 3 supporting neighbours, support_k2 1, every pixel), written as binary PLY
 //                    (x y z float, intensity uchar, var float); every other file is unchanged
+// --render FILE      (LC mode) at the end of the run the ring's keyframes rendered into the view of the last pushed keyframe
+//                    (globalOptimize::renderLocalMap: level 0, the filter of --map, agree_k2 1); the depth plane is written as a
+//                    little-endian PFM ("Pf", rows bottom to top, 0 where nothing landed); every other file is unchanged
 // Input is otherwise a header-less file of W*H u8 grey frames (the decode itself always stays outside).
 // In LC mode finished keyframes go through the loop-closure ring (facade class globalOptimize): matching and the batched
 // alignment of a pushed keyframe run on a second thread and a second context beside tracking, joined at the next push
@@ -42,7 +45,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--map FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--map FILE] [--render FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -52,7 +55,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, map_file;
+  std::string comm_id_file, match_quality, map_file, render_file;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -70,6 +73,7 @@ int main(int argc, char** argv) {
     else if (a == "--comm-tcp" && i + 1 < argc) comm_port = std::atoi(argv[++i]);
     else if (a == "--match-quality" && i + 1 < argc) match_quality = argv[++i];
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
+    else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return -1; }
   }
@@ -204,6 +208,14 @@ int main(int argc, char** argv) {
       std::vector<ellc_map_point> cloud;
       globalOptimizeLoop->exportLocalMap(filter, 0, cloud);
       write_ply(map_file, cloud);
+    }
+    if (globalOptimizeLoop && !render_file.empty()) {
+      if (globalOptimizeLoop->lastPushedArrayId < 0) throw std::runtime_error("--render: no keyframe was pushed into the ring");
+      ellc_map_filter filter;
+      filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+      RenderedView view;
+      globalOptimizeLoop->renderLocalMap(globalOptimizeLoop->loopFrameArray[globalOptimizeLoop->lastPushedArrayId].poseWrtWorld, 0, filter, 1.0f, nullptr, view);
+      write_pfm(render_file, view.depth, view.cols, view.rows);
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "ellc_main: %s\n", e.what());

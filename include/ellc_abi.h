@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 12   /* ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 13   /* ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -330,6 +330,45 @@ typedef struct {
  * ELLC_ERR_NOT_READY: a slot without image or depth. */
 ellc_status ellc_keyframe_map_points(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, int level,
                                      const ellc_map_filter* filter, ellc_map_point* out, int capacity, int* counts, int* total);
+
+/* ---- the map rendered into a view (v13) -----------------------------------------------------------------------
+ * A forward splat of B keyframe slots into ONE camera view: the depth and variance a frame at that view would be predicted to have.
+ * Request b reads keyframe slot kf_slots[b] on pyramid level `level`; slots may repeat. T = T12 + 12 * b is a row-major 3x4 f32 that
+ * takes the keyframe's camera coordinates into the VIEW's camera coordinates. The view has the context's camera at `level` (the
+ * level's intrinsics (float)((double)fx / 2^level), as above).
+ *   A source pixel takes part iff ellc_keyframe_map_points would KEEP it under `filter` (ok, stride, max_var, support — the rule above).
+ * The CANDIDATE of a kept pixel (px, py, Z, V), all IEEE f32 in this order, no contraction, correctly rounded divisions:
+ *   X, Y and P' = (x', y', z') as the point of ellc_keyframe_map_points (PixelWisePyramid.cpp:236-244);
+ *   dropped unless z' > 0 && z' <= FLT_MAX;
+ *   nid = 1 / z';  u = (x' * nid) * fx + cx;  v = (y' * nid) * fy + cy  (DepthPropagation.cpp:1050-1054);  ux = u + 0.5f;  vy = v + 0.5f;
+ *   dropped unless ux >= 0 && ux < (float)cols && vy >= 0 && vy < (float)rows (NaN fails); the target is ((int)ux, (int)vy) (:1065);
+ *   r = nid / (1 / Z);  r *= r;  r *= r;  nvar = r * V  (:1082-1086, applied to the variance);  dropped unless nvar >= 0 && nvar <= FLT_MAX.
+ * The WINNER of a target is the candidate with the smallest 64-bit key (bits(z') << 32) | (b << 24) | i, i the source pixel's raster
+ * index on the level: the nearest surface wins, exact ties go to the lower request, then to the lower raster index. Candidates are
+ * not fused (the merge of :1124-1148 is not applied) and there is no photometric gate (:1066-1076). agree[target] counts the
+ * candidates of that target, the winner included, for which d = nid - nid_winner satisfies d * d <= agree_k2 * (nvar + nvar_winner).
+ *   Outputs are host pointers, dense cols x rows of the level, each may be NULL:
+ *     depth      z' of the winner                                   0 without a winner
+ *     var        nvar of the winner                                 -1
+ *     source     (b << 24) | i of the winner                        -1
+ *     agree      the count above (>= 1)                             0
+ *     intensity  the winner's grey value on that level's image      0
+ * (0 / -1 are what ellc_keyframe_set_depth takes for "no hypothesis".) *n_valid (may be NULL) receives the number of targets with a
+ * winner. A result is a function of the intrinsics, the level, the slots' three planes, the T's, the filter and agree_k2 ALONE:
+ * cfg.arith, cfg.grid_batch and whatever else is in flight do not enter it, and it does not depend on the order candidates arrive in.
+ *   dst_kf_slot == -1: nothing is written to any slot. dst_kf_slot >= 0 (level 0 only, not among kf_slots): afterwards the slot is in
+ * every respect what ellc_keyframe_set_depth(ctx, dst_kf_slot, depth, var) with the planes this call returns would leave — pyramid
+ * levels, invalidated records, validity mark, dense hint, reciprocal planes — without the planes travelling to the host and back.
+ *   Synchronous, ordered like every other non-batch entry point; its scratch is its own, allocated by the first call. A refused call
+ * changes nothing.
+ * ELLC_ERR_BAD_ARG: B < 1, B > max_keyframes, B > 256, a slot or the level out of range, more than 2^24 pixels on the level, kf_slots,
+ * T12 or filter NULL, the filter errors of ellc_keyframe_map_points, agree_k2 negative or not finite, dst_kf_slot < -1 or >=
+ * max_keyframes, a destination with level != 0, a destination that is also a source;
+ * ELLC_ERR_NOT_READY: a source slot without image or depth. */
+ellc_status ellc_keyframe_render_depth(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, int level,
+                                       const ellc_map_filter* filter, float agree_k2, int dst_kf_slot,
+                                       float* depth, float* var, int32_t* source, int32_t* agree, uint8_t* intensity,
+                                       int* n_valid);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

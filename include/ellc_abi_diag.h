@@ -31,6 +31,12 @@ ellc_status ellc_profile_depth_stage(ellc_ctx* ctx, int stage, int frame_slot, c
 ellc_status ellc_profile_map_points(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* filter,
                                     ellc_map_point* out, int capacity, int* counts, int* total, float* launches_ms);
 
+/* ellc_keyframe_render_depth with HIP events around its launches (the preset of the keys, render_min, render_resolve, render_finish,
+ * render_agree): launches_ms receives their device time, without the copies that follow. Everything else as the product call. */
+ellc_status ellc_profile_render_depth(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* filter,
+                                      float agree_k2, int dst_kf_slot, float* depth, float* var, int32_t* source, int32_t* agree,
+                                      uint8_t* intensity, int* n_valid, float* launches_ms);
+
 /* Counter calibration: stream `bytes` of device memory once per launch with 4-byte-per-lane loads (the access
  * width of the compacted pixel arrays), `reps` launches, so FETCH_SIZE can be scaled against a known byte count
  * (MI355X_MICROARCH.md, HBM section). Returns average milliseconds per launch. */

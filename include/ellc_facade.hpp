@@ -370,6 +370,17 @@ inline std::vector<float> TrackFrameAndObserve(frame* prev_frame, frame* current
 // into it (ellc_copy_slot_across = new frame(*currentframe) / new depthMap(*currentDepthMap), :185-186) and the thread only
 // ever touches the ring context. The ring context fixes its launch grids per batch (ellc_ctx_set_grid_batch; Runtime::lc_fixed_grids):
 // a rank's shard of a batch has the bits of the whole batch.
+// What globalOptimize::renderLocalMap returns: the five planes of ellc_keyframe_render_depth (dense cols x rows of the level), the number
+// of targets with a winner, and the requests they were rendered from.
+struct RenderedView {
+  int cols = 0, rows = 0, n_valid = 0;
+  std::vector<int> ids, slots;    // ring array ids / ring keyframe slots of the requests, in request order (source >> 24 indexes them)
+  std::vector<float> T;           // [requests][12]: keyframe camera -> view camera, as passed to the library
+  std::vector<float> depth, var;
+  std::vector<int32_t> source, agree;
+  std::vector<uint8_t> intensity;
+};
+
 class globalOptimize {
  public:
   static const int MAX_LOOP_ARRAY_LENGTH = 20;                                   // ExternVariable.h:161
@@ -473,6 +484,7 @@ class globalOptimize {
     loopFrame& slot = loopFrameArray[currentArrayId];
     slot.kf_slot = currentArrayId;
     slot.isStray = false;
+    lastPushedArrayId = currentArrayId;
     // :185-186 deep copies of the keyframe and its depth map, into the ring context
     rt->check(ellc_copy_slot_across(ring.ctx, 1, slot.kf_slot, rt->ctx, 1, currentframe->kf_slot), "ellc_copy_slot_across");
     TestFrame test;
@@ -534,6 +546,50 @@ class globalOptimize {
                "ellc_keyframe_map_points");
     return ids;
   }
+
+  // The ring's map seen from a camera pose (ellc_keyframe_render_depth; the reference's findConnection, GlobalOptimize.cpp:862-896, does
+  // this with a copied depthMap and createKeyFrame behind its unconditional return). Waits for the match thread, then splats every
+  // valid, non-stray ring entry, in ring-array order, into the view whose world-to-camera transform is exp(viewPoseWrtWorld) — the
+  // poseWrtWorld convention of exportLocalMap: request b goes through T_b = exp(viewPoseWrtWorld) * exp(poseWrtWorld_b)^-1, composed in
+  // f32 (viewTransform). into (may be null; level 0 only): a keyframe of the TRACKING runtime that receives the rendered depth and
+  // variance as its level-0 planes (ellc_keyframe_set_depth: the ring lives in a context of its own, so the planes this call returns
+  // anyway are handed across; inside one context ellc_keyframe_render_depth's dst_kf_slot does it without the host).
+  static void viewTransform(const float* viewPoseWrtWorld, const float* poseWrtWorld, float* T12) {
+    float V[16], M[12];
+    ellc_se3_exp(viewPoseWrtWorld, V);
+    mapTransform(poseWrtWorld, 1.0f, M);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++)
+        T12[4 * r + c] = ((V[4 * r] * M[c] + V[4 * r + 1] * M[4 + c]) + V[4 * r + 2] * M[8 + c]) + (c == 3 ? V[4 * r + 3] : 0.0f);
+  }
+  void renderLocalMap(const float* viewPoseWrtWorld, int level, const ellc_map_filter& filter, float agree_k2, frame* into, RenderedView& out) {
+    join_all();
+    if (level < 0 || level >= ring.cfg.levels) throw std::runtime_error("renderLocalMap: level out of range");
+    if (into && (level != 0 || into->kf_slot < 0)) throw std::runtime_error("renderLocalMap: the destination must be a keyframe and the level 0");
+    out = RenderedView();
+    out.cols = ring.cfg.width >> level;
+    out.rows = ring.cfg.height >> level;
+    for (int i = 0; i < MAX_LOOP_ARRAY_LENGTH_SCALE_AVG; i++) {
+      const loopFrame& e = loopFrameArray[i];
+      if (!e.isValid || e.isStray || e.kf_slot < 0) continue;
+      out.ids.push_back(i);
+      out.slots.push_back(e.kf_slot);
+      out.T.resize(out.T.size() + 12);
+      viewTransform(viewPoseWrtWorld, e.poseWrtWorld, &out.T[out.T.size() - 12]);
+    }
+    const size_t n = (size_t)out.cols * out.rows;
+    out.depth.assign(n, 0.0f);
+    out.var.assign(n, -1.0f);
+    out.source.assign(n, -1);
+    out.agree.assign(n, 0);
+    out.intensity.assign(n, 0);
+    if (!out.ids.empty())
+      ring.check(ellc_keyframe_render_depth(ring.ctx, (int)out.ids.size(), out.slots.data(), out.T.data(), level, &filter, agree_k2, -1, out.depth.data(),
+                                            out.var.data(), out.source.data(), out.agree.data(), out.intensity.data(), &out.n_valid),
+                 "ellc_keyframe_render_depth");
+    if (into) rt->check(ellc_keyframe_set_depth(rt->ctx, into->kf_slot, out.depth.data(), out.var.data()), "ellc_keyframe_set_depth");
+  }
+  int lastPushedArrayId = -1;   // the ring entry of the most recent pushToArray
 
  private:
   // what the matching thread keeps of the pushed keyframe (the reference hands it loopFrameArray[currentArrayId].this_frame, a
@@ -717,6 +773,16 @@ inline void write_ply(const std::string& path, const std::vector<ellc_map_point>
   }
   f.write(buf.data(), (std::streamsize)buf.size());
   if (!f) throw std::runtime_error("write_ply: cannot write " + path);
+}
+
+// A float plane as a little-endian greyscale PFM ("Pf", scale -1.0); PFM stores its scanlines bottom to top. Host-only.
+inline void write_pfm(const std::string& path, const std::vector<float>& plane, int cols, int rows) {
+  if (plane.size() != (size_t)cols * rows) throw std::runtime_error("write_pfm: plane size");
+  std::ofstream f(path.c_str(), std::ios::binary);
+  if (!f) throw std::runtime_error("write_pfm: cannot open " + path);
+  f << "Pf\n" << cols << " " << rows << "\n-1.0\n";
+  for (int y = rows - 1; y >= 0; y--) f.write((const char*)&plane[(size_t)y * cols], (std::streamsize)cols * 4);   // (little-endian hosts)
+  if (!f) throw std::runtime_error("write_pfm: cannot write " + path);
 }
 
 }  // namespace ellc
