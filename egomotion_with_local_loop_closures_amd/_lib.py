@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "ellc_depth_observe", "ellc_depth_fill_holes", "ellc_depth_regularize", "ellc_depth_make_inv_depth_one", "ellc_depth_regularize_fill_regularize", "ellc_depth_do_regularization",
     "ellc_depth_update_depth_image", "ellc_depth_create_keyframe", "ellc_depth_seeds", "ellc_track_frame",
     "ellc_histogram", "ellc_kl_divergence", "ellc_copy_slot", "ellc_copy_slot_across", "ellc_keyframe_map_points", "ellc_keyframe_render_depth",
+    "ellc_keyframe_depth_consistency",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
     "ellc_gather_start", "ellc_gather_finish", "ellc_gather_results",
@@ -33,7 +34,7 @@ DIAG_SYMBOLS = [
     "ellc_profile_gn_kernel", "ellc_profile_align", "ellc_profile_depth_stage", "ellc_profile_calibrate_read", "ellc_profile_stream_read",
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
     "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
-    "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth",
+    "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_depth_consistency",
 ]
 
 
@@ -66,6 +67,14 @@ class EllcMapPoint(C.Structure):
 class EllcMapFilter(C.Structure):
     """ellc_map_filter: which pixels ellc_keyframe_map_points keeps."""
     _fields_ = [("max_var", C.c_float), ("min_support", C.c_int), ("support_k2", C.c_float), ("stride", C.c_int)]
+
+
+class EllcDepthConsistency(C.Structure):
+    """ellc_depth_consistency: what ellc_keyframe_depth_consistency returns per request (72 bytes)."""
+    _fields_ = [("sum_chi2", C.c_double), ("sum_w_ss", C.c_double), ("sum_w_st", C.c_double),
+                ("sum_abs_di", C.c_int64), ("sum_di2", C.c_int64),
+                ("n_kept", C.c_int32), ("n_in_view", C.c_int32), ("n_overlap", C.c_int32), ("n_agree", C.c_int32),
+                ("n_in_front", C.c_int32), ("n_behind", C.c_int32), ("n_weighted", C.c_int32)]
 
 
 class EllcError(RuntimeError):

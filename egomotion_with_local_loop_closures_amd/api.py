@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -379,6 +379,27 @@ class Context:
         return self._render(self._l.ellc_keyframe_render_depth, "ellc_keyframe_render_depth", (), kf_slots, T12, level, agree_k2, dst_slot,
                             max_var, min_support, support_k2, stride, out)
 
+    # ---- one keyframe's map against another's
+    def _consistency(self, fn, name, extra, src_slots, dst_slots, Ts, level, agree_k2, max_var, min_support, support_k2, stride):
+        src = np.ascontiguousarray(src_slots, np.int32).reshape(-1)
+        dst = np.ascontiguousarray(dst_slots, np.int32).reshape(-1)
+        B = src.size
+        assert dst.size == B
+        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        out = np.zeros(B, np.dtype(EllcDepthConsistency))
+        self._ck(fn(self.h, B, _p(src), _p(dst), _p(T), int(level), C.byref(flt), C.c_float(agree_k2), _p(out), *extra), name)
+        return out
+
+    def depth_consistency(self, src_slots, dst_slots, Ts, level=0, agree_k2=1.0, max_var=0.0, min_support=0, support_k2=1.0, stride=1):
+        """Keyframe slot src_slots[b]'s map on `level` against slot dst_slots[b]'s (ellc_keyframe_depth_consistency): Ts[b] is the
+        row-major 3x4 transform from the source's camera into the destination's. Returns a structured array of B
+        ellc_depth_consistency records: n_kept, n_in_view, n_overlap, n_agree, n_in_front, n_behind, n_weighted (int32), sum_abs_di,
+        sum_di2 (int64), sum_chi2, sum_w_ss, sum_w_st (f64); sum_w_st / sum_w_ss is the scale that takes the source's inverse depths
+        onto the destination's."""
+        return self._consistency(self._l.ellc_keyframe_depth_consistency, "ellc_keyframe_depth_consistency", (), src_slots, dst_slots, Ts, level,
+                                 agree_k2, max_var, min_support, support_k2, stride)
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -506,6 +527,14 @@ class Context:
                            dst_slot, max_var, min_support, support_k2, stride, out)
         out["launches_ms"] = ms.value
         return out
+
+    def profile_depth_consistency(self, src_slots, dst_slots, Ts, level=0, agree_k2=1.0, max_var=0.0, min_support=0, support_k2=1.0, stride=1):
+        """depth_consistency through ellc_profile_depth_consistency: (records, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_depth_consistency")
+        ms = C.c_float(0)
+        out = self._consistency(self._l.ellc_profile_depth_consistency, "ellc_profile_depth_consistency", (C.byref(ms),), src_slots, dst_slots, Ts,
+                                level, agree_k2, max_var, min_support, support_k2, stride)
+        return out, ms.value
 
     def profile_calibrate_read(self, nbytes, reps=10):
         self._need_diag("ellc_profile_calibrate_read")

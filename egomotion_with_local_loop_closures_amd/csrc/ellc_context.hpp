@@ -241,6 +241,13 @@ struct ellc_ctx {
   uint8_t* render_intensity_d = nullptr;
   int* render_block_counts_d = nullptr;     // [ceil(W*H / 256)] targets with a winner per block of render_resolve
   int *render_nvalid_h = nullptr, *render_nvalid_dev_alias = nullptr;   // pinned: their sum (render_finish writes it)
+  // ellc_keyframe_depth_consistency: staging and scratch of its own (not from the arena: they grow with the largest call)
+  int consist_cap = 0;                      // requests the staging holds
+  int* consist_stage_h = nullptr;           // pinned: [cap] source slots, [cap] destination slots, [cap][12] f32 transforms
+  int* consist_stage_d = nullptr;           //   and its device copy
+  void *consist_out_h = nullptr, *consist_out_dev_alias = nullptr;   // pinned: [cap] records (consist_finish writes them)
+  void* consist_partials_d = nullptr;       // [requests of one launch][tiles of the level] partial records
+  size_t consist_partials_cap = 0;          //   records it holds
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

@@ -23,6 +23,11 @@
 // --match-quality PATH  (LC mode) one line per line of matchframes_globalopt.txt: "frameId kfId n_depth n_used rms wrms" — how well the
 //                    candidate fits at the pose the batch returned (ellc_align_quality_at, level 0); every other file is unchanged.
 //                    Single process only: refused with --world > 1 (the gather record stays 8 floats)
+// --match-geometry PATH  (LC mode) one line per line of matchframes_globalopt.txt: "frameId kfId n_kept n_in_view n_overlap n_agree
+//                    n_in_front n_behind scale mean_chi2 mean_abs_di" — the candidate's map against the pushed keyframe's at the pose the
+//                    batch returned, after the two maps were brought to one scale (ellc_keyframe_depth_consistency, level 0, the filter
+//                    of --map, agree_k2 1; globalOptimize::collectMatchGeometry); every other file is unchanged. With --world > 1 every
+//                    rank computes the whole batch: the ring is replicated
 // --map FILE         (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
 //                    level 0, no variance test, at least 3 supporting neighbours, support_k2 1, every pixel), written as binary PLY
 //                    (x y z float, intensity uchar, var float); every other file is unchanged
@@ -45,7 +50,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--map FILE] [--render FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--map FILE] [--render FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -55,7 +60,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, map_file, render_file;
+  std::string comm_id_file, match_quality, match_geometry, map_file, render_file;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -72,6 +77,7 @@ int main(int argc, char** argv) {
     else if (a == "--comm-id" && i + 1 < argc) comm_id_file = argv[++i];
     else if (a == "--comm-tcp" && i + 1 < argc) comm_port = std::atoi(argv[++i]);
     else if (a == "--match-quality" && i + 1 < argc) match_quality = argv[++i];
+    else if (a == "--match-geometry" && i + 1 < argc) match_geometry = argv[++i];
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
@@ -140,6 +146,11 @@ int main(int argc, char** argv) {
       globalOptimizeLoop->match_quality_file.open(match_quality.c_str());
       if (!globalOptimizeLoop->match_quality_file) { std::fprintf(stderr, "cannot open %s\n", match_quality.c_str()); return -1; }
       globalOptimizeLoop->collectMatchQuality = true;
+    }
+    if (lc && !match_geometry.empty()) {
+      globalOptimizeLoop->match_geometry_file.open(match_geometry.c_str());
+      if (!globalOptimizeLoop->match_geometry_file) { std::fprintf(stderr, "cannot open %s\n", match_geometry.c_str()); return -1; }
+      globalOptimizeLoop->collectMatchGeometry = true;
     }
     std::vector<std::unique_ptr<frame>> frameptr_vector;
     frame* activeKeyFrame = nullptr;

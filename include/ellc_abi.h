@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 13   /* ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 14   /* ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -369,6 +369,51 @@ ellc_status ellc_keyframe_render_depth(ellc_ctx* ctx, int B, const int* kf_slots
                                        const ellc_map_filter* filter, float agree_k2, int dst_kf_slot,
                                        float* depth, float* var, int32_t* source, int32_t* agree, uint8_t* intensity,
                                        int* n_valid);
+
+/* ---- one keyframe's map against another's (v14) ------------------------------------------------------------------
+ * The geometric check of a loop closure, and the scale between two maps: request b compares keyframe slot src_kf_slots[b] with slot
+ * dst_kf_slots[b] on pyramid level `level`. T = T12 + 12 * b is a row-major 3x4 f32 that takes the SOURCE's camera coordinates into
+ * the DESTINATION's (a caller folds a scale into all twelve entries). Source and destination may be the same slot, slots may repeat
+ * across requests. Per source pixel, all arithmetic IEEE f32 in this order, no contraction, correctly rounded divisions:
+ *   1. it takes part iff ellc_keyframe_map_points would KEEP it under `filter` (n_kept);
+ *   2. its candidate (target, z', nid, nvar) is ellc_keyframe_render_depth's, with the same drops (n_in_view);
+ *   3. at the target pixel of the destination slot's level: Zt, Vt and the grey value It (the image is read with its stored pitch);
+ *   4. it overlaps iff Zt > 0 && Zt <= FLT_MAX && Vt >= 0 (n_overlap); `filter` is not applied to the destination;
+ *   5. idt = 1 / Zt;  d = nid - idt;  s = nvar + Vt;
+ *   6. it agrees iff d * d <= agree_k2 * s; it is in front iff it does not agree and d > 0; it is behind otherwise;
+ *   7. Is is the source's grey value at the pixel; |Is - It| and its square are added as integers;
+ *   8. it is weighted iff s > 0 && s <= FLT_MAX; then w = 1 / s, q = (d * d) * w, ss = (nid * nid) * w, st = (nid * idt) * w, each
+ *      converted to double and added to its sum (terms that overflow f32 are the caller's business).
+ * sum_w_st / sum_w_ss is the least-squares factor that takes the source's inverse depths, as seen in the destination, onto the
+ * destination's: to bring the maps to one scale a caller divides all twelve entries of T by it and calls again.
+ *   Record b is a function of the intrinsics, the level, the two slots' planes, T, the filter and agree_k2 ALONE: the pixels are
+ * partitioned by the level's size (2048-pixel tiles), partial sums are combined in a fixed order in double; B, the position in the
+ * batch, the other requests, cfg.arith, cfg.grid_batch and whatever else is in flight do not enter it, and a shard of a batch gives
+ * the bytes of the whole batch.
+ *   Synchronous, ordered like every other non-batch entry point. Reads planes only: nothing that belongs to a slot is written. Its
+ * scratch and staging are its own, allocated by the first call and grown by the largest. 1 <= B <= 2048 (not bounded by
+ * max_keyframes: all ordered pairs of a ring are one call). A refused call changes nothing and writes nothing to `out`.
+ * ELLC_ERR_BAD_ARG: B out of range, a slot or the level out of range, more than 2^24 pixels on the level, a NULL pointer, the filter
+ * errors of ellc_keyframe_map_points, agree_k2 negative or not finite;
+ * ELLC_ERR_NOT_READY: a source or destination slot without image or depth. */
+typedef struct {
+  double  sum_chi2;    /* sum of (double)q over the weighted pixels */
+  double  sum_w_ss;    /* sum of (double)((nid * nid) * w) */
+  double  sum_w_st;    /* sum of (double)((nid * idt) * w) */
+  int64_t sum_abs_di;  /* sum of |Is - It| over the overlap pixels (grey values of the level's images) */
+  int64_t sum_di2;     /* sum of (Is - It)^2 over the overlap pixels */
+  int32_t n_kept;      /* source pixels ellc_keyframe_map_points would keep under `filter` */
+  int32_t n_in_view;   /* of those, pixels with a candidate (ellc_keyframe_render_depth's rule) */
+  int32_t n_overlap;   /* of those, pixels whose target in the destination slot holds a hypothesis */
+  int32_t n_agree;     /* of the overlap */
+  int32_t n_in_front;  /* of the overlap: not agreeing, source surface nearer than the destination's */
+  int32_t n_behind;    /* of the overlap: the rest (n_overlap == n_agree + n_in_front + n_behind, always) */
+  int32_t n_weighted;  /* overlap pixels that enter the three double sums */
+} ellc_depth_consistency;   /* 72 bytes, every field naturally aligned */
+
+ellc_status ellc_keyframe_depth_consistency(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots,
+                                            const float* T12, int level, const ellc_map_filter* filter, float agree_k2,
+                                            ellc_depth_consistency* out);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

@@ -16,6 +16,7 @@
 
 #include "ellc_abi.h"
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -415,6 +416,22 @@ class globalOptimize {
   bool collectMatchQuality = false;
   std::vector<ellc_align_quality> lastMatchQuality;
   std::ofstream match_quality_file;
+  // Whether each candidate's MAP agrees with the pushed keyframe's at that pose (ellc_keyframe_depth_consistency, level 0, candidate's
+  // slot -> testFrame's slot, T = the top three rows of exp(pose)): every keyframe's map is rescaled to mean inverse depth one
+  // (makeInvDepthOne), so the first call's sum_w_st / sum_w_ss is the relative scale of the two maps, and a second call with T divided
+  // by it compares them at one scale. Off by default: nothing changes. On: lastMatchGeometry holds the second call's record and the
+  // scale (1 where sum_w_ss is 0 or the ratio is not a positive finite number) per line the batch wrote to the match file, in that
+  // order, and match_geometry_file (when open) gets "frameId kfId n_kept n_in_view n_overlap n_agree n_in_front n_behind scale
+  // mean_chi2 mean_abs_di" per line (mean_chi2 = sum_chi2 / n_weighted, mean_abs_di = sum_abs_di / n_overlap; 0 for an empty
+  // denominator). The ring is replicated, and a record does not depend on the batch it is computed in: every rank of a sharded run
+  // computes the whole batch. What to do with the figures is the caller's.
+  struct MatchGeometry {
+    ellc_depth_consistency rec;
+    double scale;
+  };
+  bool collectMatchGeometry = false;
+  std::vector<MatchGeometry> lastMatchGeometry;
+  std::ofstream match_geometry_file;
 
   static ellc_config ring_config(const ellc_config& tracking, bool fixed_grids) {
     ellc_config c = tracking;
@@ -725,6 +742,30 @@ class globalOptimize {
         lastMatchQuality.assign((size_t)B, ellc_align_quality());
         ring.check(ellc_align_quality_at(ring.ctx, B, kf.data(), fr.data(), out.data(), 0, lastMatchQuality.data()), "ellc_align_quality_at");
       }
+      if (collectMatchGeometry) {
+        std::vector<int> dst((size_t)B, testFrame.ring_slot);
+        std::vector<float> T((size_t)B * 12);
+        std::vector<ellc_depth_consistency> rec((size_t)B);
+        ellc_map_filter filter;   // the filter of ellc_main --map; agree_k2 1
+        filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+        for (int b = 0; b < B; b++) {
+          float M[16];
+          ellc_se3_exp(&out[(size_t)b * 6], M);
+          for (int k = 0; k < 12; k++) T[(size_t)b * 12 + k] = M[k];
+        }
+        ring.check(ellc_keyframe_depth_consistency(ring.ctx, B, kf.data(), dst.data(), T.data(), 0, &filter, 1.0f, rec.data()),
+                   "ellc_keyframe_depth_consistency");
+        lastMatchGeometry.assign((size_t)B, MatchGeometry());
+        for (int b = 0; b < B; b++) {
+          double scale = rec[(size_t)b].sum_w_ss > 0.0 ? rec[(size_t)b].sum_w_st / rec[(size_t)b].sum_w_ss : 1.0;
+          if (!(scale > 0.0 && scale <= (double)FLT_MAX)) scale = 1.0;
+          lastMatchGeometry[(size_t)b].scale = scale;
+          for (int k = 0; k < 12; k++) T[(size_t)b * 12 + k] = (float)((double)T[(size_t)b * 12 + k] / scale);
+        }
+        ring.check(ellc_keyframe_depth_consistency(ring.ctx, B, kf.data(), dst.data(), T.data(), 0, &filter, 1.0f, rec.data()),
+                   "ellc_keyframe_depth_consistency");
+        for (int b = 0; b < B; b++) lastMatchGeometry[(size_t)b].rec = rec[(size_t)b];
+      }
       for (int b = 0; b < B; b++) {
         const loopFrame& m = loopFrameArray[matches[b].arrayId];
         float poseWrtOrigin[6];
@@ -742,9 +783,18 @@ class globalOptimize {
           match_quality_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << (m.frameId + rt->BATCH_START_ID - 1) << " " << q.n_depth << " "
                              << q.n_used << " " << rms << " " << wrms << "\n";
         }
+        if (collectMatchGeometry && match_geometry_file.is_open()) {
+          const MatchGeometry& q = lastMatchGeometry[(size_t)b];
+          const double mean_chi2 = q.rec.n_weighted > 0 ? q.rec.sum_chi2 / (double)q.rec.n_weighted : 0.0;
+          const double mean_abs_di = q.rec.n_overlap > 0 ? (double)q.rec.sum_abs_di / (double)q.rec.n_overlap : 0.0;
+          match_geometry_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << (m.frameId + rt->BATCH_START_ID - 1) << " " << q.rec.n_kept << " "
+                              << q.rec.n_in_view << " " << q.rec.n_overlap << " " << q.rec.n_agree << " " << q.rec.n_in_front << " " << q.rec.n_behind
+                              << " " << q.scale << " " << mean_chi2 << " " << mean_abs_di << "\n";
+        }
       }
       match_file.flush();
       if (match_quality_file.is_open()) match_quality_file.flush();
+      if (match_geometry_file.is_open()) match_geometry_file.flush();
     }
     // :614-641
     currentArrayId++;
