@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "ellc_depth_observe", "ellc_depth_fill_holes", "ellc_depth_regularize", "ellc_depth_make_inv_depth_one", "ellc_depth_regularize_fill_regularize", "ellc_depth_do_regularization",
     "ellc_depth_update_depth_image", "ellc_depth_create_keyframe", "ellc_depth_seeds", "ellc_track_frame",
     "ellc_histogram", "ellc_kl_divergence", "ellc_copy_slot", "ellc_copy_slot_across", "ellc_keyframe_map_points", "ellc_keyframe_render_depth",
-    "ellc_keyframe_depth_consistency",
+    "ellc_keyframe_depth_consistency", "ellc_keyframe_sim3_step", "ellc_keyframe_sim3_align", "ellc_sim3_default_params", "ellc_sim3_solve", "ellc_sim3_apply",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
     "ellc_gather_start", "ellc_gather_finish", "ellc_gather_results",
@@ -34,7 +34,7 @@ DIAG_SYMBOLS = [
     "ellc_profile_gn_kernel", "ellc_profile_align", "ellc_profile_depth_stage", "ellc_profile_calibrate_read", "ellc_profile_stream_read",
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
     "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
-    "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_depth_consistency",
+    "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
 ]
 
 
@@ -75,6 +75,18 @@ class EllcDepthConsistency(C.Structure):
                 ("sum_abs_di", C.c_int64), ("sum_di2", C.c_int64),
                 ("n_kept", C.c_int32), ("n_in_view", C.c_int32), ("n_overlap", C.c_int32), ("n_agree", C.c_int32),
                 ("n_in_front", C.c_int32), ("n_behind", C.c_int32), ("n_weighted", C.c_int32)]
+
+
+class EllcSim3Params(C.Structure):
+    """ellc_sim3_params: the weights and gates of ellc_keyframe_sim3_step."""
+    _fields_ = [("sigma_i2", C.c_float), ("huber_k", C.c_float), ("gate_k2", C.c_float), ("depth_weight", C.c_float)]
+
+
+class EllcSim3Normal(C.Structure):
+    """ellc_sim3_normal: what ellc_keyframe_sim3_step returns per request (320 bytes)."""
+    _fields_ = [("H", C.c_double * 28), ("b", C.c_double * 7), ("chi2_photo", C.c_double), ("chi2_depth", C.c_double),
+                ("n_kept", C.c_int32), ("n_in_view", C.c_int32), ("n_photo", C.c_int32), ("n_photo_huber", C.c_int32),
+                ("n_depth", C.c_int32), ("n_depth_gated", C.c_int32)]
 
 
 class EllcError(RuntimeError):
@@ -136,6 +148,9 @@ def _bind(path, symbols, what):
     h.ellc_stream.restype = C.c_void_p
     h.ellc_kl_divergence.restype = C.c_double
     h.ellc_comm_last_error.restype = C.c_char_p
+    if hasattr(h, "ellc_sim3_apply"):
+        h.ellc_sim3_apply.restype = None
+        h.ellc_sim3_default_params.restype = None
     for name in symbols:
         if _external and not hasattr(h, name):
             continue          # (diagnostic A/B builds only; the in-tree libraries must export every symbol)

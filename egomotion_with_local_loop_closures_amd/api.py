@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -10,6 +10,7 @@ ARITH_EXACT = 0
 ARITH_FAST = 1
 ERR_CAPACITY = -5
 MAP_POINT_DTYPE = np.dtype(EllcMapPoint)   # x y z var (f32), px py (u16), intensity support (u8), source (u16): 24 bytes
+SIM3_NORMAL_DTYPE = np.dtype(EllcSim3Normal)   # H (28 f64), b (7 f64), chi2_photo, chi2_depth (f64), six int32 counts: 320 bytes
 HYP_FIELDS = ("invDepth", "invDepthSmoothed", "variance", "varianceSmoothed", "validity", "blacklisted", "valid")
 
 
@@ -400,6 +401,51 @@ class Context:
         return self._consistency(self._l.ellc_keyframe_depth_consistency, "ellc_keyframe_depth_consistency", (), src_slots, dst_slots, Ts, level,
                                  agree_k2, max_var, min_support, support_k2, stride)
 
+    # ---- Sim(3) refinement of a pair of keyframes
+    def _sim3_args(self, src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params):
+        src = np.ascontiguousarray(src_slots, np.int32).reshape(-1)
+        dst = np.ascontiguousarray(dst_slots, np.int32).reshape(-1)
+        B = src.size
+        assert dst.size == B
+        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
+        return B, src, dst, T, EllcMapFilter(max_var, int(min_support), support_k2, int(stride)), sim3_params(**(params or {}))
+
+    def sim3_step(self, src_slots, dst_slots, Ts, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None):
+        """The normal equations of one seven-parameter Gauss-Newton step (ellc_keyframe_sim3_step) of keyframe slot src_slots[b] against
+        slot dst_slots[b] on `level` at Ts[b], the row-major 3x4 transform from the source's camera into the destination's with the scale
+        in its 3x3 block. params: dict of sigma_i2, huber_k, gate_k2, depth_weight (defaults 16, 1.345, 9, 1). Returns a structured
+        array of B ellc_sim3_normal records: H (28, upper triangle by rows), b (7), chi2_photo, chi2_depth (f64), n_kept, n_in_view,
+        n_photo, n_photo_huber, n_depth, n_depth_gated (int32). A step solves H xi = -b (sim3_solve) and T <- sim3_apply(xi, T)."""
+        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
+        out = np.zeros(B, SIM3_NORMAL_DTYPE)
+        self._ck(self._l.ellc_keyframe_sim3_step(self.h, B, _p(src), _p(dst), _p(T), int(level), C.byref(flt), C.byref(prm), _p(out)),
+                 "ellc_keyframe_sim3_step")
+        return out
+
+    def sim3_align(self, src_slots, dst_slots, Ts, level_from=0, level_to=0, max_iter=10, eps=1e-4, max_var=0.0, min_support=0, support_k2=1.0,
+                   stride=1, params=None, trace=False):
+        """The Gauss-Newton loop over sim3_step (ellc_keyframe_sim3_align), coarse to fine from level_from down to level_to, at most
+        max_iter updates per level, a pair leaving a level when max |xi_i| <= eps or its system is singular. Returns dict(T = [B][12]
+        f32, rec = the records at those T, iters = [B][levels visited] updates per level) and, with trace=True, trace_T / trace_rec:
+        per pair the T of every evaluation in order and its record (the final evaluation included)."""
+        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
+        n_levels = max(int(level_from) - int(level_to) + 1, 1)
+        cap = n_levels * max(int(max_iter), 1) + 1
+        T_out = np.zeros((B, 12), np.float32)
+        out = np.zeros(B, SIM3_NORMAL_DTYPE)
+        iters = np.zeros((B, n_levels), np.int32)
+        tT = np.zeros((B, cap, 12), np.float32) if trace else None
+        tR = np.zeros((B, cap), SIM3_NORMAL_DTYPE) if trace else None
+        self._ck(self._l.ellc_keyframe_sim3_align(self.h, B, _p(src), _p(dst), _p(T), int(level_from), int(level_to), C.byref(flt), C.byref(prm),
+                                                  int(max_iter), C.c_float(eps), _p(T_out), _p(out), _p(iters), _p(tT), _p(tR), cap if trace else 0),
+                 "ellc_keyframe_sim3_align")
+        res = dict(T=T_out, rec=out, iters=iters)
+        if trace:
+            n = [int((tR[b]["n_kept"] >= 0).sum()) for b in range(B)]
+            res["trace_T"] = [tT[b, :n[b]].copy() for b in range(B)]
+            res["trace_rec"] = [tR[b, :n[b]].copy() for b in range(B)]
+        return res
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -536,6 +582,16 @@ class Context:
                                 level, agree_k2, max_var, min_support, support_k2, stride)
         return out, ms.value
 
+    def profile_sim3_step(self, src_slots, dst_slots, Ts, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None):
+        """sim3_step through ellc_profile_sim3_step: (records, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_sim3_step")
+        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
+        out = np.zeros(B, SIM3_NORMAL_DTYPE)
+        ms = C.c_float(0)
+        self._ck(self._l.ellc_profile_sim3_step(self.h, B, _p(src), _p(dst), _p(T), int(level), C.byref(flt), C.byref(prm), _p(out), C.byref(ms)),
+                 "ellc_profile_sim3_step")
+        return out, ms.value
+
     def profile_calibrate_read(self, nbytes, reps=10):
         self._need_diag("ellc_profile_calibrate_read")
         ms = C.c_float(0)
@@ -601,6 +657,33 @@ def se3_log(T):
     p = np.zeros(6, np.float32)
     _lib.lib().ellc_se3_log(_p(T), _p(p))
     return p
+
+
+def sim3_params(sigma_i2=None, huber_k=None, gate_k2=None, depth_weight=None):
+    """ellc_sim3_params: the library's defaults (ellc_sim3_default_params) with the given fields replaced."""
+    p = EllcSim3Params()
+    _lib.lib().ellc_sim3_default_params(C.byref(p))
+    for k, v in (("sigma_i2", sigma_i2), ("huber_k", huber_k), ("gate_k2", gate_k2), ("depth_weight", depth_weight)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def sim3_solve(rec):
+    """ellc_sim3_solve of one ellc_sim3_normal record (a row of sim3_step's array): (xi7 f64, singular)."""
+    r = np.ascontiguousarray(np.asarray(rec, SIM3_NORMAL_DTYPE).reshape(1))
+    xi = np.zeros(7, np.float64)
+    singular = _lib.lib().ellc_sim3_solve(_p(r), _p(xi))
+    return xi, bool(singular)
+
+
+def sim3_apply(xi7, T12):
+    """ellc_sim3_apply: float(exp(xi^) * T) with the generator [[w]x + sigma I, v; 0 0], as 12 f32."""
+    xi = np.ascontiguousarray(xi7, np.float64).reshape(7)
+    T = np.ascontiguousarray(T12, np.float32).reshape(12)
+    out = np.zeros(12, np.float32)
+    _lib.lib().ellc_sim3_apply(_p(xi), _p(T), _p(out))
+    return out
 
 
 def kl_divergence(p, q):

@@ -248,6 +248,13 @@ struct ellc_ctx {
   void *consist_out_h = nullptr, *consist_out_dev_alias = nullptr;   // pinned: [cap] records (consist_finish writes them)
   void* consist_partials_d = nullptr;       // [requests of one launch][tiles of the level] partial records
   size_t consist_partials_cap = 0;          //   records it holds
+  // ellc_keyframe_sim3_step / ellc_keyframe_sim3_align: the same, of their own
+  int sim3_cap = 0;
+  int* sim3_stage_h = nullptr;
+  int* sim3_stage_d = nullptr;
+  void *sim3_out_h = nullptr, *sim3_out_dev_alias = nullptr;
+  void* sim3_partials_d = nullptr;
+  size_t sim3_partials_cap = 0;
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

@@ -1240,6 +1240,10 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   if (c->consist_stage_d) (void)hipFree(c->consist_stage_d);
   if (c->consist_stage_h) (void)hipHostFree(c->consist_stage_h);
   if (c->consist_out_h) (void)hipHostFree(c->consist_out_h);
+  if (c->sim3_partials_d) (void)hipFree(c->sim3_partials_d);
+  if (c->sim3_stage_d) (void)hipFree(c->sim3_stage_d);
+  if (c->sim3_stage_h) (void)hipHostFree(c->sim3_stage_h);
+  if (c->sim3_out_h) (void)hipHostFree(c->sim3_out_h);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
   if (c->ingest_bgr) (void)hipFree(c->ingest_bgr);
   for (int p = 0; p < ellc_ctx::SETS; p++)
@@ -2728,3 +2732,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 #include "ellc_map_impl.hpp"
 #include "ellc_render_impl.hpp"
 #include "ellc_consistency_impl.hpp"
+#include "ellc_sim3_impl.hpp"

@@ -41,6 +41,7 @@ struct RenderCand {
   int target;                // raster index in the view
   unsigned long long key;
   float z, nid, nvar;        // depth in the view, its reciprocal, the propagated variance
+  float x, y, u, v;          // the rest of the point in the view's camera and its projection, before the rounding (ellc_keyframe_sim3_step)
 };
 
 // THE rule, for all three passes: what source pixel i = (x, y) of request b with depth Z and variance V becomes in the view, or nothing.
@@ -67,6 +68,7 @@ __device__ __forceinline__ bool render_candidate(const LevelGeom& g, const Rende
   c.target = (int)vy * g.cols + (int)ux;
   c.key = ((unsigned long long)__builtin_bit_cast(uint32_t, wz) << 32) | ((unsigned long long)b << 24) | (unsigned long long)(unsigned)i;
   c.z = wz; c.nid = nid; c.nvar = nvar;
+  c.x = wx; c.y = wy; c.u = u; c.v = v;
   return true;
 }
 

@@ -1,0 +1,192 @@
+// ellc_keyframe_sim3_step: the normal equations of a seven-parameter (rotation, translation, log-scale) Gauss-Newton step between two
+// keyframe slots at a given transform (no reference counterpart: frame::calculateSim3poseOtherWrtThis, Frame.cpp:419-439, states the
+// intent only). consist_pass / consist_finish's shape: two launches, no waiting between blocks and no atomics. sim3_pass leaves one
+// partial record per (request, tile), sim3_finish sums a request's tiles. map_keep (ellc_kernels_map.hpp) decides which source pixels
+// take part, render_candidate (ellc_kernels_render.hpp) where they land and what their point in the destination's camera is.
+#pragma once
+#include <float.h>
+#include "ellc_kernels_render.hpp"
+
+namespace ellc {
+
+#define ELLC_SIM3_SUMS 37   // 28 of H's upper triangle (row-major), 7 of b, chi2_photo, chi2_depth
+
+// ellc_sim3_normal as the kernels write it; the partial record of a tile has the same layout
+struct Sim3Rec {
+  double s[ELLC_SIM3_SUMS];
+  int32_t n[6];              // n_kept, n_in_view, n_photo, n_photo_huber, n_depth, n_depth_gated
+};
+
+struct Sim3Args {
+  MapArgs m;                 // geom, kf_tab, level, max_kf, tiles and the filter: what map_keep reads (its stage is not used here)
+  const int* stage;          // [cap] source slot of every request, [cap] destination slot, [cap][12] f32 transforms (device copy of the pinned record)
+  Sim3Rec* partials;         // [requests of the launch][tiles]
+  Sim3Rec* out;              // pinned, through its device-side address: [B] records (sim3_finish)
+  int cap;                   // requests the staging holds
+  int first;                 // first request of this launch: blockIdx.y counts from it
+  float w0, sp;              // 1 / sigma_i2 and its square root, both rounded to f32 on the host
+  float huber_k, gate_k2, depth_weight;
+};
+
+// H[i][j], i <= j, in the row-major upper triangle of a 7 x 7
+__device__ __forceinline__ constexpr int sim3_h(int i, int j) { return i * 7 - (i * (i - 1)) / 2 + (j - i); }
+
+// The sums no term ever reaches: the photometric Jacobian has no entry for the log-scale (index 6), the depth Jacobian none for
+// indices 2, 3 and 4, so H[2][6], H[3][6] and H[4][6] stay the zero they start as. They are kept out of the reductions.
+__device__ __forceinline__ constexpr bool sim3_never(int k) { return k == sim3_h(2, 6) || k == sim3_h(3, 6) || k == sim3_h(4, 6); }
+
+// a += b, field by field (one rounding per double field)
+__device__ __forceinline__ void sim3_add(Sim3Rec& a, const Sim3Rec& b) {
+#pragma unroll
+  for (int k = 0; k < ELLC_SIM3_SUMS; k++)
+    if (!sim3_never(k)) a.s[k] += b.s[k];
+#pragma unroll
+  for (int k = 0; k < 6; k++) a.n[k] += b.n[k];
+}
+
+// The sum over the wave's 64 lanes, in every lane: consist_wave_sum's butterfly (lane l and lane l ^ m add the same two values, so
+// every lane ends with the same bits and the order is fixed by the lane numbers alone).
+__device__ __forceinline__ void sim3_wave_sum(Sim3Rec& r) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+#pragma unroll
+    for (int k = 0; k < ELLC_SIM3_SUMS; k++) {
+      if (!sim3_never(k)) r.s[k] += __shfl_xor(r.s[k], m, 64);
+      if (k % 8 == 7) __builtin_amdgcn_sched_barrier(0);   // eight exchanges in flight, not all 34: the received copies would double the registers
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) r.n[k] += __shfl_xor(r.n[k], m, 64);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// One term of the normal equations over the Jacobian entries idx[0..N): wJ_i = w * J_i in f32; the products of two f32 values are
+// exact in double, so the fused multiply-add rounds once, as the separate addition would.
+template <int N>
+__device__ __forceinline__ void sim3_term(Sim3Rec& a, const int (&idx)[N], const float (&J)[N], float w, float r) {
+#pragma unroll
+  for (int p = 0; p < N; p++) {
+    const float wJ = w * J[p];
+#pragma unroll
+    for (int q = p; q < N; q++) a.s[sim3_h(idx[p], idx[q])] = __builtin_fma((double)wJ, (double)J[q], a.s[sim3_h(idx[p], idx[q])]);
+    a.s[28 + idx[p]] = __builtin_fma((double)wJ, (double)r, a.s[28 + idx[p]]);
+  }
+}
+
+// grid (tiles of the level) x (requests of the launch), map_count's pixel layout: thread t of tile `local` owns pixels
+// local * ELLC_TILE + j * 256 + t and adds them in the order j = 0..7; the wave's lanes are summed by the butterfly, the four waves in
+// ascending order. The partition follows from the level's size alone.
+__global__ __launch_bounds__(256) void sim3_pass(Sim3Args a) {
+  const unsigned b = (unsigned)a.first + blockIdx.y;
+  const int src = __builtin_amdgcn_readfirstlane(a.stage[b]), dst = __builtin_amdgcn_readfirstlane(a.stage[(unsigned)a.cap + b]);
+  const KfLevelDev& S = a.m.kf_tab[a.m.level * a.m.max_kf + src];
+  const KfLevelDev& D = a.m.kf_tab[a.m.level * a.m.max_kf + dst];
+  const LevelGeom& g = a.m.geom[a.m.level];
+  const ELLC_GLOBAL float* depth = gptr(S.depth);
+  const ELLC_GLOBAL float* var = gptr(S.var);
+  const ELLC_GLOBAL uint8_t* img = gptr(S.img);
+  const ELLC_GLOBAL float* tdepth = gptr(D.depth);
+  const ELLC_GLOBAL float* tvar = gptr(D.var);
+  const ELLC_GLOBAL uint8_t* timg = gptr(D.img);
+  const int cols = g.cols, rows = g.rows, sw = g.sw;
+  const float fx = g.fx, fy = g.fy;
+  RenderT T;   // block-uniform: scalar loads
+  {
+    const float* Tp = (const float*)(a.stage + 2u * (unsigned)a.cap) + 12u * b;
+#pragma unroll
+    for (int k = 0; k < 12; k++) T.t[k] = Tp[k];
+  }
+  const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
+  Sim3Rec r;
+#pragma unroll
+  for (int k = 0; k < ELLC_SIM3_SUMS; k++) r.s[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) r.n[k] = 0;
+  const int idx_photo[6] = {0, 1, 2, 3, 4, 5}, idx_depth[4] = {0, 1, 5, 6};
+#pragma unroll 1
+  for (int j = 0; j < 8; j++) {
+    const int i = base + j * 256;
+    // A pixel without a term keeps these zeros and adds exact zeros below: the sums are those of the pixels that take part, and the
+    // accumulators are updated in ONE place, outside the branches (updated inside them, every branch edge held a copy of all of them).
+    float Jp[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rp = 0.0f, wp = 0.0f;
+    float Jd[4] = {0.0f, 0.0f, 0.0f, 0.0f}, rd = 0.0f, wd = 0.0f;
+    MapPixel p;
+    RenderCand c;
+    if (map_keep(a.m, depth, var, cols, rows, i, p)) {
+      r.n[0]++;
+      if (render_candidate(g, T, 0u, i, p.x, p.y, p.Z, p.V, c)) {   // (the request number only enters the key, which is not used here)
+        r.n[1]++;
+        // the photometric term: the four taps of the destination's image around (u, v), where they exist
+        if (c.u >= 0.0f && c.v >= 0.0f) {   // (NaN fails; u < cols and v < rows by render_candidate's bounds test, so the casts are in range)
+          const int x0 = (int)c.u, y0 = (int)c.v;
+          if (x0 + 1 < cols && y0 + 1 < rows) {
+            r.n[2]++;
+            const unsigned t0 = (unsigned)(y0 * sw + x0);
+            const float I00 = (float)timg[t0], I01 = (float)timg[t0 + 1u], I10 = (float)timg[t0 + (unsigned)sw], I11 = (float)timg[t0 + (unsigned)sw + 1u];
+            const float Is = (float)img[(unsigned)(p.y * sw + p.x)];
+            const float ax = c.u - (float)x0, ay = c.v - (float)y0;
+            const float dx0 = I01 - I00, dx1 = I11 - I10;
+            const float top = I00 + ax * dx0, bot = I10 + ax * dx1;
+            const float gy = bot - top;
+            const float Iw = top + ay * gy;
+            const float gx = dx0 + ay * (dx1 - dx0);
+            rp = Iw - Is;
+            const float A = (gx * fx) * c.nid, Bv = (gy * fy) * c.nid;
+            const float Cq = -(((A * c.x) + (Bv * c.y)) * c.nid);
+            Jp[0] = Cq * c.y - Bv * c.z; Jp[1] = A * c.z - Cq * c.x; Jp[2] = Bv * c.x - A * c.y; Jp[3] = A; Jp[4] = Bv; Jp[5] = Cq;
+            const float e = fabsf(rp) * a.sp;
+            wp = a.w0;
+            if (!(e <= a.huber_k)) {
+              wp = a.w0 * (a.huber_k / e);
+              r.n[3]++;
+            }
+          }
+        }
+        // the depth term: the target of the destination's map, where it holds a hypothesis
+        const float Zt = tdepth[(unsigned)c.target], Vt = tvar[(unsigned)c.target];   // (target < cols * rows: render_candidate's bounds test)
+        const float s = c.nvar + Vt;
+        if (map_ok(Zt, Vt) && s > 0.0f && s <= FLT_MAX) {
+          const float d = c.nid - 1.0f / Zt;
+          if (d * d <= a.gate_k2 * s) {
+            r.n[4]++;
+            rd = d;
+            wd = a.depth_weight * (1.0f / s);
+            const float a2 = c.nid * c.nid;
+            Jd[0] = -(a2 * c.y); Jd[1] = a2 * c.x; Jd[2] = -a2; Jd[3] = -c.nid;
+          } else {
+            r.n[5]++;
+          }
+        }
+      }
+    }
+    sim3_term(r, idx_photo, Jp, wp, rp);
+    r.s[35] += (double)((rp * rp) * wp);
+    sim3_term(r, idx_depth, Jd, wd, rd);
+    r.s[36] += (double)((rd * rd) * wd);
+  }
+  sim3_wave_sum(r);
+  __shared__ Sim3Rec ws[4];
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = r;
+  __syncthreads();
+  // thread k adds field k of the four waves in ascending order (one thread adding whole records would hold four of them in registers)
+  Sim3Rec& out = a.partials[blockIdx.y * (unsigned)a.m.tiles + blockIdx.x];
+  const unsigned k = threadIdx.x;
+  if (k < ELLC_SIM3_SUMS) out.s[k] = ((ws[0].s[k] + ws[1].s[k]) + ws[2].s[k]) + ws[3].s[k];
+  else if (k < ELLC_SIM3_SUMS + 6) out.n[k - ELLC_SIM3_SUMS] = ws[0].n[k - ELLC_SIM3_SUMS] + ws[1].n[k - ELLC_SIM3_SUMS] + ws[2].n[k - ELLC_SIM3_SUMS] + ws[3].n[k - ELLC_SIM3_SUMS];
+}
+
+// One wave per request of the launch: lane l adds the tiles l, l + 64, ... in ascending order, the butterfly adds the lanes: the order
+// is fixed by the number of tiles alone (consist_finish's discipline). The record goes to pinned host memory.
+__global__ __launch_bounds__(64) void sim3_finish(Sim3Args a) {
+  const Sim3Rec* part = a.partials + blockIdx.x * (unsigned)a.m.tiles;
+  Sim3Rec r;
+#pragma unroll
+  for (int k = 0; k < ELLC_SIM3_SUMS; k++) r.s[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) r.n[k] = 0;
+  for (int k = (int)threadIdx.x; k < a.m.tiles; k += 64) sim3_add(r, part[k]);
+  sim3_wave_sum(r);
+  if (threadIdx.x == 0) a.out[(unsigned)a.first + blockIdx.x] = r;
+}
+
+}  // namespace ellc

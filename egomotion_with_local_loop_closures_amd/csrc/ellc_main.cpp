@@ -28,6 +28,10 @@
 //                    batch returned, after the two maps were brought to one scale (ellc_keyframe_depth_consistency, level 0, the filter
 //                    of --map, agree_k2 1; globalOptimize::collectMatchGeometry); every other file is unchanged. With --world > 1 every
 //                    rank computes the whole batch: the ring is replicated
+// --match-sim3 PATH  (LC mode) one line per line of matchframes_globalopt.txt: "frameId kfId scale tx ty tz wx wy wz n_photo n_depth
+//                    chi2_photo chi2_depth iters" - the similarity transform from the candidate's camera into the pushed keyframe's,
+//                    refined over seven parameters from the pose the batch returned (ellc_keyframe_sim3_align;
+//                    globalOptimize::refineMatchSim3); every other file is unchanged. With --world > 1 every rank computes the whole batch
 // --map FILE         (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
 //                    level 0, no variance test, at least 3 supporting neighbours, support_k2 1, every pixel), written as binary PLY
 //                    (x y z float, intensity uchar, var float); every other file is unchanged
@@ -50,7 +54,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--map FILE] [--render FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH] [--map FILE] [--render FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -60,7 +64,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, match_geometry, map_file, render_file;
+  std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -78,6 +82,7 @@ int main(int argc, char** argv) {
     else if (a == "--comm-tcp" && i + 1 < argc) comm_port = std::atoi(argv[++i]);
     else if (a == "--match-quality" && i + 1 < argc) match_quality = argv[++i];
     else if (a == "--match-geometry" && i + 1 < argc) match_geometry = argv[++i];
+    else if (a == "--match-sim3" && i + 1 < argc) match_sim3 = argv[++i];
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
@@ -151,6 +156,11 @@ int main(int argc, char** argv) {
       globalOptimizeLoop->match_geometry_file.open(match_geometry.c_str());
       if (!globalOptimizeLoop->match_geometry_file) { std::fprintf(stderr, "cannot open %s\n", match_geometry.c_str()); return -1; }
       globalOptimizeLoop->collectMatchGeometry = true;
+    }
+    if (lc && !match_sim3.empty()) {
+      globalOptimizeLoop->match_sim3_file.open(match_sim3.c_str());
+      if (!globalOptimizeLoop->match_sim3_file) { std::fprintf(stderr, "cannot open %s\n", match_sim3.c_str()); return -1; }
+      globalOptimizeLoop->refineMatchSim3 = true;
     }
     std::vector<std::unique_ptr<frame>> frameptr_vector;
     frame* activeKeyFrame = nullptr;

@@ -1,0 +1,323 @@
+// ellc_keyframe_sim3_step, ellc_keyframe_sim3_align, ellc_sim3_solve, ellc_sim3_apply (include/ellc_abi.h): the host side of the
+// Sim(3) refinement. Included at the end of ellc_hip.hip (the library is one translation unit).
+#pragma once
+#include "ellc_context.hpp"
+#include "ellc_kernels_sim3.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+using namespace ellc;
+
+static_assert(sizeof(Sim3Rec) == sizeof(ellc_sim3_normal) && sizeof(ellc_sim3_normal) == 320 && offsetof(Sim3Rec, s) == offsetof(ellc_sim3_normal, H) &&
+                  offsetof(ellc_sim3_normal, b) == 28 * 8 && offsetof(ellc_sim3_normal, chi2_photo) == 35 * 8 &&
+                  offsetof(ellc_sim3_normal, chi2_depth) == 36 * 8 && offsetof(Sim3Rec, n) == offsetof(ellc_sim3_normal, n_kept) &&
+                  offsetof(ellc_sim3_normal, n_depth_gated) == offsetof(Sim3Rec, n) + 20,
+              "Sim3Rec mirrors ellc_sim3_normal");
+
+namespace {
+
+const int SIM3_MAX_B = 2048;
+const size_t SIM3_SCRATCH_BYTES = (size_t)32 << 20;   // partial records of one launch: a larger batch goes in several launches
+
+// what both entry points refuse, before anything is touched
+ellc_status sim3_validate(ellc_ctx* c, const char* who, int B, const int* src, const int* dst, const float* T12, int level_lo, int level_hi,
+                          const ellc_map_filter* f, const ellc_sim3_params* p) {
+  const std::string w(who);
+  if (!src || !dst || !T12 || !f || !p) return fail(c, ELLC_ERR_BAD_ARG, w + ": null pointer");
+  if (B < 1 || B > SIM3_MAX_B) return fail(c, ELLC_ERR_BAD_ARG, w + ": B out of range");
+  if (level_lo < 0 || level_hi >= c->L || level_lo > level_hi) return fail(c, ELLC_ERR_BAD_ARG, w + ": level out of range");
+  if (c->geom_h[level_lo].n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, w + ": more than 2^24 pixels on the level");
+  if (f->min_support < 0 || f->min_support > 8 || f->stride < 1 || !(f->support_k2 >= 0.0f) || !std::isfinite(f->support_k2) || std::isnan(f->max_var))
+    return fail(c, ELLC_ERR_BAD_ARG, w + ": filter out of range");
+  if (!std::isfinite(p->sigma_i2) || !std::isfinite(p->huber_k) || !std::isfinite(p->gate_k2) || !std::isfinite(p->depth_weight) ||
+      !(p->sigma_i2 > 0.0f) || !(p->huber_k > 0.0f) || !(p->gate_k2 >= 0.0f) || !(p->depth_weight >= 0.0f))
+    return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
+  for (int b = 0; b < B; b++)
+    if (!slot_ok(src[b], c->cfg.max_keyframes) || !slot_ok(dst[b], c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, w + ": slot index out of range");
+  for (int b = 0; b < B; b++)
+    if (!c->kf_has_image[src[b]] || !c->kf_has_depth[src[b]] || !c->kf_has_image[dst[b]] || !c->kf_has_depth[dst[b]])
+      return fail(c, ELLC_ERR_NOT_READY, w + ": keyframe slot lacks image or depth");
+  return ELLC_OK;
+}
+
+// One evaluation of B validated requests on `level`, behind ELLC_ENTER; synchronous. launches_ms (the diagnostic hook only): device
+// time of the launches, HIP events around them.
+ellc_status sim3_evaluate(ellc_ctx* c, int B, const int* src, const int* dst, const float* T12, int level, const ellc_map_filter* f,
+                          const ellc_sim3_params* p, ellc_sim3_normal* out, float* launches_ms) {
+  const int tiles = c->tile_begin[level + 1] - c->tile_begin[level];
+  const int per_launch = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, SIM3_SCRATCH_BYTES / ((size_t)tiles * sizeof(Sim3Rec))));
+  // (nothing of this call is in flight when its buffers grow: the call is synchronous)
+  if (B > c->sim3_cap) {
+    if (c->sim3_stage_h) (void)hipHostFree(c->sim3_stage_h);
+    if (c->sim3_out_h) (void)hipHostFree(c->sim3_out_h);
+    if (c->sim3_stage_d) (void)hipFree(c->sim3_stage_d);
+    c->sim3_stage_h = nullptr; c->sim3_out_h = nullptr; c->sim3_stage_d = nullptr; c->sim3_out_dev_alias = nullptr;
+    c->sim3_cap = 0;
+    void *sh = nullptr, *oh = nullptr, *sd = nullptr, *da = nullptr;
+    ELLC_HIP(c, hipHostMalloc(&sh, (size_t)14 * B * sizeof(int), hipHostMallocDefault));
+    c->sim3_stage_h = (int*)sh;
+    ELLC_HIP(c, hipHostMalloc(&oh, (size_t)B * sizeof(Sim3Rec), hipHostMallocDefault));
+    c->sim3_out_h = oh;
+    ELLC_HIP(c, hipMalloc(&sd, (size_t)14 * B * sizeof(int)));
+    c->sim3_stage_d = (int*)sd;
+    ELLC_HIP(c, hipHostGetDevicePointer(&da, oh, 0));
+    c->sim3_out_dev_alias = da;
+    c->sim3_cap = B;
+  }
+  const size_t need = (size_t)per_launch * tiles;
+  if (need > c->sim3_partials_cap) {
+    if (c->sim3_partials_d) (void)hipFree(c->sim3_partials_d);
+    c->sim3_partials_d = nullptr;
+    c->sim3_partials_cap = 0;
+    ELLC_HIP(c, hipMalloc(&c->sim3_partials_d, need * sizeof(Sim3Rec)));
+    c->sim3_partials_cap = need;
+  }
+  const int cap = c->sim3_cap;
+  std::memcpy(c->sim3_stage_h, src, (size_t)B * sizeof(int));
+  std::memcpy(c->sim3_stage_h + cap, dst, (size_t)B * sizeof(int));
+  std::memcpy(c->sim3_stage_h + 2 * (size_t)cap, T12, (size_t)B * 12 * sizeof(float));
+  // (requests beyond B are never read: blockIdx.y < B)
+  ELLC_HIP(c, hipMemcpyAsync(c->sim3_stage_d, c->sim3_stage_h, (size_t)14 * cap * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  Sim3Args a;
+  a.m.geom = c->geom_d;
+  a.m.kf_tab = c->kf_tab_d;
+  a.m.stage = nullptr;
+  a.m.tile_counts = nullptr;
+  a.m.tile_offsets = nullptr;
+  a.m.totals = nullptr;
+  a.m.out = nullptr;
+  a.m.out_cap = 0u;
+  a.m.level = level;
+  a.m.max_kf = c->cfg.max_keyframes;
+  a.m.tiles = tiles;
+  a.m.B = B;
+  a.m.max_var = f->max_var;
+  a.m.min_support = f->min_support;
+  a.m.support_k2 = f->support_k2;
+  a.m.stride = f->stride;
+  a.stage = c->sim3_stage_d;
+  a.partials = (Sim3Rec*)c->sim3_partials_d;
+  a.out = (Sim3Rec*)c->sim3_out_dev_alias;
+  a.cap = cap;
+  a.w0 = 1.0f / p->sigma_i2;
+  a.sp = sqrtf(a.w0);
+  a.huber_k = p->huber_k;
+  a.gate_k2 = p->gate_k2;
+  a.depth_weight = p->depth_weight;
+  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
+  for (int first = 0; first < B; first += per_launch) {   // (a record depends on its own request only: the split does not enter it)
+    const int n = std::min(per_launch, B - first);
+    a.first = first;
+    hipLaunchKernelGGL(sim3_pass, dim3(tiles, n), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(sim3_finish, dim3(n), dim3(64), 0, c->stream, a);
+  }
+  ELLC_HIP(c, hipGetLastError());
+  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  std::memcpy(out, c->sim3_out_h, (size_t)B * sizeof(Sim3Rec));
+  if (launches_ms) ELLC_HIP(c, hipEventElapsedTime(launches_ms, c->ev0, c->ev1));
+  return ELLC_OK;
+}
+
+ellc_status sim3_step_impl(ellc_ctx* c, int B, const int* src, const int* dst, const float* T12, int level, const ellc_map_filter* f,
+                           const ellc_sim3_params* p, ellc_sim3_normal* out, float* launches_ms) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  // validated first: a refused call leaves the context as it was and `out` unwritten
+  if (!out) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_sim3_step: null pointer");
+  const ellc_status s = sim3_validate(c, "ellc_keyframe_sim3_step", B, src, dst, T12, level, level, f, p);
+  if (s != ELLC_OK) return s;
+  ELLC_ENTER(c);   // behind the batches in flight, on the main stream
+  return sim3_evaluate(c, B, src, dst, T12, level, f, p, out, launches_ms);
+}
+
+// exp of the 4 x 4 generator [[w]x + sigma I, v; 0 0] in double: scaling by a power of two until the largest row sum is <= 1/4, the
+// Taylor series to the 20th power (the remainder is below 1e-30), then the squarings. The zero generator gives the identity exactly.
+void sim3_exp(const double xi[7], double M[16]) {
+  double G[16] = {xi[6], -xi[2], xi[1], xi[3], xi[2], xi[6], -xi[0], xi[4], -xi[1], xi[0], xi[6], xi[5], 0, 0, 0, 0};
+  double norm = 0.0;
+  for (int r = 0; r < 3; r++) norm = std::max(norm, std::fabs(G[4 * r]) + std::fabs(G[4 * r + 1]) + std::fabs(G[4 * r + 2]) + std::fabs(G[4 * r + 3]));
+  int squarings = 0;
+  while (norm > 0.25 && squarings < 64) { norm *= 0.5; squarings++; }
+  const double sc = std::ldexp(1.0, -squarings);
+  for (int k = 0; k < 16; k++) G[k] *= sc;
+  double term[16], next[16];
+  for (int k = 0; k < 16; k++) M[k] = term[k] = (k % 5 == 0) ? 1.0 : 0.0;
+  for (int n = 1; n <= 20; n++) {
+    for (int r = 0; r < 4; r++)
+      for (int q = 0; q < 4; q++) {
+        double s = 0.0;
+        for (int k = 0; k < 4; k++) s += term[4 * r + k] * G[4 * k + q];
+        next[4 * r + q] = s / (double)n;
+      }
+    for (int k = 0; k < 16; k++) { term[k] = next[k]; M[k] += term[k]; }
+  }
+  for (int i = 0; i < squarings; i++) {
+    for (int r = 0; r < 4; r++)
+      for (int q = 0; q < 4; q++) {
+        double s = 0.0;
+        for (int k = 0; k < 4; k++) s += M[4 * r + k] * M[4 * k + q];
+        next[4 * r + q] = s;
+      }
+    for (int k = 0; k < 16; k++) M[k] = next[k];
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+void ellc_sim3_default_params(ellc_sim3_params* p) {
+  if (!p) return;
+  p->sigma_i2 = 16.0f; p->huber_k = 1.345f; p->gate_k2 = 9.0f; p->depth_weight = 1.0f;
+}
+
+int ellc_sim3_solve(const ellc_sim3_normal* n, double* xi7) {
+  for (int i = 0; i < 7; i++) xi7[i] = 0.0;
+  double A[7][7], Lm[7][7], d[7];
+  for (int i = 0, k = 0; i < 7; i++)
+    for (int j = i; j < 7; j++, k++) A[i][j] = A[j][i] = n->H[k];
+  double big = A[0][0];
+  for (int j = 1; j < 7; j++) big = std::max(big, A[j][j]);   // (a NaN on the diagonal fails its own pivot test below)
+  const double thr = 1e-10 * big;
+  for (int j = 0; j < 7; j++) {
+    double dj = A[j][j];
+    for (int k = 0; k < j; k++) dj -= Lm[j][k] * Lm[j][k] * d[k];
+    if (!(dj > thr)) return 1;
+    d[j] = dj;
+    for (int i = j + 1; i < 7; i++) {
+      double s = A[i][j];
+      for (int k = 0; k < j; k++) s -= Lm[i][k] * Lm[j][k] * d[k];
+      Lm[i][j] = s / dj;
+    }
+  }
+  double y[7];
+  for (int i = 0; i < 7; i++) {   // L y = -b
+    double s = -n->b[i];
+    for (int k = 0; k < i; k++) s -= Lm[i][k] * y[k];
+    y[i] = s;
+  }
+  for (int i = 0; i < 7; i++) y[i] /= d[i];
+  for (int i = 6; i >= 0; i--) {   // L^T xi = y
+    double s = y[i];
+    for (int k = i + 1; k < 7; k++) s -= Lm[k][i] * y[k];
+    y[i] = s;
+  }
+  for (int i = 0; i < 7; i++) xi7[i] = y[i];
+  return 0;
+}
+
+void ellc_sim3_apply(const double* xi7, const float* T12_in, float* T12_out) {
+  double M[16];
+  sim3_exp(xi7, M);
+  float o[12];
+  for (int r = 0; r < 3; r++)
+    for (int q = 0; q < 4; q++) {
+      double s = 0.0;
+      for (int k = 0; k < 3; k++) s += M[4 * r + k] * (double)T12_in[4 * k + q];
+      if (q == 3) s += M[4 * r + 3];
+      o[4 * r + q] = (float)s;
+    }
+  std::memcpy(T12_out, o, sizeof(o));
+}
+
+ellc_status ellc_keyframe_sim3_step(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,
+                                    const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out) {
+  return sim3_step_impl(c, B, src_kf_slots, dst_kf_slots, T12, level, filter, params, out, nullptr);
+}
+
+ellc_status ellc_keyframe_sim3_align(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12_in, int level_from,
+                                     int level_to, const ellc_map_filter* filter, const ellc_sim3_params* params, int max_iter, float eps,
+                                     float* T12_out, ellc_sim3_normal* out, int* iters_out, float* trace_T12, ellc_sim3_normal* trace_rec,
+                                     int trace_capacity) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  const char* who = "ellc_keyframe_sim3_align";
+  if (!T12_out || !out) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": null pointer");
+  if (level_from < level_to) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": level_from below level_to");
+  if (max_iter < 1 || max_iter > 64) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": max_iter out of range");
+  if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": eps negative or not finite");
+  const ellc_status s = sim3_validate(c, who, B, src_kf_slots, dst_kf_slots, T12_in, level_to, level_from, filter, params);
+  if (s != ELLC_OK) return s;
+  const int n_levels = level_from - level_to + 1;
+  if ((trace_T12 || trace_rec) && trace_capacity < n_levels * max_iter + 1) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": trace_capacity too small");
+  ELLC_ENTER(c);
+  // everything of the call is kept here until it has succeeded: a failure half-way leaves the caller's arrays as they were
+  std::vector<float> T(T12_in, T12_in + (size_t)B * 12), tT;
+  std::vector<int> iters((size_t)B * n_levels, 0), n_trace((size_t)B, 0);
+  std::vector<ellc_sim3_normal> tR, rec((size_t)B);
+  if (trace_T12) tT.assign((size_t)B * trace_capacity * 12, 0.0f);
+  if (trace_rec) {
+    ellc_sim3_normal unused;
+    std::memset(&unused, 0, sizeof(unused));
+    unused.n_kept = -1;
+    tR.assign((size_t)B * trace_capacity, unused);
+  }
+  std::vector<int> active, as, ad;
+  std::vector<float> aT;
+  // one launch sequence over the pairs in `active`, its records into rec[0..active.size()) and the traces
+  auto evaluate = [&](int level) -> ellc_status {
+    const int n = (int)active.size();
+    as.resize(n); ad.resize(n); aT.resize((size_t)n * 12);
+    for (int k = 0; k < n; k++) {
+      as[k] = src_kf_slots[active[k]]; ad[k] = dst_kf_slots[active[k]];
+      std::memcpy(&aT[(size_t)k * 12], &T[(size_t)active[k] * 12], 12 * sizeof(float));
+    }
+    const ellc_status st = sim3_evaluate(c, n, as.data(), ad.data(), aT.data(), level, filter, params, rec.data(), nullptr);
+    if (st != ELLC_OK) return st;
+    for (int k = 0; k < n; k++) {
+      const int b = active[k];
+      const size_t e = (size_t)b * trace_capacity + n_trace[b];
+      if (trace_T12) std::memcpy(&tT[e * 12], &aT[(size_t)k * 12], 12 * sizeof(float));
+      if (trace_rec) tR[e] = rec[k];
+      n_trace[b]++;
+    }
+    return ELLC_OK;
+  };
+  for (int li = 0; li < n_levels; li++) {
+    const int level = level_from - li;
+    active.resize(B);
+    for (int b = 0; b < B; b++) active[b] = b;
+    while (!active.empty()) {
+      const ellc_status st = evaluate(level);
+      if (st != ELLC_OK) return st;
+      std::vector<int> still;
+      for (size_t k = 0; k < active.size(); k++) {
+        const int b = active[k];
+        double xi[7];
+        if (ellc_sim3_solve(&rec[k], xi)) continue;   // singular: no update, the pair leaves the level
+        ellc_sim3_apply(xi, &T[(size_t)b * 12], &T[(size_t)b * 12]);
+        const int made = ++iters[(size_t)b * n_levels + li];
+        double m = 0.0;
+        for (int i = 0; i < 7; i++) m = std::max(m, std::fabs(xi[i]));
+        if (m <= (double)eps || made >= max_iter) continue;
+        still.push_back(b);
+      }
+      active.swap(still);
+    }
+  }
+  active.resize(B);
+  for (int b = 0; b < B; b++) active[b] = b;
+  {
+    const ellc_status st = evaluate(level_to);
+    if (st != ELLC_OK) return st;
+  }
+  std::memcpy(out, rec.data(), (size_t)B * sizeof(ellc_sim3_normal));
+  std::memcpy(T12_out, T.data(), (size_t)B * 12 * sizeof(float));
+  if (iters_out) std::memcpy(iters_out, iters.data(), iters.size() * sizeof(int));
+  if (trace_T12) std::memcpy(trace_T12, tT.data(), tT.size() * sizeof(float));
+  if (trace_rec) std::memcpy(trace_rec, tR.data(), tR.size() * sizeof(ellc_sim3_normal));
+  return ELLC_OK;
+}
+
+#ifdef ELLC_DIAG_ABI
+ellc_status ellc_profile_sim3_step(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,
+                                   const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out, float* launches_ms) {
+  float ms = 0.0f;
+  const ellc_status s = sim3_step_impl(c, B, src_kf_slots, dst_kf_slots, T12, level, filter, params, out, &ms);
+  if (launches_ms) *launches_ms = ms;
+  return s;
+}
+#endif   // ELLC_DIAG_ABI
+
+}  // extern "C"

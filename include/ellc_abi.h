@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 14   /* ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 15   /* ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -414,6 +414,101 @@ typedef struct {
 ellc_status ellc_keyframe_depth_consistency(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots,
                                             const float* T12, int level, const ellc_map_filter* filter, float agree_k2,
                                             ellc_depth_consistency* out);
+
+/* ---- Sim(3) refinement of a loop-closure pair (v15) ----------------------------------------------------------------
+ * makeInvDepthOne rescales every keyframe's map on its own (DepthPropagation.cpp:1546-1587), so two ring keyframes never share a
+ * scale; the reference states the intent (frame::calculateSim3poseOtherWrtThis, Frame.cpp:419-439; Sim3_R, Frame.h:124) and has no
+ * implementation. ellc_keyframe_sim3_step gives the normal equations of ONE Gauss-Newton step over seven parameters, in the order
+ * (wx, wy, wz, vx, vy, vz, sigma): rotation first, as everywhere in this interface, then translation, then the log-scale.
+ * ellc_keyframe_sim3_align runs the loop. The photometric residual fixes rotation and translation, the inverse-depth residual between
+ * the two maps fixes the scale and strengthens the motion along the optical axis (alone its H is singular: no entry for wz, vx, vy).
+ *   Request b compares keyframe slot src_kf_slots[b] with slot dst_kf_slots[b] on pyramid level `level` at T = T12 + 12 * b, a
+ * row-major 3x4 f32 that takes the SOURCE's camera coordinates into the DESTINATION's, the scale folded into the 3x3 block. Source
+ * and destination may be the same slot, slots may repeat. Per source pixel, all arithmetic IEEE f32 in this order, no contraction,
+ * correctly rounded divisions:
+ *   1. it takes part iff ellc_keyframe_map_points would KEEP it under `filter` (n_kept);
+ *   2. its point P' = (x', y', z'), nid, u, v, target and nvar are ellc_keyframe_render_depth's candidate, with the same drops
+ *      (n_in_view); fx, fy are the level's intrinsics;
+ *   3. PHOTOMETRIC TERM. It takes part iff u >= 0 && v >= 0 (NaN fails) and, with x0 = (int)u, y0 = (int)v, x0 + 1 < cols &&
+ *      y0 + 1 < rows (n_photo). I00 = image(y0, x0), I01 = (y0, x0 + 1), I10 = (y0 + 1, x0), I11 = (y0 + 1, x0 + 1) of the destination
+ *      slot's level (read with its stored pitch) and Is, the source's grey value at the pixel, are converted to f32;
+ *        ax = u - (float)x0;  ay = v - (float)y0;  dx0 = I01 - I00;  dx1 = I11 - I10;
+ *        top = I00 + ax * dx0;  bot = I10 + ax * dx1;  gy = bot - top;  Iw = top + ay * gy;  gx = dx0 + ay * (dx1 - dx0);
+ *      (gx, gy are the exact derivatives of the bilinear interpolant Iw);  rp = Iw - Is;
+ *        A = (gx * fx) * nid;  Bv = (gy * fy) * nid;  Cq = -(((A * x') + (Bv * y')) * nid);
+ *        Jp = [Cq * y' - Bv * z',  A * z' - Cq * x',  Bv * x' - A * y',  A,  Bv,  Cq,  0]
+ *      (each product rounded, then the difference; the projection does not see the scale: the seventh entry is structurally zero);
+ *      w0 = 1 / sigma_i2 and sp = sqrtf(w0) are computed once on the host in f32;  e = |rp| * sp;  wp = w0 if e <= huber_k,
+ *      otherwise wp = w0 * (huber_k / e) (n_photo_huber);  chi2_photo += (double)((rp * rp) * wp);
+ *   4. DEPTH TERM. At the target pixel of the destination slot's level: Zt, Vt. It takes part iff Zt > 0 && Zt <= FLT_MAX && Vt >= 0
+ *      (v14's overlap rule; `filter` is not applied to the destination), s = nvar + Vt satisfies s > 0 && s <= FLT_MAX, and, with
+ *      rd = nid - 1 / Zt, rd * rd <= gate_k2 * s (n_depth); a pixel that fails the last test only is counted in n_depth_gated;
+ *        wd = depth_weight * (1 / s);  a2 = nid * nid;  Jd = [-(a2 * y'),  a2 * x',  0,  0,  0,  -a2,  -nid];
+ *      chi2_depth += (double)((rd * rd) * wd);
+ *   5. SUMS. For either term with weight w, residual r and Jacobian J: wJ_i = w * J_i in f32, H_ij += (double)wJ_i * (double)J_j for
+ *      i <= j, b_i += (double)wJ_i * (double)r. Both products are exact in double: every term is known exactly. A structurally zero
+ *      entry of J contributes no term (for finite values: the exact zero it would contribute), so H[2][6], H[3][6] and H[4][6] are
+ *      always 0. A step solves H xi = -b; T <- exp(xi^) * T with the generator [[w]x + sigma I, v; 0 0]. Terms that overflow f32
+ *      are the caller's business.
+ *   Record b is a function of the intrinsics, the level, the two slots' planes, T, the filter and the parameters ALONE: the pixels
+ * are partitioned by the level's size (2048-pixel tiles), partial sums are combined in a fixed order in double; B, the position in
+ * the batch, the other requests, cfg.arith, cfg.grid_batch and whatever else is in flight do not enter it.
+ *   Synchronous, ordered like every other non-batch entry point. Reads planes only: nothing that belongs to a slot is written. Its
+ * scratch and staging are its own, allocated by the first call and grown by the largest. 1 <= B <= 2048. A refused call changes
+ * nothing and writes nothing to its outputs.
+ * ELLC_ERR_BAD_ARG: the errors of ellc_keyframe_depth_consistency (B, a slot or the level out of range, more than 2^24 pixels on the
+ * level, a NULL pointer, the filter errors), a parameter that is not finite, sigma_i2 <= 0, huber_k <= 0, gate_k2 < 0,
+ * depth_weight < 0;  ELLC_ERR_NOT_READY: a source or destination slot without image or depth. */
+typedef struct {
+  float sigma_i2;      /* > 0: variance of a grey value; the photometric weight is 1 / sigma_i2 inside the Huber threshold */
+  float huber_k;       /* > 0: Huber threshold on |rp| / sigma_i */
+  float gate_k2;       /* >= 0: the depth term takes rd * rd <= gate_k2 * (nvar + Vt) only */
+  float depth_weight;  /* >= 0: factor on the depth term's weight 1 / (nvar + Vt) */
+} ellc_sim3_params;
+void ellc_sim3_default_params(ellc_sim3_params* params);   /* {16, 1.345, 9, 1} */
+
+typedef struct {
+  double  H[28];          /* upper triangle of the 7 x 7, row-major: H[0][0..6], H[1][1..6], ..., H[6][6] */
+  double  b[7];
+  double  chi2_photo;     /* sum of (double)((rp * rp) * wp) over the photometric pixels */
+  double  chi2_depth;     /* sum of (double)((rd * rd) * wd) over the depth pixels */
+  int32_t n_kept;         /* source pixels ellc_keyframe_map_points would keep under `filter` */
+  int32_t n_in_view;      /* of those, pixels with a candidate (ellc_keyframe_render_depth's rule) */
+  int32_t n_photo;        /* of those, pixels with four taps: the photometric term */
+  int32_t n_photo_huber;  /* of those, pixels beyond the Huber threshold */
+  int32_t n_depth;        /* pixels in view that enter the depth term */
+  int32_t n_depth_gated;  /* pixels in view whose target holds a hypothesis and a usable s, but beyond the gate */
+} ellc_sim3_normal;       /* 320 bytes, every field naturally aligned */
+
+ellc_status ellc_keyframe_sim3_step(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,
+                                    const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out);
+
+/* Host only, no device work (like ellc_se3_exp). ellc_sim3_solve: L D L^T in double without pivoting on the mirrored 7 x 7 of `n`,
+ * then H xi = -b. The system is singular iff some pivot fails d_i > 1e-10 * max_j H_jj (NaN fails): then xi7 is all zero and the
+ * return value is 1, otherwise 0. ellc_sim3_apply: T12_out = float(exp(xi^) * T12_in) with the generator [[w]x + sigma I, v; 0 0] -
+ * the exponential in double, then the product in double, then ONE rounding to f32 per entry; xi = 0 returns T12_in's bits. T12_out
+ * may be T12_in. */
+int  ellc_sim3_solve(const ellc_sim3_normal* n, double* xi7);
+void ellc_sim3_apply(const double* xi7, const float* T12_in, float* T12_out);
+
+/* The loop, coarse to fine over the levels level_from, level_from - 1, ..., level_to (level_from >= level_to; n_levels of them).
+ * Pair b starts at T12_in + 12 * b. Per level, every pair still ACTIVE on it is evaluated at its T (ellc_keyframe_sim3_step's
+ * record), solved on the host (ellc_sim3_solve) and updated, T <- ellc_sim3_apply(xi, T); a pair leaves the level when its solve is
+ * singular (no update, T unchanged), when max_i |xi_i| <= eps after an update, or when it has made max_iter updates on the level.
+ * Pairs that have left a level are not part of that level's later launches. After the last level one more evaluation of every pair
+ * at the T it ends with fills out[b]; that T goes to T12_out + 12 * b. iters_out[b * n_levels + k] (may be NULL) receives the updates
+ * pair b made on the k-th visited level. A pair's sequence of T's depends on nothing but its own inputs.
+ *   trace_T12 / trace_rec (each may be NULL): for pair b, entry b * trace_capacity + e receives, in order of evaluation, the T that
+ * evaluation e was made at and its record, the final one included - at most n_levels * max_iter + 1 entries; trace_capacity must be
+ * at least that when either pointer is given. The entries a pair does not use are marked: twelve zeros, and a record that is all
+ * zero but for n_kept = -1.
+ *   Synchronous; everything else as ellc_keyframe_sim3_step, whose errors it shares. Also ELLC_ERR_BAD_ARG: level_from < level_to,
+ * max_iter outside 1..64, eps negative or not finite, T12_out or out NULL, a trace_capacity too small for a given trace. A refused
+ * call writes nothing. */
+ellc_status ellc_keyframe_sim3_align(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12_in,
+                                     int level_from, int level_to, const ellc_map_filter* filter, const ellc_sim3_params* params,
+                                     int max_iter, float eps, float* T12_out, ellc_sim3_normal* out, int* iters_out,
+                                     float* trace_T12, ellc_sim3_normal* trace_rec, int trace_capacity);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

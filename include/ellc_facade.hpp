@@ -432,6 +432,24 @@ class globalOptimize {
   bool collectMatchGeometry = false;
   std::vector<MatchGeometry> lastMatchGeometry;
   std::ofstream match_geometry_file;
+  // The similarity transform between each candidate and the pushed keyframe (ellc_keyframe_sim3_align): the batch's alignment has six
+  // degrees of freedom and every keyframe's map a scale of its own, so each candidate is refined over seven - from the top three rows
+  // of exp(pose) divided by ellc_keyframe_depth_consistency's scale (level 0, the filter of ellc_main --map, agree_k2 1; 1 where that
+  // scale is not a positive finite number), coarse to fine from level 1 (where the pyramid has one) to level 0, at most 10 updates a
+  // level, eps 1e-4, the default ellc_sim3_params and the same filter. Off by default: nothing changes. On: lastMatchSim3 holds one
+  // entry per line the batch wrote to the match file, in that order - T takes the candidate's camera into the pushed keyframe's, scale
+  // is the cube root of the determinant of its 3x3 block, rec the record at T, iters the updates over all levels - and match_sim3_file
+  // (when open) gets "frameId kfId scale tx ty tz wx wy wz n_photo n_depth chi2_photo chi2_depth iters" per line, (wx, wy, wz) the
+  // rotation vector of the 3x3 block over the scale. Every rank of a sharded run computes the whole batch, as for the geometry.
+  struct MatchSim3 {
+    ellc_sim3_normal rec;
+    float T[12];
+    double scale;
+    int iters;
+  };
+  bool refineMatchSim3 = false;
+  std::vector<MatchSim3> lastMatchSim3;
+  std::ofstream match_sim3_file;
 
   static ellc_config ring_config(const ellc_config& tracking, bool fixed_grids) {
     ellc_config c = tracking;
@@ -766,6 +784,45 @@ class globalOptimize {
                    "ellc_keyframe_depth_consistency");
         for (int b = 0; b < B; b++) lastMatchGeometry[(size_t)b].rec = rec[(size_t)b];
       }
+      if (refineMatchSim3) {
+        std::vector<int> dst((size_t)B, testFrame.ring_slot);
+        std::vector<float> T((size_t)B * 12), Tout((size_t)B * 12);
+        std::vector<ellc_depth_consistency> rec((size_t)B);
+        ellc_map_filter filter;   // the filter of ellc_main --map
+        filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+        for (int b = 0; b < B; b++) {
+          float M[16];
+          ellc_se3_exp(&out[(size_t)b * 6], M);
+          for (int k = 0; k < 12; k++) T[(size_t)b * 12 + k] = M[k];
+        }
+        ring.check(ellc_keyframe_depth_consistency(ring.ctx, B, kf.data(), dst.data(), T.data(), 0, &filter, 1.0f, rec.data()),
+                   "ellc_keyframe_depth_consistency");
+        for (int b = 0; b < B; b++) {
+          double scale = rec[(size_t)b].sum_w_ss > 0.0 ? rec[(size_t)b].sum_w_st / rec[(size_t)b].sum_w_ss : 1.0;
+          if (!(scale > 0.0 && scale <= (double)FLT_MAX)) scale = 1.0;
+          for (int k = 0; k < 12; k++) T[(size_t)b * 12 + k] = (float)((double)T[(size_t)b * 12 + k] / scale);
+        }
+        ellc_sim3_params params;
+        ellc_sim3_default_params(&params);
+        const int level_from = ring.cfg.levels > 1 ? 1 : 0, n_levels = level_from + 1;
+        std::vector<ellc_sim3_normal> normal((size_t)B);
+        std::vector<int> iters((size_t)B * n_levels);
+        ring.check(ellc_keyframe_sim3_align(ring.ctx, B, kf.data(), dst.data(), T.data(), level_from, 0, &filter, &params, 10, 1e-4f, Tout.data(),
+                                            normal.data(), iters.data(), nullptr, nullptr, 0),
+                   "ellc_keyframe_sim3_align");
+        lastMatchSim3.assign((size_t)B, MatchSim3());
+        for (int b = 0; b < B; b++) {
+          MatchSim3& q = lastMatchSim3[(size_t)b];
+          q.rec = normal[(size_t)b];
+          const float* A = &Tout[(size_t)b * 12];
+          for (int k = 0; k < 12; k++) q.T[k] = A[k];
+          const double det = (double)A[0] * ((double)A[5] * A[10] - (double)A[6] * A[9]) - (double)A[1] * ((double)A[4] * A[10] - (double)A[6] * A[8]) +
+                             (double)A[2] * ((double)A[4] * A[9] - (double)A[5] * A[8]);
+          q.scale = std::cbrt(det);
+          q.iters = 0;
+          for (int l = 0; l < n_levels; l++) q.iters += iters[(size_t)b * n_levels + l];
+        }
+      }
       for (int b = 0; b < B; b++) {
         const loopFrame& m = loopFrameArray[matches[b].arrayId];
         float poseWrtOrigin[6];
@@ -783,6 +840,18 @@ class globalOptimize {
           match_quality_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << (m.frameId + rt->BATCH_START_ID - 1) << " " << q.n_depth << " "
                              << q.n_used << " " << rms << " " << wrms << "\n";
         }
+        if (refineMatchSim3 && match_sim3_file.is_open()) {
+          const MatchSim3& q = lastMatchSim3[(size_t)b];
+          float R16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, w6[6] = {0, 0, 0, 0, 0, 0};
+          if (q.scale > 0.0 && q.scale <= (double)FLT_MAX) {   // the rotation vector of the 3x3 block over the scale
+            for (int r = 0; r < 3; r++)
+              for (int k = 0; k < 3; k++) R16[4 * r + k] = (float)((double)q.T[4 * r + k] / q.scale);
+            ellc_se3_log(R16, w6);
+          }
+          match_sim3_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << (m.frameId + rt->BATCH_START_ID - 1) << " " << q.scale << " " << q.T[3]
+                          << " " << q.T[7] << " " << q.T[11] << " " << w6[0] << " " << w6[1] << " " << w6[2] << " " << q.rec.n_photo << " "
+                          << q.rec.n_depth << " " << q.rec.chi2_photo << " " << q.rec.chi2_depth << " " << q.iters << "\n";
+        }
         if (collectMatchGeometry && match_geometry_file.is_open()) {
           const MatchGeometry& q = lastMatchGeometry[(size_t)b];
           const double mean_chi2 = q.rec.n_weighted > 0 ? q.rec.sum_chi2 / (double)q.rec.n_weighted : 0.0;
@@ -794,6 +863,7 @@ class globalOptimize {
       }
       match_file.flush();
       if (match_quality_file.is_open()) match_quality_file.flush();
+      if (match_sim3_file.is_open()) match_sim3_file.flush();
       if (match_geometry_file.is_open()) match_geometry_file.flush();
     }
     // :614-641
