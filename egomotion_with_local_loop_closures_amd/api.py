@@ -380,6 +380,34 @@ class Context:
         return self._render(self._l.ellc_keyframe_render_depth, "ellc_keyframe_render_depth", (), kf_slots, T12, level, agree_k2, dst_slot,
                             max_var, min_support, support_k2, stride, out)
 
+    # ---- the maps fused in a view
+    def _fuse(self, fn, name, extra, kf_slots, T12, level, agree_k2, max_merge, dst_slot, max_var, min_support, support_k2, stride, out=None):
+        kf = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        B = kf.size
+        T = np.ascontiguousarray(T12, np.float32).reshape(B, 12)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        shp = self.level_shape(level) if 0 <= level < self.levels else (1, 1)   # (a level out of range is the library's to refuse)
+        kinds = (("depth", np.float32), ("var", np.float32), ("source", np.int32), ("agree", np.int32), ("merged", np.int32), ("intensity", np.uint8))
+        if out is None:
+            out = {k: np.zeros(shp, dt) for k, dt in kinds}
+        for k, dt in kinds:
+            assert out[k].dtype == dt and out[k].shape == shp and out[k].flags.c_contiguous, k
+        n = C.c_int(0); nf = C.c_int(0)
+        self._ck(fn(self.h, B, _p(kf), _p(T), int(level), C.byref(flt), C.c_float(agree_k2), int(max_merge), int(dst_slot), _p(out["depth"]),
+                    _p(out["var"]), _p(out["source"]), _p(out["agree"]), _p(out["merged"]), _p(out["intensity"]), C.byref(n), C.byref(nf), *extra), name)
+        out["n_valid"] = n.value
+        out["n_fused"] = nf.value
+        return out
+
+    def fuse_depth(self, kf_slots, T12, level=0, agree_k2=1.0, max_merge=64, dst_slot=-1, max_var=0.0, min_support=0, support_k2=1.0, stride=1,
+                   out=None):
+        """render_depth with the candidates that agree with a target's winner merged into it in ascending (request, raster index) order,
+        at most max_merge per target (ellc_keyframe_fuse_depth). Returns render_depth's dict with the plane merged (int32: hypotheses
+        fused into the target, the winner included) and n_fused (targets with merged >= 2) added; source, agree, intensity and n_valid
+        are the render's. dst_slot >= 0 (level 0 only) also leaves depth / var in that keyframe slot, which may be one of kf_slots."""
+        return self._fuse(self._l.ellc_keyframe_fuse_depth, "ellc_keyframe_fuse_depth", (), kf_slots, T12, level, agree_k2, max_merge, dst_slot,
+                          max_var, min_support, support_k2, stride, out)
+
     # ---- one keyframe's map against another's
     def _consistency(self, fn, name, extra, src_slots, dst_slots, Ts, level, agree_k2, max_var, min_support, support_k2, stride):
         src = np.ascontiguousarray(src_slots, np.int32).reshape(-1)
@@ -571,6 +599,17 @@ class Context:
         ms = C.c_float(0)
         out = self._render(self._l.ellc_profile_render_depth, "ellc_profile_render_depth", (C.byref(ms),), kf_slots, T12, level, agree_k2,
                            dst_slot, max_var, min_support, support_k2, stride, out)
+        out["launches_ms"] = ms.value
+        return out
+
+    def profile_fuse_depth(self, kf_slots, T12, level=0, agree_k2=1.0, max_merge=64, dst_slot=-1, max_var=0.0, min_support=0, support_k2=1.0,
+                           stride=1, out=None):
+        """fuse_depth through ellc_profile_fuse_depth: its dict plus launches_ms, the device time of the launches (the host's read of the
+        list's size lies inside it)."""
+        self._need_diag("ellc_profile_fuse_depth")
+        ms = C.c_float(0)
+        out = self._fuse(self._l.ellc_profile_fuse_depth, "ellc_profile_fuse_depth", (C.byref(ms),), kf_slots, T12, level, agree_k2, max_merge,
+                         dst_slot, max_var, min_support, support_k2, stride, out)
         out["launches_ms"] = ms.value
         return out
 

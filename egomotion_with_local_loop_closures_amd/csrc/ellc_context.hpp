@@ -241,6 +241,17 @@ struct ellc_ctx {
   uint8_t* render_intensity_d = nullptr;
   int* render_block_counts_d = nullptr;     // [ceil(W*H / 256)] targets with a winner per block of render_resolve
   int *render_nvalid_h = nullptr, *render_nvalid_dev_alias = nullptr;   // pinned: their sum (render_finish writes it)
+  // ellc_keyframe_fuse_depth: the render's scratch above (its kernels run first) and, of its own, allocated by the first call:
+  void* fuse_block_d = nullptr;             // one device allocation that holds:
+  unsigned* fuse_cursor_d = nullptr;        //   [W*H] begin, then end, of every target's segment of the list
+  int32_t* fuse_merged_d = nullptr;         //   [W*H] the merged plane
+  unsigned long long* fuse_tile_sums_d = nullptr;   // [tiles of level 0] agreeing candidates per tile
+  int* fuse_block_counts_d = nullptr;       //   [ceil(W*H / 256)] fused targets per block of fuse_merge
+  long long *fuse_totals_h = nullptr, *fuse_totals_dev_alias = nullptr;   // pinned: the list's size (fuse_offsets), n_fused (fuse_finish)
+  unsigned long long* fuse_mask_d = nullptr;   // one bit per source pixel of every request (fuse_agree): grows with the largest requests x tiles
+  size_t fuse_mask_cap = 0;                 //   words it holds
+  uint32_t* fuse_list_d = nullptr;          // the candidate ids, segment after segment: an allocation of its own that grows with the largest call
+  size_t fuse_list_cap = 0;                 //   entries it holds
   // ellc_keyframe_depth_consistency: staging and scratch of its own (not from the arena: they grow with the largest call)
   int consist_cap = 0;                      // requests the staging holds
   int* consist_stage_h = nullptr;           // pinned: [cap] source slots, [cap] destination slots, [cap][12] f32 transforms

@@ -38,6 +38,11 @@
 // --render FILE      (LC mode) at the end of the run the ring's keyframes rendered into the view of the last pushed keyframe
 //                    (globalOptimize::renderLocalMap: level 0, the filter of --map, agree_k2 1); the depth plane is written as a
 //                    little-endian PFM ("Pf", rows bottom to top, 0 where nothing landed); every other file is unchanged
+// --fuse FILE        (LC mode) the same view with the ring's agreeing hypotheses merged per target (globalOptimize::fuseLocalMap: the
+//                    filter and agree_k2 of --render, at most 64 members per target), its depth plane written as such a PFM; every
+//                    other file is unchanged. --fuse-inputs DIR (with --fuse) also writes what that view was made from, for a caller to
+//                    fuse it again through another binding: T.bin ([requests][12] f32, keyframe camera -> view camera, request order) and
+//                    slot<k>.depth / slot<k>.var (request k's level-0 planes, raw f32 rows top to bottom)
 // Input is otherwise a header-less file of W*H u8 grey frames (the decode itself always stays outside).
 // In LC mode finished keyframes go through the loop-closure ring (facade class globalOptimize): matching and the batched
 // alignment of a pushed keyframe run on a second thread and a second context beside tracking, joined at the next push
@@ -54,7 +59,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH] [--map FILE] [--render FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -64,7 +69,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file;
+  std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file, fuse_file, fuse_inputs;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -85,6 +90,8 @@ int main(int argc, char** argv) {
     else if (a == "--match-sim3" && i + 1 < argc) match_sim3 = argv[++i];
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
+    else if (a == "--fuse" && i + 1 < argc) fuse_file = argv[++i];
+    else if (a == "--fuse-inputs" && i + 1 < argc) fuse_inputs = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return -1; }
   }
@@ -237,6 +244,31 @@ int main(int argc, char** argv) {
       RenderedView view;
       globalOptimizeLoop->renderLocalMap(globalOptimizeLoop->loopFrameArray[globalOptimizeLoop->lastPushedArrayId].poseWrtWorld, 0, filter, 1.0f, nullptr, view);
       write_pfm(render_file, view.depth, view.cols, view.rows);
+    }
+    if (globalOptimizeLoop && !fuse_file.empty()) {
+      if (globalOptimizeLoop->lastPushedArrayId < 0) throw std::runtime_error("--fuse: no keyframe was pushed into the ring");
+      ellc_map_filter filter;
+      filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+      FusedView view;
+      globalOptimizeLoop->fuseLocalMap(globalOptimizeLoop->loopFrameArray[globalOptimizeLoop->lastPushedArrayId].poseWrtWorld, 0, filter, 1.0f,
+                                       ELLC_FUSE_MAX_MERGE, nullptr, view);
+      write_pfm(fuse_file, view.depth, view.cols, view.rows);
+      if (!fuse_inputs.empty()) {
+        auto dump = [](const std::string& path, const void* p, size_t bytes) {
+          std::ofstream f(path, std::ios::binary);
+          f.write((const char*)p, (std::streamsize)bytes);
+          if (!f) throw std::runtime_error("--fuse-inputs: cannot write " + path);
+        };
+        const size_t n = (size_t)view.cols * view.rows;
+        std::vector<float> d(n), v(n);
+        dump(fuse_inputs + "/T.bin", view.T.data(), view.T.size() * sizeof(float));
+        for (size_t k = 0; k < view.slots.size(); k++) {
+          globalOptimizeLoop->ring.check(ellc_keyframe_get_depth_level(globalOptimizeLoop->ring.ctx, view.slots[k], 0, d.data(), v.data()),
+                                         "ellc_keyframe_get_depth_level");
+          dump(fuse_inputs + "/slot" + std::to_string(k) + ".depth", d.data(), n * sizeof(float));
+          dump(fuse_inputs + "/slot" + std::to_string(k) + ".var", v.data(), n * sizeof(float));
+        }
+      }
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "ellc_main: %s\n", e.what());

@@ -10,30 +10,9 @@ using namespace ellc;
 
 namespace {
 
-// launches_ms (the diagnostic hook only): device time from the preset of the keys to the end of render_agree, HIP events around them
-ellc_status render_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* f, float agree_k2,
-                              int dst, float* depth, float* var, int32_t* source, int32_t* agree, uint8_t* intensity, int* n_valid,
-                              float* launches_ms) {
-  if (!c) return ELLC_ERR_BAD_ARG;
-  // validated first: a refused call leaves the context and every slot as they were
-  if (!kf_slots || !T12 || !f) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: null pointer");
-  if (B < 1 || B > c->cfg.max_keyframes || B > 256) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: B out of range");
-  if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: level out of range");
-  const LevelGeom& g = c->geom_h[level];
-  if (g.n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: more than 2^24 pixels on the level");
-  if (f->min_support < 0 || f->min_support > 8 || f->stride < 1 || !(f->support_k2 >= 0.0f) || !std::isfinite(f->support_k2) || std::isnan(f->max_var))
-    return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: filter out of range");
-  if (!(agree_k2 >= 0.0f) || !std::isfinite(agree_k2)) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: agree_k2 negative or not finite");
-  if (dst < -1 || dst >= c->cfg.max_keyframes) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: destination slot out of range");
-  if (dst >= 0 && level != 0) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: a destination slot takes level 0 only");
-  for (int b = 0; b < B; b++)
-    if (!slot_ok(kf_slots[b], c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: slot index out of range");
-  for (int b = 0; b < B; b++)
-    if (kf_slots[b] == dst) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_render_depth: the destination slot is also a source");
-  for (int b = 0; b < B; b++)
-    if (!c->kf_has_image[kf_slots[b]] || !c->kf_has_depth[kf_slots[b]])
-      return fail(c, ELLC_ERR_NOT_READY, "ellc_keyframe_render_depth: keyframe slot lacks image or depth");
-  ELLC_ENTER(c);   // behind the batches in flight, on the main stream
+// the render's scratch, allocated by the first call that needs it (ellc_keyframe_fuse_depth runs the render's kernels on it too: both
+// calls are synchronous)
+ellc_status render_scratch(ellc_ctx* c) {
   const int MK = c->cfg.max_keyframes;
   const size_t n0 = (size_t)c->geom_h[0].n;
   const size_t blocks0 = (n0 + 255) / 256;
@@ -64,9 +43,21 @@ ellc_status render_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const flo
     c->render_nvalid_dev_alias = (int*)da;
     c->render_nvalid_h = nh;
   }
+  return ELLC_OK;
+}
+
+// the requests' slots and transforms, staged and on their way to the device
+ellc_status render_stage(ellc_ctx* c, int B, const int* kf_slots, const float* T12) {
+  const int MK = c->cfg.max_keyframes;
   for (int b = 0; b < B; b++) c->render_stage_h[b] = kf_slots[b];
   std::memcpy(c->render_stage_h + MK, T12, (size_t)B * 12 * sizeof(float));
   ELLC_HIP(c, hipMemcpyAsync(c->render_stage_d, c->render_stage_h, (size_t)13 * MK * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  return ELLC_OK;
+}
+
+RenderArgs render_args(ellc_ctx* c, int B, int level, const ellc_map_filter* f, float agree_k2) {
+  const int MK = c->cfg.max_keyframes;
+  const LevelGeom& g = c->geom_h[level];
   const size_t n = (size_t)g.n;
   RenderArgs a;
   a.m.geom = c->geom_d;
@@ -96,6 +87,47 @@ ellc_status render_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const flo
   a.n = g.n;
   a.blocks = (int)((n + 255) / 256);
   a.agree_k2 = agree_k2;
+  return a;
+}
+
+// What ellc_keyframe_render_depth and ellc_keyframe_fuse_depth refuse alike (the fusion accepts a destination among its sources).
+// Validated first: a refused call leaves the context and every slot as they were (the message is composed only when a call is refused)
+ellc_status render_validate(ellc_ctx* c, const char* who, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* f,
+                            float agree_k2, int dst, bool dst_may_be_source) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  if (!kf_slots || !T12 || !f) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": null pointer");
+  if (B < 1 || B > c->cfg.max_keyframes || B > 256) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": B out of range");
+  if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": level out of range");
+  const LevelGeom& g = c->geom_h[level];
+  if (g.n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": more than 2^24 pixels on the level");
+  if (f->min_support < 0 || f->min_support > 8 || f->stride < 1 || !(f->support_k2 >= 0.0f) || !std::isfinite(f->support_k2) || std::isnan(f->max_var))
+    return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": filter out of range");
+  if (!(agree_k2 >= 0.0f) || !std::isfinite(agree_k2)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": agree_k2 negative or not finite");
+  if (dst < -1 || dst >= c->cfg.max_keyframes) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": destination slot out of range");
+  if (dst >= 0 && level != 0) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": a destination slot takes level 0 only");
+  for (int b = 0; b < B; b++)
+    if (!slot_ok(kf_slots[b], c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": slot index out of range");
+  for (int b = 0; b < B && !dst_may_be_source; b++)
+    if (kf_slots[b] == dst) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": the destination slot is also a source");
+  for (int b = 0; b < B; b++)
+    if (!c->kf_has_image[kf_slots[b]] || !c->kf_has_depth[kf_slots[b]])
+      return fail(c, ELLC_ERR_NOT_READY, std::string(who) + ": keyframe slot lacks image or depth");
+  return ELLC_OK;
+}
+
+// launches_ms (the diagnostic hook only): device time from the preset of the keys to the end of render_agree, HIP events around them
+ellc_status render_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* f, float agree_k2,
+                              int dst, float* depth, float* var, int32_t* source, int32_t* agree, uint8_t* intensity, int* n_valid,
+                              float* launches_ms) {
+  const ellc_status ok = render_validate(c, "ellc_keyframe_render_depth", B, kf_slots, T12, level, f, agree_k2, dst, false);
+  if (ok != ELLC_OK) return ok;
+  const LevelGeom& g = c->geom_h[level];
+  ELLC_ENTER(c);   // behind the batches in flight, on the main stream
+  ellc_status st = render_scratch(c);
+  if (st == ELLC_OK) st = render_stage(c, B, kf_slots, T12);
+  if (st != ELLC_OK) return st;
+  const size_t n0 = (size_t)c->geom_h[0].n, n = (size_t)g.n;
+  const RenderArgs a = render_args(c, B, level, f, agree_k2);
   const dim3 grd(a.m.tiles, B), blk(256);
   if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
   ELLC_HIP(c, hipMemsetAsync(c->render_keys_d, 0xff, n * 8, c->stream));

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 15   /* ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 16   /* ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -369,6 +369,48 @@ ellc_status ellc_keyframe_render_depth(ellc_ctx* ctx, int B, const int* kf_slots
                                        const ellc_map_filter* filter, float agree_k2, int dst_kf_slot,
                                        float* depth, float* var, int32_t* source, int32_t* agree, uint8_t* intensity,
                                        int* n_valid);
+
+/* ---- the maps fused in a view (v16) ---------------------------------------------------------------------------
+ * ellc_keyframe_render_depth with the candidates that agree with a target's winner MERGED into it: the EKF-style merge the reference
+ * applies when it propagates a map (DepthPropagation.cpp:1124-1148, behind the occlusion test of :1090-1107), in a fixed order, so
+ * that the result stays a function of the inputs alone. The arguments are the render's, with max_merge (0 .. ELLC_FUSE_MAX_MERGE), the
+ * `merged` plane and n_fused added. Once a loop closure's Sim(3) is known, this is how the candidates' hypotheses tighten a keyframe's map.
+ *   1. Candidates and winner. A kept source pixel, its candidate (target, z', nid, nvar) and the winner of a target are exactly
+ *      ellc_keyframe_render_depth's: for the same arguments source, agree, intensity and *n_valid are byte for byte the render's.
+ *   2. Members. The MEMBERS of a target are its candidates other than the winner that agree with the winner in the render's sense: with
+ *      d = nid - nid_w, d * d <= agree_k2 * (nvar + nvar_w), taken against the winner's own, unmerged values (membership does not depend
+ *      on the merge). Members are ordered by ascending 32-bit id (b << 24) | i: the request first, then the source's raster index. Only
+ *      the first max_merge members in that order are VISITED; agree - 1 > max_merge tells a caller that a target was truncated.
+ *   3. Merge. All IEEE f32 in this order, no contraction, correctly rounded divisions (:1128, :1129, :1139). The state starts at
+ *      id_t = nid_w, var_t = nvar_w, m = 1. For each visited member (nid, nvar):  s = var_t + nvar;  a member with
+ *      !(s > 0 && s <= FLT_MAX) is skipped: it changes nothing and is not counted;  otherwise  w = nvar / s;
+ *      id_t = (w * id_t) + ((1.0f - w) * nid);  var_t = 1.0f / ((1.0f / var_t) + (1.0f / nvar)) with the old var_t;  m += 1.
+ *      A zero variance on one side goes through IEEE infinities to a fused variance of 0.
+ *   4. Outputs: host pointers, dense cols x rows of the level, each may be NULL, as the render's, and
+ *        merged     m                                                  0 without a winner
+ *      (a target has a winner iff its depth is > 0; source is a negative int32 from request 128 on, as in the render)
+ *      Where m == 1, depth and var are the winner's z' and nvar, bit for bit the render's; where m >= 2, depth = 1.0f / id_t and
+ *      var = var_t (a fused inverse depth so small that its reciprocal overflows f32 is the caller's business; no NaN can arise:
+ *      0 <= w <= 1 and every term is non-negative). Targets without a winner hold 0 / -1 / -1 / 0 / 0 / 0. *n_fused (may be NULL)
+ *      receives the number of targets with merged >= 2. With max_merge == 0 the call returns the render's five planes, byte for byte.
+ *   5. A result is a function of the intrinsics, the level, the slots' three planes, the T's, the filter, agree_k2 and max_merge
+ *      ALONE: cfg.arith, cfg.grid_batch, whatever else is in flight and the order candidates arrive in do not enter it, and a second
+ *      call gives the same bytes (no floating-point atomics: every target merges its members itself, in the order above).
+ *   6. dst_kf_slot as in the render (level 0 only, -1 for none: afterwards the slot is what ellc_keyframe_set_depth with the returned
+ *      depth and var would leave), with one difference: the destination MAY be one of the sources. Fusing loop-closure candidates into
+ *      a keyframe's own map is the main use: request 0 is the keyframe itself at the identity, the others are the candidates at their
+ *      refined Sim(3). Every kernel has read the slots before the planes are copied into the destination, in stream order.
+ *   7. Synchronous, ordered like every other non-batch entry point; a refused call changes nothing. Its scratch (the render's, and of its own a
+ *      bit per source pixel of every request and a list of 4 bytes per agreeing candidate) is allocated by the first call and grown by
+ *      the largest.
+ * ELLC_ERR_BAD_ARG, ELLC_ERR_NOT_READY: as ellc_keyframe_render_depth, except that a destination among the sources is no error; also
+ * ELLC_ERR_BAD_ARG for max_merge outside 0 .. ELLC_FUSE_MAX_MERGE;
+ * ELLC_ERR_CAPACITY: the candidates that agree (the sum of the agree plane) exceed 2^31 - 1; nothing has been changed. */
+#define ELLC_FUSE_MAX_MERGE 64
+ellc_status ellc_keyframe_fuse_depth(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, int level,
+                                     const ellc_map_filter* filter, float agree_k2, int max_merge, int dst_kf_slot,
+                                     float* depth, float* var, int32_t* source, int32_t* agree, int32_t* merged,
+                                     uint8_t* intensity, int* n_valid, int* n_fused);
 
 /* ---- one keyframe's map against another's (v14) ------------------------------------------------------------------
  * The geometric check of a loop closure, and the scale between two maps: request b compares keyframe slot src_kf_slots[b] with slot

@@ -37,6 +37,14 @@ ellc_status ellc_profile_render_depth(ellc_ctx* ctx, int B, const int* kf_slots,
                                       float agree_k2, int dst_kf_slot, float* depth, float* var, int32_t* source, int32_t* agree,
                                       uint8_t* intensity, int* n_valid, float* launches_ms);
 
+/* ellc_keyframe_fuse_depth with HIP events around its launches (the preset of the keys, render_min, render_resolve, render_finish,
+ * fuse_agree, fuse_tile_sums, fuse_offsets, fuse_scatter, fuse_merge, fuse_finish): launches_ms receives the device time from the first to the end of the last,
+ * without the copies that follow. The host's read of the list's size behind fuse_offsets - one synchronisation, and the list's growth
+ * when it has to grow - lies INSIDE that window: it is part of what the call costs. Everything else as the product call. */
+ellc_status ellc_profile_fuse_depth(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* filter,
+                                    float agree_k2, int max_merge, int dst_kf_slot, float* depth, float* var, int32_t* source, int32_t* agree,
+                                    int32_t* merged, uint8_t* intensity, int* n_valid, int* n_fused, float* launches_ms);
+
 /* ellc_keyframe_depth_consistency with HIP events around its launches (consist_pass, consist_finish): launches_ms receives their
  * device time, without the staging copy in front. Everything else as the product call. */
 ellc_status ellc_profile_depth_consistency(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,

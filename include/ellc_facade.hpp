@@ -381,6 +381,12 @@ struct RenderedView {
   std::vector<int32_t> source, agree;
   std::vector<uint8_t> intensity;
 };
+// What globalOptimize::fuseLocalMap returns: the view of ellc_keyframe_fuse_depth — a RenderedView whose depth and var hold the merged
+// hypothesis where candidates agreed with the winner — with the merged plane, the number of targets that fused and the bound it was made with.
+struct FusedView : RenderedView {
+  int n_fused = 0, max_merge = 0;
+  std::vector<int32_t> merged;    // hypotheses fused into the target, the winner included (0: no winner)
+};
 
 class globalOptimize {
  public:
@@ -597,11 +603,9 @@ class globalOptimize {
       for (int c = 0; c < 4; c++)
         T12[4 * r + c] = ((V[4 * r] * M[c] + V[4 * r + 1] * M[4 + c]) + V[4 * r + 2] * M[8 + c]) + (c == 3 ? V[4 * r + 3] : 0.0f);
   }
-  void renderLocalMap(const float* viewPoseWrtWorld, int level, const ellc_map_filter& filter, float agree_k2, frame* into, RenderedView& out) {
-    join_all();
-    if (level < 0 || level >= ring.cfg.levels) throw std::runtime_error("renderLocalMap: level out of range");
-    if (into && (level != 0 || into->kf_slot < 0)) throw std::runtime_error("renderLocalMap: the destination must be a keyframe and the level 0");
-    out = RenderedView();
+  // the requests of a view (every valid, non-stray ring entry in ring-array order) and its planes, empty: what renderLocalMap and
+  // fuseLocalMap hand the library
+  void viewRequests(const float* viewPoseWrtWorld, int level, RenderedView& out) {
     out.cols = ring.cfg.width >> level;
     out.rows = ring.cfg.height >> level;
     for (int i = 0; i < MAX_LOOP_ARRAY_LENGTH_SCALE_AVG; i++) {
@@ -618,10 +622,35 @@ class globalOptimize {
     out.source.assign(n, -1);
     out.agree.assign(n, 0);
     out.intensity.assign(n, 0);
+  }
+  void renderLocalMap(const float* viewPoseWrtWorld, int level, const ellc_map_filter& filter, float agree_k2, frame* into, RenderedView& out) {
+    join_all();
+    if (level < 0 || level >= ring.cfg.levels) throw std::runtime_error("renderLocalMap: level out of range");
+    if (into && (level != 0 || into->kf_slot < 0)) throw std::runtime_error("renderLocalMap: the destination must be a keyframe and the level 0");
+    out = RenderedView();
+    viewRequests(viewPoseWrtWorld, level, out);
     if (!out.ids.empty())
       ring.check(ellc_keyframe_render_depth(ring.ctx, (int)out.ids.size(), out.slots.data(), out.T.data(), level, &filter, agree_k2, -1, out.depth.data(),
                                             out.var.data(), out.source.data(), out.agree.data(), out.intensity.data(), &out.n_valid),
                  "ellc_keyframe_render_depth");
+    if (into) rt->check(ellc_keyframe_set_depth(rt->ctx, into->kf_slot, out.depth.data(), out.var.data()), "ellc_keyframe_set_depth");
+  }
+  // renderLocalMap with the candidates that agree with a target's winner merged into it (ellc_keyframe_fuse_depth): what the ring's
+  // keyframes TOGETHER say about the surfaces the view sees, each target fused from at most max_merge agreeing candidates in ring-array
+  // order. Requests, transforms, filter, agree_k2 and `into` as renderLocalMap.
+  void fuseLocalMap(const float* viewPoseWrtWorld, int level, const ellc_map_filter& filter, float agree_k2, int max_merge, frame* into, FusedView& out) {
+    join_all();
+    if (level < 0 || level >= ring.cfg.levels) throw std::runtime_error("fuseLocalMap: level out of range");
+    if (into && (level != 0 || into->kf_slot < 0)) throw std::runtime_error("fuseLocalMap: the destination must be a keyframe and the level 0");
+    out = FusedView();
+    viewRequests(viewPoseWrtWorld, level, out);
+    out.max_merge = max_merge;
+    out.merged.assign(out.depth.size(), 0);
+    if (!out.ids.empty())
+      ring.check(ellc_keyframe_fuse_depth(ring.ctx, (int)out.ids.size(), out.slots.data(), out.T.data(), level, &filter, agree_k2, max_merge, -1,
+                                          out.depth.data(), out.var.data(), out.source.data(), out.agree.data(), out.merged.data(), out.intensity.data(),
+                                          &out.n_valid, &out.n_fused),
+                 "ellc_keyframe_fuse_depth");
     if (into) rt->check(ellc_keyframe_set_depth(rt->ctx, into->kf_slot, out.depth.data(), out.var.data()), "ellc_keyframe_set_depth");
   }
   int lastPushedArrayId = -1;   // the ring entry of the most recent pushToArray
