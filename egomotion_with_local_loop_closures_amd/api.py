@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -408,6 +408,26 @@ class Context:
         return self._fuse(self._l.ellc_keyframe_fuse_depth, "ellc_keyframe_fuse_depth", (), kf_slots, T12, level, agree_k2, max_merge, dst_slot,
                           max_var, min_support, support_k2, stride, out)
 
+    # ---- keyframe maps folded into the live depth map
+    def _absorb(self, fn, name, extra, kf_slots, T12, params, max_var, min_support, support_k2, stride, stats):
+        kf = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+        B = kf.size
+        T = np.ascontiguousarray(T12, np.float32).reshape(B, 12)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        prm = params if isinstance(params, EllcAbsorbParams) else absorb_params(**(params or {}))
+        st = stats if stats is not None else EllcAbsorbStats()
+        self._ck(fn(self.h, B, _p(kf), _p(T), C.byref(flt), C.byref(prm), C.byref(st), *extra), name)
+        return {k: int(getattr(st, k)) for k in ABSORB_STATS_FIELDS}
+
+    def depth_absorb(self, kf_slots, T12, params=None, max_var=0.0, min_support=0, support_k2=1.0, stride=1, stats=None):
+        """The maps of keyframe slots kf_slots[b] (level 0) folded into the context's live depth map (ellc_depth_absorb_keyframes):
+        T12[b] is the row-major 3x4 transform from that slot's camera into the depth map's keyframe's, the filter is map_points'.
+        params: dict of agree_k2, max_fold, photo_gate, src_validity, finalise (defaults 1, 64, 1, 20, 1) or an EllcAbsorbParams.
+        Returns the sixteen counts of ellc_absorb_stats as a dict (stats: an EllcAbsorbStats to receive them as well). With
+        finalise=0 the caller must regularise (depth_do_regularization) before anything observes or exports the map."""
+        return self._absorb(self._l.ellc_depth_absorb_keyframes, "ellc_depth_absorb_keyframes", (), kf_slots, T12, params, max_var, min_support,
+                            support_k2, stride, stats)
+
     # ---- one keyframe's map against another's
     def _consistency(self, fn, name, extra, src_slots, dst_slots, Ts, level, agree_k2, max_var, min_support, support_k2, stride):
         src = np.ascontiguousarray(src_slots, np.int32).reshape(-1)
@@ -613,6 +633,16 @@ class Context:
         out["launches_ms"] = ms.value
         return out
 
+    def profile_depth_absorb(self, kf_slots, T12, params=None, max_var=0.0, min_support=0, support_k2=1.0, stride=1, stats=None):
+        """depth_absorb through ellc_profile_depth_absorb: its dict plus launches_ms, the device time of the fold's launches (the host's
+        read of the list's size lies inside it; finalise's launches do not)."""
+        self._need_diag("ellc_profile_depth_absorb")
+        ms = C.c_float(0)
+        out = self._absorb(self._l.ellc_profile_depth_absorb, "ellc_profile_depth_absorb", (C.byref(ms),), kf_slots, T12, params, max_var,
+                           min_support, support_k2, stride, stats)
+        out["launches_ms"] = ms.value
+        return out
+
     def profile_depth_consistency(self, src_slots, dst_slots, Ts, level=0, agree_k2=1.0, max_var=0.0, min_support=0, support_k2=1.0, stride=1):
         """depth_consistency through ellc_profile_depth_consistency: (records, launches_ms), the device time of the launches."""
         self._need_diag("ellc_profile_depth_consistency")
@@ -703,6 +733,16 @@ def sim3_params(sigma_i2=None, huber_k=None, gate_k2=None, depth_weight=None):
     p = EllcSim3Params()
     _lib.lib().ellc_sim3_default_params(C.byref(p))
     for k, v in (("sigma_i2", sigma_i2), ("huber_k", huber_k), ("gate_k2", gate_k2), ("depth_weight", depth_weight)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def absorb_params(agree_k2=None, max_fold=None, photo_gate=None, src_validity=None, finalise=None):
+    """ellc_absorb_params: the library's defaults (ellc_absorb_default_params) with the given fields replaced."""
+    p = EllcAbsorbParams()
+    _lib.lib().ellc_absorb_default_params(C.byref(p))
+    for k, v in (("agree_k2", agree_k2), ("max_fold", max_fold), ("photo_gate", photo_gate), ("src_validity", src_validity), ("finalise", finalise)):
         if v is not None:
             setattr(p, k, v)
     return p

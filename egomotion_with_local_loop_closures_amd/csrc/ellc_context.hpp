@@ -252,6 +252,9 @@ struct ellc_ctx {
   size_t fuse_mask_cap = 0;                 //   words it holds
   uint32_t* fuse_list_d = nullptr;          // the candidate ids, segment after segment: an allocation of its own that grows with the largest call
   size_t fuse_list_cap = 0;                 //   entries it holds
+  // ellc_depth_absorb_keyframes: the render's and the fusion's scratch above and, of its own, allocated by the first call:
+  void* absorb_block_d = nullptr;           // [64] words for absorb_mark's four counts, then [ceil(W*H / 256)][11] outcome counts per block of absorb_fold
+  int32_t *absorb_stats_h = nullptr, *absorb_stats_dev_alias = nullptr;   // pinned: the sixteen words of ellc_absorb_stats (absorb_finish)
   // ellc_keyframe_depth_consistency: staging and scratch of its own (not from the arena: they grow with the largest call)
   int consist_cap = 0;                      // requests the staging holds
   int* consist_stage_h = nullptr;           // pinned: [cap] source slots, [cap] destination slots, [cap][12] f32 transforms

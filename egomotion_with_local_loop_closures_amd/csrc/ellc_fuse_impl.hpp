@@ -9,20 +9,9 @@ using namespace ellc;
 
 namespace {
 
-// launches_ms (the diagnostic hook only): device time from the preset of the keys to the end of fuse_finish, HIP events around them. The
-// host's read of the list's size (one synchronisation, and the list's growth when it has to grow) lies inside that window.
-ellc_status fuse_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* f, float agree_k2,
-                            int max_merge, int dst, float* depth, float* var, int32_t* source, int32_t* agree, int32_t* merged,
-                            uint8_t* intensity, int* n_valid, int* n_fused, float* launches_ms) {
-  // the destination may be one of the sources: every kernel has read the slots before the copies into the destination, in stream order
-  const ellc_status ok = render_validate(c, "ellc_keyframe_fuse_depth", B, kf_slots, T12, level, f, agree_k2, dst, true);
-  if (ok != ELLC_OK) return ok;
-  if (max_merge < 0 || max_merge > ELLC_FUSE_MAX_MERGE) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_fuse_depth: max_merge out of range");
-  const LevelGeom& g = c->geom_h[level];
-  ELLC_ENTER(c);   // behind the batches in flight, on the main stream
-  ellc_status st = render_scratch(c);
-  if (st != ELLC_OK) return st;
-  const size_t n0 = (size_t)c->geom_h[0].n, n = (size_t)g.n;
+// the fusion's scratch of its own, allocated by the first call that needs it (ellc_depth_absorb_keyframes uses it too: both calls are synchronous)
+ellc_status fuse_scratch(ellc_ctx* c) {
+  const size_t n0 = (size_t)c->geom_h[0].n;
   if (!c->fuse_totals_h) {
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t tiles0 = (size_t)(c->tile_begin[1] - c->tile_begin[0]), blocks0 = (n0 + 255) / 256;
@@ -37,23 +26,60 @@ ellc_status fuse_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float
       c->fuse_block_counts_d = (int*)(p + o_counts);
     }
     long long* th = nullptr;
-    st = host_alloc(c, &th, 2);
+    const ellc_status st = host_alloc(c, &th, 2);
     if (st != ELLC_OK) return st;
     void* da = nullptr;
     ELLC_HIP(c, hipHostGetDevicePointer(&da, th, 0));
     c->fuse_totals_dev_alias = (long long*)da;
     c->fuse_totals_h = th;
   }
-  FuseArgs a;
-  a.r = render_args(c, B, level, f, agree_k2);
-  const size_t mask_words = (size_t)B * (size_t)a.r.m.tiles * 32;   // 8 steps x 4 waves per (request, tile)
-  if (max_merge > 0 && mask_words > c->fuse_mask_cap) {   // (grown in front of the call's first enqueue; hipFree waits for what still reads the old one)
+  return ELLC_OK;
+}
+
+// the bit per source pixel of every request: grown in front of a call's first enqueue (hipFree waits for what still reads the old one)
+ellc_status fuse_mask_reserve(ellc_ctx* c, size_t mask_words) {
+  if (mask_words > c->fuse_mask_cap) {
     if (c->fuse_mask_d) (void)hipFree(c->fuse_mask_d);
     c->fuse_mask_d = nullptr;
     c->fuse_mask_cap = 0;
     ELLC_HIP(c, hipMalloc(&c->fuse_mask_d, mask_words * sizeof(unsigned long long)));
     c->fuse_mask_cap = mask_words;
   }
+  return ELLC_OK;
+}
+
+// the list of candidate ids: grown once the call's total is known (nothing of this context is running: the stream was synchronised)
+ellc_status fuse_list_reserve(ellc_ctx* c, size_t total) {
+  if (total > c->fuse_list_cap) {
+    if (c->fuse_list_d) (void)hipFree(c->fuse_list_d);
+    c->fuse_list_d = nullptr;
+    c->fuse_list_cap = 0;
+    const size_t cap = total + total / 2;   // headroom: totals that creep up from call to call do not allocate every time
+    ELLC_HIP(c, hipMalloc(&c->fuse_list_d, cap * sizeof(uint32_t)));
+    c->fuse_list_cap = cap;
+  }
+  return ELLC_OK;
+}
+
+// launches_ms (the diagnostic hook only): device time from the preset of the keys to the end of fuse_finish, HIP events around them. The
+// host's read of the list's size (one synchronisation, and the list's growth when it has to grow) lies inside that window.
+ellc_status fuse_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* f, float agree_k2,
+                            int max_merge, int dst, float* depth, float* var, int32_t* source, int32_t* agree, int32_t* merged,
+                            uint8_t* intensity, int* n_valid, int* n_fused, float* launches_ms) {
+  // the destination may be one of the sources: every kernel has read the slots before the copies into the destination, in stream order
+  const ellc_status ok = render_validate(c, "ellc_keyframe_fuse_depth", B, kf_slots, T12, level, f, agree_k2, dst, true);
+  if (ok != ELLC_OK) return ok;
+  if (max_merge < 0 || max_merge > ELLC_FUSE_MAX_MERGE) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_fuse_depth: max_merge out of range");
+  const LevelGeom& g = c->geom_h[level];
+  ELLC_ENTER(c);   // behind the batches in flight, on the main stream
+  ellc_status st = render_scratch(c);
+  if (st != ELLC_OK) return st;
+  const size_t n0 = (size_t)c->geom_h[0].n, n = (size_t)g.n;
+  if ((st = fuse_scratch(c)) != ELLC_OK) return st;
+  FuseArgs a;
+  a.r = render_args(c, B, level, f, agree_k2);
+  const size_t mask_words = (size_t)B * (size_t)a.r.m.tiles * 32;   // 8 steps x 4 waves per (request, tile)
+  if (max_merge > 0 && (st = fuse_mask_reserve(c, mask_words)) != ELLC_OK) return st;
   st = render_stage(c, B, kf_slots, T12);
   if (st != ELLC_OK) return st;
   a.mask = c->fuse_mask_d;
@@ -81,14 +107,7 @@ ellc_status fuse_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float
     const long long total = c->fuse_totals_h[0];
     // nothing of a slot has been touched yet
     if (total > (long long)INT_MAX) return fail(c, ELLC_ERR_CAPACITY, "ellc_keyframe_fuse_depth: more than 2^31 - 1 agreeing candidates");
-    if ((size_t)total > c->fuse_list_cap) {   // (nothing of this context is running: the stream was synchronised above)
-      if (c->fuse_list_d) (void)hipFree(c->fuse_list_d);
-      c->fuse_list_d = nullptr;
-      c->fuse_list_cap = 0;
-      const size_t cap = (size_t)total + (size_t)total / 2;   // headroom: totals that creep up from call to call do not allocate every time
-      ELLC_HIP(c, hipMalloc(&c->fuse_list_d, cap * sizeof(uint32_t)));
-      c->fuse_list_cap = cap;
-    }
+    if ((st = fuse_list_reserve(c, (size_t)total)) != ELLC_OK) return st;
     a.list = c->fuse_list_d;
     a.list_cap = (unsigned)total;
     if (total > 0) hipLaunchKernelGGL(fuse_scatter, grd, blk, 0, c->stream, a);

@@ -1239,6 +1239,7 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   if (c->fuse_block_d) (void)hipFree(c->fuse_block_d);
   if (c->fuse_list_d) (void)hipFree(c->fuse_list_d);
   if (c->fuse_mask_d) (void)hipFree(c->fuse_mask_d);
+  if (c->absorb_block_d) (void)hipFree(c->absorb_block_d);
   if (c->consist_partials_d) (void)hipFree(c->consist_partials_d);
   if (c->consist_stage_d) (void)hipFree(c->consist_stage_d);
   if (c->consist_stage_h) (void)hipHostFree(c->consist_stage_h);
@@ -2737,3 +2738,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 #include "ellc_fuse_impl.hpp"
 #include "ellc_consistency_impl.hpp"
 #include "ellc_sim3_impl.hpp"
+#include "ellc_absorb_impl.hpp"

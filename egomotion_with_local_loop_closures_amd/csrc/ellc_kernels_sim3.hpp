@@ -73,6 +73,16 @@ __device__ __forceinline__ void sim3_term(Sim3Rec& a, const int (&idx)[N], const
   }
 }
 
+// The bilinear value of four taps at the fractions (ax, ay), and its two gradients, in THE order every caller's result is held to
+// (sim3_pass, absorb_mark): rows first, then the blend of the rows.
+__device__ __forceinline__ float sim3_bilinear(float I00, float I01, float I10, float I11, float ax, float ay, float& gx, float& gy) {
+  const float dx0 = I01 - I00, dx1 = I11 - I10;
+  const float top = I00 + ax * dx0, bot = I10 + ax * dx1;
+  gy = bot - top;
+  gx = dx0 + ay * (dx1 - dx0);
+  return top + ay * gy;
+}
+
 // grid (tiles of the level) x (requests of the launch), map_count's pixel layout: thread t of tile `local` owns pixels
 // local * ELLC_TILE + j * 256 + t and adds them in the order j = 0..7; the wave's lanes are summed by the butterfly, the four waves in
 // ascending order. The partition follows from the level's size alone.
@@ -125,11 +135,8 @@ __global__ __launch_bounds__(256) void sim3_pass(Sim3Args a) {
             const float I00 = (float)timg[t0], I01 = (float)timg[t0 + 1u], I10 = (float)timg[t0 + (unsigned)sw], I11 = (float)timg[t0 + (unsigned)sw + 1u];
             const float Is = (float)img[(unsigned)(p.y * sw + p.x)];
             const float ax = c.u - (float)x0, ay = c.v - (float)y0;
-            const float dx0 = I01 - I00, dx1 = I11 - I10;
-            const float top = I00 + ax * dx0, bot = I10 + ax * dx1;
-            const float gy = bot - top;
-            const float Iw = top + ay * gy;
-            const float gx = dx0 + ay * (dx1 - dx0);
+            float gx, gy;
+            const float Iw = sim3_bilinear(I00, I01, I10, I11, ax, ay, gx, gy);
             rp = Iw - Is;
             const float A = (gx * fx) * c.nid, Bv = (gy * fy) * c.nid;
             const float Cq = -(((A * c.x) + (Bv * c.y)) * c.nid);

@@ -43,6 +43,11 @@
 //                    other file is unchanged. --fuse-inputs DIR (with --fuse) also writes what that view was made from, for a caller to
 //                    fuse it again through another binding: T.bin ([requests][12] f32, keyframe camera -> view camera, request order) and
 //                    slot<k>.depth / slot<k>.var (request k's level-0 planes, raw f32 rows top to bottom)
+// --absorb-matches FILE  (LC mode) what every push's batch found is folded into the LIVE depth map of the pushed keyframe
+//                    (globalOptimize::absorbMatches: the batch and its Sim(3) refinement run synchronously, the candidates' ring slots are
+//                    copied into tracking-context keyframe slots 2, 3, ..., ellc_depth_absorb_keyframes with the default parameters), so
+//                    the map createKeyFrame propagates next carries it; FILE gets "frameId B" and the fifteen stats per push. The
+//                    tracking context is created with max_keyframes 2 + 43. Without the flag every output file is what it was
 // Input is otherwise a header-less file of W*H u8 grey frames (the decode itself always stays outside).
 // In LC mode finished keyframes go through the loop-closure ring (facade class globalOptimize): matching and the batched
 // alignment of a pushed keyframe run on a second thread and a second context beside tracking, joined at the next push
@@ -59,7 +64,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -69,7 +74,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file, fuse_file, fuse_inputs;
+  std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file, fuse_file, fuse_inputs, absorb_matches;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -92,6 +97,7 @@ int main(int argc, char** argv) {
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (a == "--fuse" && i + 1 < argc) fuse_file = argv[++i];
     else if (a == "--fuse-inputs" && i + 1 < argc) fuse_inputs = argv[++i];
+    else if (a == "--absorb-matches" && i + 1 < argc) absorb_matches = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return -1; }
   }
@@ -109,6 +115,7 @@ int main(int argc, char** argv) {
     ellc_default_config(&cfg, W, H, levels);
     cfg.device = device;   // the tracking context: keyframe slots 0,1 (active / incoming), one alignment at a time; in LC mode the
                            // loop-closure ring and its batches live in a context of their own (facade class globalOptimize)
+    if (lc && !absorb_matches.empty()) cfg.max_keyframes = 2 + globalOptimize::MAX_LOOP_ARRAY_LENGTH_SCALE_AVG;   // the candidates' copies (absorbMatches)
     Runtime rt(cfg);
     struct CommOwner {   // destroyed after the loop, before the runtime
       ellc_comm* c = nullptr;
@@ -168,6 +175,11 @@ int main(int argc, char** argv) {
       globalOptimizeLoop->match_sim3_file.open(match_sim3.c_str());
       if (!globalOptimizeLoop->match_sim3_file) { std::fprintf(stderr, "cannot open %s\n", match_sim3.c_str()); return -1; }
       globalOptimizeLoop->refineMatchSim3 = true;
+    }
+    if (lc && !absorb_matches.empty()) {
+      globalOptimizeLoop->absorb_file.open(absorb_matches.c_str());
+      if (!globalOptimizeLoop->absorb_file) { std::fprintf(stderr, "cannot open %s\n", absorb_matches.c_str()); return -1; }
+      globalOptimizeLoop->absorbMatches = true;   // (pushToArray turns the Sim(3) refinement on for its batch)
     }
     std::vector<std::unique_ptr<frame>> frameptr_vector;
     frame* activeKeyFrame = nullptr;

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 16   /* ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 17   /* ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -411,6 +411,71 @@ ellc_status ellc_keyframe_fuse_depth(ellc_ctx* ctx, int B, const int* kf_slots, 
                                      const ellc_map_filter* filter, float agree_k2, int max_merge, int dst_kf_slot,
                                      float* depth, float* var, int32_t* source, int32_t* agree, int32_t* merged,
                                      uint8_t* intensity, int* n_valid, int* n_fused);
+
+/* ---- keyframe maps folded into the live depth map (v17) ----------------------------------------------------------
+ * Everything above ends in planes of a keyframe slot. This call reaches the hypothesis STATE the depth map refines (the seven planes of
+ * ellc_depth_set_state): depthMap::propagateDepth's per-hypothesis rule (DepthPropagation.cpp:1003-1157) from B keyframe slots, each at
+ * a transform of its own, into the live map - without propagateDepth's wipe of the destination, and in a fixed order. The destination
+ * is the context's depth map and its keyframe slot K (ellc_depth_set_keyframe), level 0 only. Request b reads keyframe slot kf_slots[b]
+ * at level 0 (depth Z, variance V, the image); T = T12 + 12 * b takes that slot's camera coordinates into K's (a caller folds a Sim(3)'s
+ * scale into all twelve entries). Slots may repeat, and K itself may be among them. Every operation is IEEE f32 in the stated order, no
+ * contraction, correctly rounded divisions.
+ *   1. A source pixel takes part iff ellc_keyframe_map_points would KEEP it under `filter` (n_kept).
+ *   2. Its candidate (target, z', nid, u, v, nvar) is ellc_keyframe_render_depth's, with the same drops (n_in_view).
+ *   3. Interior bound (:1059): dropped unless u > 2.1f && v > 2.1f && u < (float)cols - 3.1f && v < (float)rows - 3.1f (n_interior).
+ *   4. Photometric gate (:1066-1076), only with photo_gate == 1. g is K's maxAbsGradient (the plane of ellc_get_max_gradient) at the
+ *      TARGET pixel - the reference reads it at the SOURCE's coordinates (a quirk its propagation is held to elsewhere); this call has no
+ *      reference output to match and reads it where it belongs. Iw is the bilinear value of K's level-0 image at (u, v) by the formulas
+ *      of ellc_keyframe_sim3_step step 3 (x0 = (int)u, ax, dx0, top, bot, Iw = top + ay * (bot - top); the four taps exist because of
+ *      step 3 above), Is the source's grey value, r = Iw - Is. Dropped iff (r * r) / (1600.0f + (0.25f * g) * g) > 1.0f || g < 5.0f
+ *      (MAX_DIFF_CONSTANT, MAX_DIFF_GRAD_MULT, MIN_ABS_GRAD_DECREASE). The survivors of 1-4 are the CANDIDATES (n_candidates).
+ *   5. Fold. A target's candidates are taken in ascending 32-bit id (b << 24) | i; only the first max_fold are VISITED (a target with
+ *      more is counted in targets_truncated). The state of a target starts as the live hypothesis: valid = isValid != 0, id = invDepth,
+ *      var = variance, val = validity_counter. Each visited candidate (nid, nvar) ends in exactly one of five outcomes:
+ *        target valid, conflict - with d = nid - id, !(d * d <= agree_k2 * (nvar + var)), so a NaN is a conflict:
+ *          d < 0: OCCLUDED, changes nothing (:1096-1099);  otherwise REPLACED: id = nid, var = nvar, val = src_validity (:1101-1121);
+ *        target valid, agreeing - with s = var + nvar:  SKIPPED iff !(s > 0 && s <= FLT_MAX) (the fusion's rule);  otherwise MERGED:
+ *          w = nvar / s;  id = (w * id) + ((1.0f - w) * nid);  var = 1.0f / ((1.0f / var) + (1.0f / nvar)) with the old var;
+ *          val = min(val + src_validity, 255) (:1128-1140);
+ *        target not valid - CREATED: id = nid, var = nvar, val = src_validity, valid = true.
+ *      A target with at least one created, replaced or merged candidate is TOUCHED: invDepth = id, variance = var, validity_counter = val,
+ *      isValid = 1, blacklisted = 0, invDepthSmoothed = varianceSmoothed = -1.0f (:1112-1118, :1138-1145). Every other hypothesis keeps
+ *      every byte.
+ *   6. Stats: n_visited == n_created + n_merged + n_replaced + n_occluded + n_skipped; targets_hit counts the targets with at least one
+ *      candidate; n_valid_before / n_valid_after count isValid around the fold, before `finalise`.
+ *   7. finalise == 1: afterwards the state and K's planes are, bit for bit, what the same call with finalise == 0 followed by
+ *      ellc_depth_do_regularization(ctx, 0) and ellc_depth_update_depth_image(ctx) leaves. With finalise == 0 the smoothed fields of
+ *      touched targets are -1, as after propagateDepth: the caller MUST regularise before anything observes or exports the map.
+ *   8. Whatever ellc_depth_set_state leaves for the rest of the library, this call leaves too: ellc_depth_seeds and ellc_track_frame count
+ *      and read the state as it then stands.
+ *   9. The result is a function of the intrinsics, the sources' three planes, K's image and maxAbsGradient, the state, the T's, the
+ *      filter and the parameters ALONE: cfg.arith, cfg.grid_batch, whatever else is in flight and the order candidates arrive in do not
+ *      enter it, and a second call on the same inputs gives the same bytes (no floating-point atomics: every target folds its
+ *      candidates itself, in the order above).
+ *  10. Synchronous, ordered like every other non-batch entry point. A refused call changes nothing and writes nothing to `out`.
+ * ELLC_ERR_BAD_ARG: B < 1, B > max_keyframes, B > 256, a slot out of range, more than 2^24 pixels, kf_slots, T12, filter or params NULL,
+ * the filter errors of ellc_keyframe_map_points, agree_k2 negative or not finite, max_fold outside 1 .. ELLC_FUSE_MAX_MERGE, src_validity
+ * outside 0..255, photo_gate or finalise outside 0..1;
+ * ELLC_ERR_NOT_READY: no depth-map keyframe or state, a source slot without image or depth;
+ * ELLC_ERR_CAPACITY: more than 2^31 - 1 candidates; nothing has been changed. */
+typedef struct {
+  float agree_k2;     /* >= 0, finite */
+  int   max_fold;     /* 1 .. ELLC_FUSE_MAX_MERGE: candidates VISITED per target */
+  int   photo_gate;   /* 0 / 1: the photometric gate of :1066-1076 */
+  int   src_validity; /* 0 .. 255: validity_counter a candidate carries (keyframe slots keep none) */
+  int   finalise;     /* 0 / 1: behind the fold, ellc_depth_do_regularization(ctx, 0) and ellc_depth_update_depth_image(ctx) */
+} ellc_absorb_params;
+void ellc_absorb_default_params(ellc_absorb_params* params);   /* {1.0f, 64, 1, 20, 1}; 20 is initializeRandomly's counter */
+
+typedef struct {      /* 16 x int32 = 64 bytes */
+  int32_t n_kept, n_in_view, n_interior, n_candidates;
+  int32_t n_visited, n_created, n_merged, n_replaced, n_occluded, n_skipped;
+  int32_t targets_hit, targets_touched, targets_truncated;
+  int32_t n_valid_before, n_valid_after, reserved;   /* reserved = 0 */
+} ellc_absorb_stats;
+
+ellc_status ellc_depth_absorb_keyframes(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
+                                        const ellc_absorb_params* params, ellc_absorb_stats* out /* may be NULL */);
 
 /* ---- one keyframe's map against another's (v14) ------------------------------------------------------------------
  * The geometric check of a loop closure, and the scale between two maps: request b compares keyframe slot src_kf_slots[b] with slot

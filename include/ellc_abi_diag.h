@@ -45,6 +45,13 @@ ellc_status ellc_profile_fuse_depth(ellc_ctx* ctx, int B, const int* kf_slots, c
                                     float agree_k2, int max_merge, int dst_kf_slot, float* depth, float* var, int32_t* source, int32_t* agree,
                                     int32_t* merged, uint8_t* intensity, int* n_valid, int* n_fused, float* launches_ms);
 
+/* ellc_depth_absorb_keyframes with HIP events around its launches (the preset of the count plane, absorb_mark, fuse_tile_sums,
+ * fuse_offsets, absorb_scatter, absorb_fold, absorb_finish): launches_ms receives the device time from the first to the end of the last,
+ * without finalise's regularisation and export behind them. The host's read of the list's size lies INSIDE that window, as in the
+ * fusion's hook. Everything else as the product call. */
+ellc_status ellc_profile_depth_absorb(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
+                                      const ellc_absorb_params* params, ellc_absorb_stats* out, float* launches_ms);
+
 /* ellc_keyframe_depth_consistency with HIP events around its launches (consist_pass, consist_finish): launches_ms receives their
  * device time, without the staging copy in front. Everything else as the product call. */
 ellc_status ellc_profile_depth_consistency(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,

@@ -456,6 +456,22 @@ class globalOptimize {
   bool refineMatchSim3 = false;
   std::vector<MatchSim3> lastMatchSim3;
   std::ofstream match_sim3_file;
+  // What a closed loop teaches, kept in the TRACKING context (ellc_depth_absorb_keyframes): every candidate of the push's batch is folded
+  // into the live depth map of the pushed keyframe at its refined Sim(3). Off by default: nothing changes. On: pushToArray runs
+  // findMatchParallel synchronously with the Sim(3) refinement, copies the ring slot of every entry of lastMatchSim3 into the tracking
+  // context's keyframe slots 2, 3, ... (ellc_copy_slot_across), calls ellc_depth_absorb_keyframes there with each entry's T (candidate ->
+  // pushed keyframe, which is the depth map's keyframe at that moment), the filter of ellc_main --map and the default parameters
+  // (finalise on: the map is regularised and exported, so what createKeyFrame propagates next is the absorbed map), and absorb_file
+  // (when open) gets "frameId B" and the fifteen stats per push (B 0 and zeros for a push without a match). The tracking runtime
+  // needs max_keyframes >= 2 + MAX_LOOP_ARRAY_LENGTH_SCALE_AVG; otherwise pushToArray throws. lastAbsorbStats keeps the record.
+  struct AbsorbRecord {
+    int frameId = 0, B = 0;
+    ellc_absorb_stats stats;
+  };
+  bool absorbMatches = false;
+  AbsorbRecord lastAbsorbStats;
+  std::vector<int> lastMatchSlots;   // ring slots of the candidates of the batch findMatchParallel ran last, in lastMatchSim3's order (empty: no match)
+  std::ofstream absorb_file;
 
   static ellc_config ring_config(const ellc_config& tracking, bool fixed_grids) {
     ellc_config c = tracking;
@@ -541,12 +557,51 @@ class globalOptimize {
     std::memcpy(slot.poseWrtOrigin, currentframe->poseWrtOrigin, 24);
     slot.rescaleFactor = currentframe->rescaleFactor;
     slot.seeds = currentDepthMap->calculate_no_of_Seeds();
-    if (FLAG_DO_PARALLEL_SHORT_LOOP_CLOSURE) {   // :239-241
+    if (absorbMatches) {   // the batch, its Sim(3) refinement and the fold before the caller goes on to createKeyFrame
+      if (rt->cfg.max_keyframes < 2 + MAX_LOOP_ARRAY_LENGTH_SCALE_AVG)
+        throw std::runtime_error("absorbMatches: the tracking runtime needs max_keyframes >= 2 + MAX_LOOP_ARRAY_LENGTH_SCALE_AVG");
+      const bool refine = refineMatchSim3;
+      refineMatchSim3 = true;
+      try { findMatchParallel(test); } catch (...) { refineMatchSim3 = refine; throw; }
+      refineMatchSim3 = refine;
+      absorbLastMatches(test.frameId);
+    } else if (FLAG_DO_PARALLEL_SHORT_LOOP_CLOSURE) {   // :239-241
       t_group = std::thread([this, test]() {
         try { findMatchParallel(test); } catch (const std::exception& e) { thread_error = e.what(); }
       });
     } else {
       findMatchParallel(test);
+    }
+  }
+
+  // absorbMatches: the candidates of the batch findMatchParallel just ran, folded into the tracking context's live depth map
+  void absorbLastMatches(int frameId) {
+    const int B = (int)lastMatchSlots.size();
+    lastAbsorbStats = AbsorbRecord();
+    lastAbsorbStats.frameId = frameId + rt->BATCH_START_ID - 1;
+    lastAbsorbStats.B = B;
+    std::memset(&lastAbsorbStats.stats, 0, sizeof(lastAbsorbStats.stats));
+    if (B > 0) {
+      if ((size_t)B != lastMatchSim3.size()) throw std::runtime_error("absorbMatches: the batch left no Sim(3) per candidate");
+      std::vector<int> slots((size_t)B);
+      std::vector<float> T((size_t)B * 12);
+      for (int b = 0; b < B; b++) {
+        slots[(size_t)b] = 2 + b;
+        rt->check(ellc_copy_slot_across(rt->ctx, 1, 2 + b, ring.ctx, 1, lastMatchSlots[(size_t)b]), "ellc_copy_slot_across");
+        for (int k = 0; k < 12; k++) T[(size_t)b * 12 + k] = lastMatchSim3[(size_t)b].T[k];
+      }
+      ellc_map_filter filter;   // the filter of ellc_main --map
+      filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+      ellc_absorb_params params;
+      ellc_absorb_default_params(&params);
+      rt->check(ellc_depth_absorb_keyframes(rt->ctx, B, slots.data(), T.data(), &filter, &params, &lastAbsorbStats.stats), "ellc_depth_absorb_keyframes");
+    }
+    if (absorb_file.is_open()) {
+      const int32_t* v = &lastAbsorbStats.stats.n_kept;   // sixteen int32 in a row (ellc_abi.h); the reserved word is not written
+      absorb_file << lastAbsorbStats.frameId << " " << B;
+      for (int k = 0; k < 15; k++) absorb_file << " " << v[k];
+      absorb_file << "\n";
+      absorb_file.flush();
     }
   }
 
@@ -735,6 +790,7 @@ class globalOptimize {
     const int RING = MAX_LOOP_ARRAY_LENGTH_SCALE_AVG;
     struct Match { int arrayId; float matchValue, rms, angle; };
     std::vector<Match> matches;
+    lastMatchSlots.clear();
     loopFrameArray[nextArrayId].frameId = testFrame.frameId;
     lastTestedLoopClosureArrayId = -1;
     firstTestedLoopClosureArrayId = -1;
@@ -759,6 +815,7 @@ class globalOptimize {
         kf[b] = m.kf_slot;
         ellc_concatenate_origin_pose(testFrame.poseWrtWorld, m.poseWrtWorld, &init[(size_t)b * 6]);   // ImageFunc.cpp:106
       }
+      lastMatchSlots = kf;
       if (fixed_grids_) ring.check(ellc_ctx_set_grid_batch(ring.ctx, lc_grid_bucket(B)), "ellc_ctx_set_grid_batch");   // of the WHOLE batch, on every rank
       if (rt->comm && rt->world > 1) {
         // this rank's contiguous block of the candidates on its own GPU, then the one exchange of the batch: 8 floats per
