@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "ellc_depth_observe", "ellc_depth_fill_holes", "ellc_depth_regularize", "ellc_depth_make_inv_depth_one", "ellc_depth_regularize_fill_regularize", "ellc_depth_do_regularization",
     "ellc_depth_update_depth_image", "ellc_depth_create_keyframe", "ellc_depth_seeds", "ellc_track_frame",
     "ellc_histogram", "ellc_kl_divergence", "ellc_copy_slot", "ellc_copy_slot_across", "ellc_keyframe_map_points", "ellc_keyframe_render_depth", "ellc_keyframe_fuse_depth",
-    "ellc_depth_absorb_keyframes", "ellc_absorb_default_params",
+    "ellc_depth_absorb_keyframes", "ellc_absorb_default_params", "ellc_keyframe_trial_propagate", "ellc_depth_restart_from_keyframes",
     "ellc_keyframe_depth_consistency", "ellc_keyframe_sim3_step", "ellc_keyframe_sim3_align", "ellc_sim3_default_params", "ellc_sim3_solve", "ellc_sim3_apply",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
@@ -35,7 +35,7 @@ DIAG_SYMBOLS = [
     "ellc_profile_gn_kernel", "ellc_profile_align", "ellc_profile_depth_stage", "ellc_profile_calibrate_read", "ellc_profile_stream_read",
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
     "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
-    "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_fuse_depth", "ellc_profile_depth_absorb", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
+    "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_fuse_depth", "ellc_profile_depth_absorb", "ellc_profile_trial_propagate", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
 ]
 
 
@@ -102,6 +102,13 @@ ABSORB_STATS_FIELDS = ("n_kept", "n_in_view", "n_interior", "n_candidates", "n_v
 class EllcAbsorbStats(C.Structure):
     """ellc_absorb_stats: what ellc_depth_absorb_keyframes counts (64 bytes)."""
     _fields_ = [(name, C.c_int32) for name in ABSORB_STATS_FIELDS]
+
+
+class EllcTrialPropagation(C.Structure):
+    """ellc_trial_propagation: what ellc_keyframe_trial_propagate returns per request (48 bytes)."""
+    _fields_ = [("sum_r2", C.c_double), ("sum_abs_r", C.c_double),
+                ("n_kept", C.c_int32), ("n_in_view", C.c_int32), ("n_interior", C.c_int32), ("n_low_grad", C.c_int32),
+                ("n_candidates", C.c_int32), ("n_targets", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class EllcError(RuntimeError):

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -409,14 +409,15 @@ class Context:
                           max_var, min_support, support_k2, stride, out)
 
     # ---- keyframe maps folded into the live depth map
-    def _absorb(self, fn, name, extra, kf_slots, T12, params, max_var, min_support, support_k2, stride, stats):
+    def _absorb(self, fn, name, extra, kf_slots, T12, params, max_var, min_support, support_k2, stride, stats, tail=None):
         kf = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
         B = kf.size
         T = np.ascontiguousarray(T12, np.float32).reshape(B, 12)
         flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
         prm = params if isinstance(params, EllcAbsorbParams) else absorb_params(**(params or {}))
         st = stats if stats is not None else EllcAbsorbStats()
-        self._ck(fn(self.h, B, _p(kf), _p(T), C.byref(flt), C.byref(prm), C.byref(st), *extra), name)
+        # (tail: arguments in front of the stats pointer - ellc_depth_restart_from_keyframes' rescale factor)
+        self._ck(fn(self.h, B, _p(kf), _p(T), C.byref(flt), C.byref(prm), *(tail or ()), C.byref(st), *extra), name)
         return {k: int(getattr(st, k)) for k in ABSORB_STATS_FIELDS}
 
     def depth_absorb(self, kf_slots, T12, params=None, max_var=0.0, min_support=0, support_k2=1.0, stride=1, stats=None):
@@ -427,6 +428,36 @@ class Context:
         finalise=0 the caller must regularise (depth_do_regularization) before anything observes or exports the map."""
         return self._absorb(self._l.ellc_depth_absorb_keyframes, "ellc_depth_absorb_keyframes", (), kf_slots, T12, params, max_var, min_support,
                             support_k2, stride, stats)
+
+    def depth_restart(self, new_kf_slot, kf_slots, T12, params=None, max_var=0.0, min_support=0, support_k2=1.0, stride=1, stats=None):
+        """The live depth map re-seated on keyframe slot new_kf_slot (which holds an image and is not among kf_slots) from the maps of
+        keyframe slots kf_slots[b], starting EMPTY (ellc_depth_restart_from_keyframes): the wipe, depth_absorb's fold with T12[b] the
+        transform from slot kf_slots[b]'s camera into new_kf_slot's, and with finalise=1 (the default) createKeyFrame's tail. The
+        context needs no state beforehand. Returns (the sixteen counts of ellc_absorb_stats as a dict, the rescale factor)."""
+        factor = C.c_float(0.0)
+        out = self._absorb(lambda h, *a: self._l.ellc_depth_restart_from_keyframes(h, int(new_kf_slot), *a), "ellc_depth_restart_from_keyframes",
+                           (), kf_slots, T12, params, max_var, min_support, support_k2, stride, stats, tail=(C.byref(factor),))
+        return out, float(factor.value)
+
+    # ---- trial propagation: what a keyframe's map would seed in an image
+    def _trial(self, fn, name, extra, src_slots, dst_slots, Ts, dst_is_keyframe, photo_gate, max_var, min_support, support_k2, stride):
+        src = np.ascontiguousarray(src_slots, np.int32).reshape(-1)
+        dst = np.ascontiguousarray(dst_slots, np.int32).reshape(-1)
+        B = src.size
+        assert dst.size == B
+        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        out = np.zeros(B, np.dtype(EllcTrialPropagation))
+        self._ck(fn(self.h, B, _p(src), int(dst_is_keyframe), _p(dst), _p(T), C.byref(flt), int(photo_gate), _p(out), *extra), name)
+        return out
+
+    def trial_propagate(self, src_slots, dst_slots, Ts, dst_is_keyframe=False, photo_gate=1, max_var=0.0, min_support=0, support_k2=1.0, stride=1):
+        """What propagating keyframe slot src_slots[b]'s map into the image of slot dst_slots[b] (a frame slot, or a keyframe slot with
+        dst_is_keyframe) at Ts[b] (row-major 3x4, source camera into destination camera) would give (ellc_keyframe_trial_propagate): a
+        structured array of B ellc_trial_propagation records - n_kept, n_in_view, n_interior, n_low_grad, n_candidates, n_targets
+        (int32), sum_r2, sum_abs_r (f64). n_targets is the number of hypotheses a restart from that request alone would create."""
+        return self._trial(self._l.ellc_keyframe_trial_propagate, "ellc_keyframe_trial_propagate", (), src_slots, dst_slots, Ts, dst_is_keyframe,
+                           photo_gate, max_var, min_support, support_k2, stride)
 
     # ---- one keyframe's map against another's
     def _consistency(self, fn, name, extra, src_slots, dst_slots, Ts, level, agree_k2, max_var, min_support, support_k2, stride):
@@ -642,6 +673,16 @@ class Context:
                            min_support, support_k2, stride, stats)
         out["launches_ms"] = ms.value
         return out
+
+    def profile_trial_propagate(self, src_slots, dst_slots, Ts, dst_is_keyframe=False, photo_gate=1, max_group_requests=0, max_var=0.0,
+                                min_support=0, support_k2=1.0, stride=1):
+        """trial_propagate through ellc_profile_trial_propagate: (records, launches_ms), with the number of requests per launch forced
+        to max_group_requests (0: the product call's choice). The records do not depend on it."""
+        self._need_diag("ellc_profile_trial_propagate")
+        ms = C.c_float(0.0)
+        out = self._trial(self._l.ellc_profile_trial_propagate, "ellc_profile_trial_propagate", (int(max_group_requests), C.byref(ms)), src_slots,
+                          dst_slots, Ts, dst_is_keyframe, photo_gate, max_var, min_support, support_k2, stride)
+        return out, float(ms.value)
 
     def profile_depth_consistency(self, src_slots, dst_slots, Ts, level=0, agree_k2=1.0, max_var=0.0, min_support=0, support_k2=1.0, stride=1):
         """depth_consistency through ellc_profile_depth_consistency: (records, launches_ms), the device time of the launches."""

@@ -14,20 +14,26 @@ namespace {
 
 // launches_ms (the diagnostic hook only): device time from the preset of the count plane to the end of absorb_finish (finalise's
 // launches are not inside), HIP events around them. The host's read of the list's size lies inside that window, as in the fusion.
+// restart_slot >= 0: ellc_depth_restart_from_keyframes. That slot takes K's place, the state is wiped in front of the fold (behind
+// everything that can refuse the call) and `finalise` runs createKeyFrame's tail, whose factor goes to *rescale_factor.
 ellc_status absorb_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const ellc_map_filter* f, const ellc_absorb_params* p,
-                        ellc_absorb_stats* out, float* launches_ms) {
-  const char* who = "ellc_depth_absorb_keyframes";
+                        ellc_absorb_stats* out, float* launches_ms, int restart_slot = -1, float* rescale_factor = nullptr) {
+  const bool restart = restart_slot >= 0;
+  const char* who = restart ? "ellc_depth_restart_from_keyframes" : "ellc_depth_absorb_keyframes";
   if (!c) return ELLC_ERR_BAD_ARG;
   if (!p) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": null pointer");
   // (the parameters first: a bad argument is reported in front of a slot that is not ready)
   if (p->max_fold < 1 || p->max_fold > ELLC_FUSE_MAX_MERGE) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": max_fold out of range");
   if (p->src_validity < 0 || p->src_validity > 255) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": src_validity out of range");
   if (p->photo_gate < 0 || p->photo_gate > 1 || p->finalise < 0 || p->finalise > 1) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": photo_gate / finalise not 0 or 1");
-  ellc_status st = render_validate(c, who, B, kf_slots, T12, 0, f, p->agree_k2, -1, true);
+  ellc_status st = render_validate(c, who, B, kf_slots, T12, 0, f, p->agree_k2, restart_slot, !restart);   // (the new keyframe is no source)
   if (st != ELLC_OK) return st;
-  if (!c->dm_ready || c->dm_kf_slot < 0) return fail(c, ELLC_ERR_NOT_READY, std::string(who) + ": call ellc_depth_set_state and ellc_depth_set_keyframe first");
+  if (restart) {
+    if (!c->kf_has_image[restart_slot]) return fail(c, ELLC_ERR_NOT_READY, std::string(who) + ": the new keyframe slot has no image");
+  } else if (!c->dm_ready || c->dm_kf_slot < 0)
+    return fail(c, ELLC_ERR_NOT_READY, std::string(who) + ": call ellc_depth_set_state and ellc_depth_set_keyframe first");
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
-  const int K = c->dm_kf_slot;
+  const int K = restart ? restart_slot : c->dm_kf_slot;
   if ((st = render_scratch(c)) != ELLC_OK) return st;
   if ((st = fuse_scratch(c)) != ELLC_OK) return st;
   const size_t n0 = (size_t)c->geom_h[0].n, blocks0 = (n0 + 255) / 256;
@@ -80,16 +86,34 @@ ellc_status absorb_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T1
   if ((st = fuse_list_reserve(c, (size_t)total)) != ELLC_OK) return st;
   a.f.list = c->fuse_list_d;
   a.f.list_cap = (unsigned)total;
+  const int old_slot = c->dm_kf_slot;
+  if (restart) {   // from here on the call cannot be refused: the map is re-seated on the new keyframe, EMPTY
+    hipLaunchKernelGGL(absorb_wipe, dim3(a.f.r.blocks), blk, 0, c->stream, a.s, a.f.r.n);
+    c->dm_kf_slot = K;
+    c->dm_ready = true;
+  }
+  // a device error part-way through a restart: the map no longer matches either keyframe (as in ellc_depth_create_keyframe)
+  auto broken = [&](ellc_status s) {
+    if (restart) {
+      c->dm_kf_slot = old_slot;
+      c->dm_ready = false;
+    }
+    return s;
+  };
   if (total > 0) hipLaunchKernelGGL(absorb_scatter, grd, blk, 0, c->stream, a);
   hipLaunchKernelGGL(absorb_fold, dim3(a.f.r.blocks), blk, 0, c->stream, a);
   hipLaunchKernelGGL(absorb_finish, dim3(1), blk, 0, c->stream, a);
-  ELLC_HIP(c, hipGetLastError());
+  if (hipGetLastError() != hipSuccess) return broken(fail(c, ELLC_ERR_HIP, std::string(who) + ": a launch failed"));
   if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
-  if (p->finalise) {   // ellc_depth_do_regularization(ctx, 0) and ellc_depth_update_depth_image(ctx), as they enqueue them
+  float factor = 1.0f;
+  if (p->finalise && restart) {   // createKeyFrame's tail, as ellc_depth_create_keyframe enqueues it
+    if ((st = do_create_keyframe_tail(c, &factor)) != ELLC_OK) return broken(st);
+  } else if (p->finalise) {   // ellc_depth_do_regularization(ctx, 0) and ellc_depth_update_depth_image(ctx), as they enqueue them
     if ((st = do_fill_regularize(c, 0)) != ELLC_OK) return st;
     if ((st = do_update_depth_image(c)) != ELLC_OK) return st;
   }
-  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  if (hipStreamSynchronize(c->stream) != hipSuccess) return broken(fail(c, ELLC_ERR_HIP, std::string(who) + ": the stream failed"));
+  if (rescale_factor) *rescale_factor = factor;
   if (out) std::memcpy(out, c->absorb_stats_h, sizeof(ellc_absorb_stats));
   if (launches_ms) ELLC_HIP(c, hipEventElapsedTime(launches_ms, c->ev0, c->ev1));
   return ELLC_OK;
@@ -111,6 +135,13 @@ void ellc_absorb_default_params(ellc_absorb_params* p) {
 ellc_status ellc_depth_absorb_keyframes(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
                                         const ellc_absorb_params* params, ellc_absorb_stats* out) {
   return absorb_impl(c, B, kf_slots, T12, filter, params, out, nullptr);
+}
+
+ellc_status ellc_depth_restart_from_keyframes(ellc_ctx* c, int new_kf_slot, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
+                                              const ellc_absorb_params* params, float* rescale_factor, ellc_absorb_stats* out) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  if (!slot_ok(new_kf_slot, c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, "ellc_depth_restart_from_keyframes: new keyframe slot out of range");
+  return absorb_impl(c, B, kf_slots, T12, filter, params, out, nullptr, new_kf_slot, rescale_factor);
 }
 
 #ifdef ELLC_DIAG_ABI

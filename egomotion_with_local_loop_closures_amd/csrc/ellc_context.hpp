@@ -262,6 +262,15 @@ struct ellc_ctx {
   void *consist_out_h = nullptr, *consist_out_dev_alias = nullptr;   // pinned: [cap] records (consist_finish writes them)
   void* consist_partials_d = nullptr;       // [requests of one launch][tiles of the level] partial records
   size_t consist_partials_cap = 0;          //   records it holds
+  // ellc_keyframe_trial_propagate: the same, of its own
+  int trial_cap = 0;                        // requests the staging holds
+  void* trial_req_h = nullptr;              // pinned: [cap] TrialReq (source slot, destination planes, transform)
+  void* trial_req_d = nullptr;              //   and its device copy
+  void *trial_out_h = nullptr, *trial_out_dev_alias = nullptr;   // pinned: [cap] records (trial_finish writes them)
+  void* trial_partials_d = nullptr;         // [requests of one launch][tiles of level 0] partial records
+  size_t trial_partials_cap = 0;            //   records it holds
+  unsigned* trial_bits_d = nullptr;         // [requests of one launch][ceil(W*H / 32)] one bit per target pixel
+  size_t trial_bits_cap = 0;                //   words it holds
   // ellc_keyframe_sim3_step / ellc_keyframe_sim3_align: the same, of their own
   int sim3_cap = 0;
   int* sim3_stage_h = nullptr;

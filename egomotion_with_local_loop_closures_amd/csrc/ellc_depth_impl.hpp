@@ -209,6 +209,19 @@ ellc_status do_propagate(ellc_ctx* c, int new_kf_slot, const float* pose_new_wrt
   return ELLC_OK;
 }
 
+// createKeyFrame behind its propagation, with dm_kf_slot already the new keyframe: :1775 regularizeDepthMap(true), :1777
+// doRegularization(false) = fill + regularise: one launch, which also leaves the per-tile sums of :1779 makeInvDepthOne; the export's
+// launch (:1781 updateDepthImage) finishes that sum and rescales first
+ellc_status do_create_keyframe_tail(ellc_ctx* c, float* rescale_factor) {
+  ellc_status s;
+  const bool merged = rescale_in_export(c);
+  if ((s = do_reg_fill_reg(c, 1, merged)) == ELLC_OK &&
+      (merged || (s = do_rescale_enqueue(c)) == ELLC_OK) &&
+      (s = do_update_depth_image(c, merged)) == ELLC_OK)
+    s = do_rescale_finish(c, rescale_factor);   // the one host wait of the whole sequence: the factor the caller is handed
+  return s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -467,13 +480,7 @@ ellc_status ellc_depth_create_keyframe(ellc_ctx* c, int new_kf_slot, const float
   if ((s = do_propagate(c, new_kf_slot, pose_new_wrt_old)) != ELLC_OK) return s;   // :1769 (on failure the map is unchanged)
   const int old_slot = c->dm_kf_slot;
   c->dm_kf_slot = new_kf_slot;                                                     // :1772
-  // :1775 regularizeDepthMap(true), :1777 doRegularization(false) = fill + regularise: one launch, which also leaves the per-tile
-  // sums of :1779 makeInvDepthOne; the export's launch (:1781 updateDepthImage) finishes that sum and rescales first
-  const bool merged = rescale_in_export(c);
-  if ((s = do_reg_fill_reg(c, 1, merged)) == ELLC_OK &&
-      (merged || (s = do_rescale_enqueue(c)) == ELLC_OK) &&
-      (s = do_update_depth_image(c, merged)) == ELLC_OK)
-    s = do_rescale_finish(c, rescale_factor);   // the one host wait of the whole sequence: the factor the caller is handed
+  s = do_create_keyframe_tail(c, rescale_factor);                                  // :1775-1781
   if (s != ELLC_OK) {   // a device error part-way: the map no longer matches either keyframe
     c->dm_kf_slot = old_slot;
     c->dm_ready = false;

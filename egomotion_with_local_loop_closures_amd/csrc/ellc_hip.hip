@@ -1244,6 +1244,11 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   if (c->consist_stage_d) (void)hipFree(c->consist_stage_d);
   if (c->consist_stage_h) (void)hipHostFree(c->consist_stage_h);
   if (c->consist_out_h) (void)hipHostFree(c->consist_out_h);
+  if (c->trial_partials_d) (void)hipFree(c->trial_partials_d);
+  if (c->trial_bits_d) (void)hipFree(c->trial_bits_d);
+  if (c->trial_req_d) (void)hipFree(c->trial_req_d);
+  if (c->trial_req_h) (void)hipHostFree(c->trial_req_h);
+  if (c->trial_out_h) (void)hipHostFree(c->trial_out_h);
   if (c->sim3_partials_d) (void)hipFree(c->sim3_partials_d);
   if (c->sim3_stage_d) (void)hipFree(c->sim3_stage_d);
   if (c->sim3_stage_h) (void)hipHostFree(c->sim3_stage_h);
@@ -2739,3 +2744,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 #include "ellc_consistency_impl.hpp"
 #include "ellc_sim3_impl.hpp"
 #include "ellc_absorb_impl.hpp"
+#include "ellc_trial_impl.hpp"

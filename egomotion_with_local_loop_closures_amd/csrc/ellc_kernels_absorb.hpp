@@ -9,7 +9,9 @@
 //   absorb_scatter                  the walk again over the kept bits: every candidate takes the next entry of its target's segment
 //   absorb_fold + absorb_finish     one thread per target: its candidates in ascending id order, eight at a walk (fuse_merge's selection),
 //                                   folded in registers into the target's own hypothesis, which is written in place
+//   absorb_wipe                     ellc_depth_restart_from_keyframes only, in front of the scatter: every hypothesis empty
 // No waiting between blocks, integer atomics only, no floating-point atomics. render_candidate and map_keep decide every pass.
+// absorb_interior and absorb_photo, the two halves of absorb_mark's gate, also decide ellc_keyframe_trial_propagate's pass (ellc_kernels_trial.hpp).
 #pragma once
 #include "ellc_context.hpp"
 #include "ellc_kernels_fuse.hpp"
@@ -30,24 +32,38 @@ struct AbsorbArgs {
   int max_fold, photo_gate, src_validity;
 };
 
-// THE rule behind render_candidate, for absorb_mark: does the candidate of source pixel (x, y) of image `img` pass the interior bound
-// (:1059) and, when it is on, the photometric gate (:1066-1076: MAX_DIFF_CONSTANT 1600, MAX_DIFF_GRAD_MULT 0.25, MIN_ABS_GRAD_DECREASE 5)
-__device__ __forceinline__ bool absorb_gate(const AbsorbArgs& a, const LevelGeom& g, const ELLC_GLOBAL uint8_t* img, int x, int y, const RenderCand& c,
-                                            bool& interior) {
-  interior = c.u > 2.1f && c.v > 2.1f && c.u < (float)g.cols - 3.1f && c.v < (float)g.rows - 3.1f;
-  if (!interior) return false;
-  if (!a.photo_gate) return true;
+// The interior bound of :1059 on a candidate's projection: inside it the four bilinear taps exist
+__device__ __forceinline__ bool absorb_interior(const LevelGeom& g, const RenderCand& c) {
+  return c.u > 2.1f && c.v > 2.1f && c.u < (float)g.cols - 3.1f && c.v < (float)g.rows - 3.1f;
+}
+
+// The photometric gate of :1066-1076 (MAX_DIFF_CONSTANT 1600, MAX_DIFF_GRAD_MULT 0.25, MIN_ABS_GRAD_DECREASE 5) on an INTERIOR candidate of
+// source pixel (x, y) of image `img`, against the destination's level-0 image k_img (pitch g.sw) and maxAbsGradient plane k_maxgrad: does
+// the candidate pass. r = Iw - Is and gr (the gradient at the TARGET) are handed back for ellc_keyframe_trial_propagate's sums.
+__device__ __forceinline__ bool absorb_photo(const LevelGeom& g, const uint8_t* k_img, const float* k_maxgrad, const ELLC_GLOBAL uint8_t* img, int x, int y,
+                                             const RenderCand& c, float& r, float& gr) {
   // 2 < u < cols - 3 and 2 < v < rows - 3: the four taps exist
   const int x0 = (int)c.u, y0 = (int)c.v;
   const unsigned t0 = (unsigned)(y0 * g.sw + x0);
-  const float I00 = (float)a.k_img[t0], I01 = (float)a.k_img[t0 + 1u], I10 = (float)a.k_img[t0 + (unsigned)g.sw], I11 = (float)a.k_img[t0 + (unsigned)g.sw + 1u];
+  const float I00 = (float)k_img[t0], I01 = (float)k_img[t0 + 1u], I10 = (float)k_img[t0 + (unsigned)g.sw], I11 = (float)k_img[t0 + (unsigned)g.sw + 1u];
   const float ax = c.u - (float)x0, ay = c.v - (float)y0;
   float gx, gy;
   const float Iw = sim3_bilinear(I00, I01, I10, I11, ax, ay, gx, gy);
   const float Is = (float)img[(unsigned)(y * g.sw + x)];
-  const float r = Iw - Is;
-  const float gr = a.k_maxgrad[(unsigned)c.target];   // at the TARGET (the reference reads the source's coordinates: dm_prop_project's Q14)
+  r = Iw - Is;
+  gr = k_maxgrad[(unsigned)c.target];   // at the TARGET (the reference reads the source's coordinates: dm_prop_project's Q14)
   return !((r * r) / (1600.0f + (0.25f * gr) * gr) > 1.0f || gr < 5.0f);
+}
+
+// THE rule behind render_candidate, for absorb_mark: does the candidate of source pixel (x, y) of image `img` pass the interior bound
+// and, when it is on, the photometric gate against k_img / k_maxgrad
+__device__ __forceinline__ bool absorb_gate(const LevelGeom& g, const uint8_t* k_img, const float* k_maxgrad, int photo_gate, const ELLC_GLOBAL uint8_t* img,
+                                            int x, int y, const RenderCand& c, bool& interior) {
+  interior = absorb_interior(g, c);
+  if (!interior) return false;
+  if (!photo_gate) return true;
+  float r, gr;
+  return absorb_photo(g, k_img, k_maxgrad, img, x, y, c, r, gr);
 }
 
 // fuse_agree's grid (tiles of level 0) x B and walk
@@ -74,7 +90,7 @@ __global__ __launch_bounds__(256) void absorb_mark(AbsorbArgs a) {
       if (render_candidate(g, T, b, i, p.x, p.y, p.Z, p.V, c)) {
         n_view++;
         bool interior;
-        ok = absorb_gate(a, g, img, p.x, p.y, c, interior);
+        ok = absorb_gate(g, a.k_img, a.k_maxgrad, a.photo_gate, img, p.x, p.y, c, interior);
         n_int += interior ? 1 : 0;
         if (ok) {
           n_cand++;
@@ -242,6 +258,20 @@ __global__ __launch_bounds__(256) void absorb_fold(AbsorbArgs a) {
   __syncthreads();
   if (threadIdx.x < ELLC_ABSORB_FOLD_COUNTS)
     a.fold_counts[blockIdx.x * (unsigned)ELLC_ABSORB_FOLD_COUNTS + threadIdx.x] = ws[0][threadIdx.x] + ws[1][threadIdx.x] + ws[2][threadIdx.x] + ws[3][threadIdx.x];
+}
+
+// ellc_depth_restart_from_keyframes: every hypothesis EMPTY in front of the fold (all seven fields, unlike propagateDepth's two), so that
+// what absorb_fold leaves is a function of the call's inputs alone
+__global__ __launch_bounds__(256) void absorb_wipe(DepthSoA s, int n) {
+  const int t = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (t >= n) return;
+  s.invDepth[(unsigned)t] = 0.0f;
+  s.variance[(unsigned)t] = 0.0f;
+  s.invDepthSmoothed[(unsigned)t] = -1.0f;
+  s.varianceSmoothed[(unsigned)t] = -1.0f;
+  s.validity[(unsigned)t] = 0;
+  s.blacklisted[(unsigned)t] = 0;
+  s.isValid[(unsigned)t] = (uint8_t)0;
 }
 
 // One block: the sums of absorb_fold's counts and absorb_mark's four, as ellc_absorb_stats, for the host (integers: the order does not matter)

@@ -48,11 +48,19 @@
 //                    copied into tracking-context keyframe slots 2, 3, ..., ellc_depth_absorb_keyframes with the default parameters), so
 //                    the map createKeyFrame propagates next carries it; FILE gets "frameId B" and the fifteen stats per push. The
 //                    tracking context is created with max_keyframes 2 + 43. Without the flag every output file is what it was
+// --restore-connection FILE  (LC mode) FLAG_RESTORE_CONNECTION (main.cpp:252-324): before a frame is tracked the live map is checked
+//                    (globalOptimize::checkConnection); when it has no seeds left the frame is re-localised against the ring
+//                    (globalOptimize::findConnection with restoreConnection on: one batched alignment, one ellc_keyframe_trial_propagate,
+//                    ellc_depth_restart_from_keyframes from the best candidate). On success the pose and match lines of main.cpp:289 / :301
+//                    are written, the frame becomes the active keyframe and the next frame is taken; otherwise the frame is dropped.
+//                    FILE gets one line per lost frame, "frameId n_candidates chosen_kfId n_targets seeds_after rescale" ("frameId
+//                    n_candidates -1 0 0 0" for a frame without a connection). The tracking context is created with max_keyframes 3
+//                    at least. Without the flag every output file is what it was
 // Input is otherwise a header-less file of W*H u8 grey frames (the decode itself always stays outside).
 // In LC mode finished keyframes go through the loop-closure ring (facade class globalOptimize): matching and the batched
 // alignment of a pushed keyframe run on a second thread and a second context beside tracking, joined at the next push
-// (GlobalOptimize.cpp:241 / :161); tracking-loss recovery
-// (findConnection) and the MATLAB rotation averaging are not part of this path.
+// (GlobalOptimize.cpp:241 / :161); tracking-loss recovery (findConnection) runs with --restore-connection only, and the MATLAB
+// rotation averaging is not part of this path.
 #include "../../include/ellc_facade.hpp"
 #include <cstdio>
 #include <fstream>
@@ -64,7 +72,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -74,7 +82,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file, fuse_file, fuse_inputs, absorb_matches;
+  std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -98,6 +106,7 @@ int main(int argc, char** argv) {
     else if (a == "--fuse" && i + 1 < argc) fuse_file = argv[++i];
     else if (a == "--fuse-inputs" && i + 1 < argc) fuse_inputs = argv[++i];
     else if (a == "--absorb-matches" && i + 1 < argc) absorb_matches = argv[++i];
+    else if (a == "--restore-connection" && i + 1 < argc) restore_connection = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return -1; }
   }
@@ -116,6 +125,7 @@ int main(int argc, char** argv) {
     cfg.device = device;   // the tracking context: keyframe slots 0,1 (active / incoming), one alignment at a time; in LC mode the
                            // loop-closure ring and its batches live in a context of their own (facade class globalOptimize)
     if (lc && !absorb_matches.empty()) cfg.max_keyframes = 2 + globalOptimize::MAX_LOOP_ARRAY_LENGTH_SCALE_AVG;   // the candidates' copies (absorbMatches)
+    if (lc && !restore_connection.empty() && cfg.max_keyframes < 3) cfg.max_keyframes = 3;   // the chosen candidate's copy (restoreConnection)
     Runtime rt(cfg);
     struct CommOwner {   // destroyed after the loop, before the runtime
       ellc_comm* c = nullptr;
@@ -181,6 +191,12 @@ int main(int argc, char** argv) {
       if (!globalOptimizeLoop->absorb_file) { std::fprintf(stderr, "cannot open %s\n", absorb_matches.c_str()); return -1; }
       globalOptimizeLoop->absorbMatches = true;   // (pushToArray turns the Sim(3) refinement on for its batch)
     }
+    std::ofstream restore_file;
+    if (lc && !restore_connection.empty()) {
+      restore_file.open(restore_connection.c_str());
+      if (!restore_file) { std::fprintf(stderr, "cannot open %s\n", restore_connection.c_str()); return -1; }
+      globalOptimizeLoop->restoreConnection = true;
+    }
     std::vector<std::unique_ptr<frame>> frameptr_vector;
     frame* activeKeyFrame = nullptr;
     std::vector<uint8_t> buf(bgr ? (size_t)W * H * 48 : (size_t)W * H);
@@ -206,6 +222,42 @@ int main(int argc, char** argv) {
         int temp_frame_no;
         initialize_pose_file >> temp_frame_no >> initial_pose[0] >> initial_pose[1] >> initial_pose[2] >> initial_pose[3] >> initial_pose[4] >> initial_pose[5];
         if (!initialize_pose_file) { std::fprintf(stderr, "initial-pose file ends before frame %d\n", frame_counter); return -1; }
+      }
+      if (restore_file.is_open()) {   // main.cpp:252-324
+        globalOptimize& g = *globalOptimizeLoop;
+        g.checkConnection(&currentDepthMap);
+        if (g.connectionLost) {
+          g.findConnection(cur);
+          const globalOptimize::RestoreRecord& r = g.lastRestore;
+          if (!g.connectionLost) {   // a new connection: the frame becomes the active keyframe
+            int n_targets = 0;
+            for (size_t b = 0; b < r.ids.size(); b++)
+              if (r.ids[b] == r.chosen) n_targets = r.records[b].n_targets;
+            restore_file << (cur->frameId + rt.BATCH_START_ID - 1) << " " << r.ids.size() << " " << (r.chosenFrameId + rt.BATCH_START_ID - 1) << " " << n_targets
+                         << " " << r.seedsAfter << " " << r.rescaleFactor << "\n";
+            restore_file.flush();
+            currentDepthMap = *g.temp_depthMap;   // :267
+            const float seeds_found = currentDepthMap.calculate_no_of_Seeds();
+            const int id = cur->frameId + rt.BATCH_START_ID - 1, kid = activeKeyFrame->frameId + rt.BATCH_START_ID - 1;
+            pose_file_orig << id << " " << kid << " " << cur->poseWrtWorld[0] << " " << cur->poseWrtWorld[1] << " " << cur->poseWrtWorld[2] << " "
+                           << cur->poseWrtWorld[3] << " " << cur->poseWrtWorld[4] << " " << cur->poseWrtWorld[5] << " " << activeKeyFrame->rescaleFactor
+                           << " " << seeds_found << "\n";   // :289
+            if (cur->frameId % KEYFRAME_PROPAGATE_INTERVAL == 0)   // :296-301
+              match_file << id << " " << kid << " " << cur->poseWrtOrigin[0] << " " << cur->poseWrtOrigin[1] << " " << cur->poseWrtOrigin[2] << " "
+                         << cur->poseWrtOrigin[3] << " " << cur->poseWrtOrigin[4] << " " << cur->poseWrtOrigin[5] << " " << activeKeyFrame->rescaleFactor
+                         << " " << seeds_found << " " << "0" << " " << "0" << " " << "0" << "\n";
+            currentDepthMap.keyFrame = cur;   // :307-308
+            activeKeyFrame = cur;
+            delete g.temp_depthMap;
+            g.temp_depthMap = nullptr;
+            frameptr_vector.erase(frameptr_vector.begin(), frameptr_vector.end() - 1);   // keep only the new keyframe
+            continue;   // :314
+          }
+          restore_file << (cur->frameId + rt.BATCH_START_ID - 1) << " " << r.ids.size() << " -1 0 0 0\n";
+          restore_file.flush();
+          frameptr_vector.pop_back();   // :319-322: the frame is of no use
+          continue;
+        }
       }
       // a frame that switches the keyframe (main.cpp:404) is aligned on its own; with --fused every other frame goes through the
       // fused call: alignment + observe + regularise + export as one device sequence (TrackFrameAndObserve)

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 17   /* ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 18   /* ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -476,6 +476,76 @@ typedef struct {      /* 16 x int32 = 64 bytes */
 
 ellc_status ellc_depth_absorb_keyframes(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
                                         const ellc_absorb_params* params, ellc_absorb_stats* out /* may be NULL */);
+
+/* ---- trial propagation records and a map restart (v18) -------------------------------------------------------------
+ * What a tracker that has LOST its map needs (main.cpp:252-324, GlobalOptimize.cpp:717-943): a score per candidate keyframe, and the
+ * live map re-seated on a new keyframe from keyframe slots, starting empty.
+ *
+ * ellc_keyframe_trial_propagate answers, for B (source, destination, transform) triples in one call and without touching the live
+ * map: "if this keyframe slot's map were propagated into that image at this transform, how much map would there be?" Request b reads
+ * keyframe slot src_kf_slots[b] at level 0 (depth, variance, image); the destination is slot dst_slots[b], a keyframe slot if
+ * dst_is_keyframe == 1 and a frame slot if 0, of which only the level-0 image is needed (no depth); T = T12 + 12 * b takes the source's
+ * camera coordinates into the destination's. Slots may repeat. The rule is steps 1-4 of ellc_depth_absorb_keyframes with the
+ * destination's level-0 image and maxAbsGradient plane (ellc_get_max_gradient) in the place of K's: a source pixel takes part iff
+ * ellc_keyframe_map_points would keep it (n_kept); its candidate is ellc_keyframe_render_depth's, with the same drops (n_in_view); the
+ * interior bound of step 3 (n_interior). For EVERY interior pixel - the four taps exist there - g is the destination's maxAbsGradient
+ * at the TARGET, Iw the bilinear value of step 4 and r = Iw - Is: n_low_grad counts g < 5.0f, sum_r2 adds (double)(r * r) and
+ * sum_abs_r adds (double)|r|, whether or not the gate is on. photo_gate only decides whether step 4 drops candidates: n_candidates
+ * counts the survivors of steps 1-4, n_targets the DISTINCT target pixels among them.
+ *   n_targets is the number of hypotheses the fold would CREATE from this request alone in an empty map: n_created == targets_hit ==
+ * n_valid_after of ellc_depth_absorb_keyframes of this one request, same gate and filter, into a wiped state. 100 * n_targets / (W * H)
+ * is the seeds figure before regularisation.
+ *   Record b is a function of the intrinsics, the two slots' planes, T, the filter and photo_gate ALONE: the pixels are partitioned by
+ * the level's size (2048-pixel tiles, 256 threads, eight pixels a thread), partial sums are combined in a fixed order in double; B,
+ * the position in the batch, the other requests, cfg.arith, cfg.grid_batch and whatever else is in flight do not enter it, and a shard
+ * of a batch gives the bytes of the whole batch. Distinct targets are counted through one bit per destination pixel and request in
+ * device scratch (an integer atomic OR: the count does not depend on the arrival order); requests go to the device in groups whose
+ * bitmaps fit 64 MB, which cannot enter a record either.
+ *   Synchronous, ordered like every other non-batch entry point. Builds the destination's maxAbsGradient plane where it is not built
+ * yet, as the absorb does for K, and writes nothing else that belongs to a slot. 1 <= B <= 2048 (not bounded by max_keyframes). A
+ * refused call changes nothing and leaves `out` untouched.
+ * ELLC_ERR_BAD_ARG: B out of range, a slot out of range, a NULL pointer, more than 2^24 pixels, the filter errors of
+ * ellc_keyframe_map_points, photo_gate or dst_is_keyframe outside 0..1;
+ * ELLC_ERR_NOT_READY: a source without image or depth, a destination without image. */
+typedef struct {            /* 48 bytes, every field naturally aligned */
+  double  sum_r2;           /* sum of (double)(r * r) over the pixels counted in n_interior */
+  double  sum_abs_r;        /* sum of (double)|r| over the same pixels */
+  int32_t n_kept;           /* source pixels ellc_keyframe_map_points would keep under `filter` */
+  int32_t n_in_view;        /* of those, pixels with a candidate (ellc_keyframe_render_depth's rule and drops) */
+  int32_t n_interior;       /* of those, inside the bound of ellc_depth_absorb_keyframes step 3 */
+  int32_t n_low_grad;       /* of those, g < 5.0f (counted whether or not the gate is on) */
+  int32_t n_candidates;     /* survivors of absorb's steps 1-4 with this destination in the role of K */
+  int32_t n_targets;        /* DISTINCT target pixels among the candidates */
+  int32_t reserved[2];      /* 0 */
+} ellc_trial_propagation;
+
+ellc_status ellc_keyframe_trial_propagate(ellc_ctx* ctx, int B, const int* src_kf_slots, int dst_is_keyframe, const int* dst_slots,
+                                          const float* T12, const ellc_map_filter* filter, int photo_gate, ellc_trial_propagation* out);
+
+/* ellc_depth_restart_from_keyframes: depthMap::createKeyFrame (DepthPropagation.cpp:1765-1782) with propagateDepth replaced by the
+ * fold of ellc_depth_absorb_keyframes from B keyframe slots into an EMPTY map. new_kf_slot holds an image, is NOT among kf_slots and
+ * becomes the depth map's keyframe K; T = T12 + 12 * b takes slot kf_slots[b]'s camera coordinates into new_kf_slot's. The context
+ * needs no state and no depth-map keyframe beforehand: the call can START a map.
+ *   1. Wipe. Every hypothesis becomes isValid = 0, blacklisted = 0, validity_counter = 0, invDepth = 0, variance = 0, both smoothed
+ *      fields -1.0f (all seven fields, unlike propagateDepth's two): nothing of an earlier state, NaNs included, reaches the result.
+ *   2. Fold. The B requests are folded exactly as ellc_depth_absorb_keyframes folds them (steps 1-6 there: same rule, same order, same
+ *      stats; n_valid_before == 0).
+ *   3. params->finalise == 0: that is all; the smoothed fields of touched targets are -1, the caller regularises, *rescale_factor = 1.
+ *      finalise == 1: createKeyFrame's tail as ellc_depth_create_keyframe runs it - regularise with occlusion removal, fill + regularise,
+ *      makeInvDepthOne, the export into new_kf_slot's planes; *rescale_factor (may be NULL) receives makeInvDepthOne's factor.
+ *   With finalise == 1 the state, new_kf_slot's planes on every level and the factor are, bit for bit, what ellc_depth_set_keyframe(
+ * new_kf_slot), ellc_depth_set_state(the wiped planes), ellc_depth_absorb_keyframes(finalise = 0), ellc_depth_regularize(1),
+ * ellc_depth_fill_holes, ellc_depth_regularize(0), ellc_depth_make_inv_depth_one and ellc_depth_update_depth_image leave; with
+ * finalise == 0, what the first three leave - without seven planes travelling from the host.
+ *   Validation, the pass that counts the candidates and the host's read of their number all come BEFORE anything of the state or of the
+ * depth map's keyframe is touched: a refused call changes nothing, ELLC_ERR_CAPACITY included. A device error part-way leaves the depth
+ * map not ready, as in ellc_depth_create_keyframe. Synchronous, ordered like every other non-batch entry point.
+ * ELLC_ERR_BAD_ARG: everything ellc_depth_absorb_keyframes refuses, new_kf_slot out of range or among the sources;
+ * ELLC_ERR_NOT_READY: a source slot without image or depth, new_kf_slot without an image;
+ * ELLC_ERR_CAPACITY: more than 2^31 - 1 candidates. */
+ellc_status ellc_depth_restart_from_keyframes(ellc_ctx* ctx, int new_kf_slot, int B, const int* kf_slots, const float* T12,
+                                              const ellc_map_filter* filter, const ellc_absorb_params* params,
+                                              float* rescale_factor /* may be NULL */, ellc_absorb_stats* out /* may be NULL */);
 
 /* ---- one keyframe's map against another's (v14) ------------------------------------------------------------------
  * The geometric check of a loop closure, and the scale between two maps: request b compares keyframe slot src_kf_slots[b] with slot

@@ -52,6 +52,14 @@ ellc_status ellc_profile_fuse_depth(ellc_ctx* ctx, int B, const int* kf_slots, c
 ellc_status ellc_profile_depth_absorb(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
                                       const ellc_absorb_params* params, ellc_absorb_stats* out, float* launches_ms);
 
+/* ellc_keyframe_trial_propagate with the number of requests per launch forced (max_group_requests >= 1; 0: as many as the bitmaps'
+ * 64 MB hold, the product call's choice) and HIP events around its launches (the preset of the bitmaps, trial_pass, trial_finish, per
+ * group): launches_ms receives their device time, without the staging copy in front. Everything else as the product call: the records
+ * do not depend on the split. */
+ellc_status ellc_profile_trial_propagate(ellc_ctx* ctx, int B, const int* src_kf_slots, int dst_is_keyframe, const int* dst_slots, const float* T12,
+                                         const ellc_map_filter* filter, int photo_gate, ellc_trial_propagation* out, int max_group_requests,
+                                         float* launches_ms);
+
 /* ellc_keyframe_depth_consistency with HIP events around its launches (consist_pass, consist_finish): launches_ms receives their
  * device time, without the staging copy in front. Everything else as the product call. */
 ellc_status ellc_profile_depth_consistency(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,

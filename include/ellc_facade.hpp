@@ -500,11 +500,48 @@ class globalOptimize {
   // ---- tracking-loss recovery (FLAG_RESTORE_CONNECTION, ExternVariable.h:176: off as shipped; main.cpp:252-324) -------------------
   // GlobalOptimize.cpp:934-943: the connection is lost when the depth map has no seeds left (MIN_SEEDS_FOR_CONNECTION_LOST = 0, ExternVariable.h:171)
   static constexpr float MIN_SEEDS_FOR_CONNECTION_LOST = 0.0f;
-  depthMap* temp_depthMap = nullptr;   // the depth map a recovered connection would hand to main (main.cpp:270); never set as shipped
-  void checkConnection(depthMap* currentDepthMap) { connectionLost = currentDepthMap->calculate_no_of_Seeds() <= MIN_SEEDS_FOR_CONNECTION_LOST; }
-  // GlobalOptimize.cpp:717-760 AS SHIPPED: waits for the match thread, pushes the stray test frame (no depth map) into the ring at
-  // currentArrayId — histogram, ids, image — and returns: the search that follows in the source sits behind an unconditional return
-  // (:759), so connectionLost stays as checkConnection left it and temp_depthMap stays null.
+  depthMap* temp_depthMap = nullptr;   // the depth map a recovered connection hands to main (main.cpp:270); never set while restoreConnection is off
+  void checkConnection(depthMap* currentDepthMap) {
+    checkedDepthMap_ = currentDepthMap;
+    connectionLost = currentDepthMap->calculate_no_of_Seeds() <= MIN_SEEDS_FOR_CONNECTION_LOST;
+  }
+  // FLAG_RESTORE_CONNECTION. Off (the default), findConnection is GlobalOptimize.cpp:717-760 AS SHIPPED (below). On, it goes on with the
+  // search of :760-913 as ONE batch instead of one candidate after the other:
+  //   (a) the candidates are every ring entry findMatch(..., strayFlag = true) hands out, collected by the loop of :780-913 - with the
+  //       stray flag the source takes every valid, non-stray entry of the match window that is more than MIN_MATCH_DIFFERENCE frames
+  //       older, whatever its histogram distance (:365) and without the view-angle test;
+  //   (b) the test frame is aligned against all of them from the zero pose (:849-864) in the ring context, as findMatchParallel runs its batch;
+  //   (c) ONE ellc_keyframe_trial_propagate of all candidates into the test frame (ring frame slot 0): T = the top three rows of
+  //       exp(pose_b), the gate on, the filter of ellc_main --map;
+  //   (d) they are tried in descending n_targets, ties to the lower ring index; a candidate with n_targets == 0 is skipped;
+  //   (e) each in turn: its ring slot is copied into keyframe slot 2 of the tracking context (which therefore needs max_keyframes >= 3),
+  //       the test frame is promoted to the tracking context's other keyframe slot, ellc_depth_restart_from_keyframes (B = 1, the default
+  //       parameters) re-seats the live map on it, and checkConnection decides; the first that leaves the connection not lost is kept.
+  //       B = 1 on purpose: every ring map carries a scale of its own (makeInvDepthOne) and the lost frame has no depth to reconcile
+  //       two of them against;
+  //   (f) on success the test frame's poses are what GetImagePoseEstimate sets against the matched keyframe, then - as
+  //       temp_depthMap->createKeyFrame(testFrame) leaves them (:890, DepthPropagation.cpp:1772-1789) - it is a keyframe with the
+  //       restart's rescale factor and a zero poseWrtOrigin; connectionLost is false and temp_depthMap is the depth map main.cpp:262-314
+  //       takes over. On failure connectionLost stays true, temp_depthMap stays null and the tracking context's depth map sits on the
+  //       keyframe it sat on before, empty. Either way the stray entry is reset at the end (:919).
+  // lastRestore keeps what the search saw.
+  struct RestoreRecord {
+    int frameId = 0;
+    std::vector<int> ids, slots;                  // ring array ids / ring keyframe slots of the candidates, in the order findMatch handed them out
+    std::vector<float> poses;                     // [candidates][6]: the test frame w.r.t. each candidate, as the batch returned them
+    std::vector<float> T;                         // [candidates][12]: candidate camera -> test frame camera, as passed to the library
+    std::vector<ellc_trial_propagation> records;  // per candidate
+    std::vector<int> tried;                       // ring array ids in the order their restart was run
+    int chosen = -1;                              // the ring array id the map was restarted from, -1: none
+    int chosenFrameId = -1, newKeyframeSlot = -1;
+    ellc_absorb_stats stats;                      // of the last restart that was run (zeros: none)
+    float rescaleFactor = 0.0f, seedsAfter = 0.0f;
+  };
+  bool restoreConnection = false;
+  RestoreRecord lastRestore;
+  // With restoreConnection off, GlobalOptimize.cpp:717-760 AS SHIPPED: waits for the match thread, pushes the stray test frame (no depth
+  // map) into the ring at currentArrayId — histogram, ids, image — and returns: the search that follows in the source sits behind an
+  // unconditional return (:759), so connectionLost stays as checkConnection left it and temp_depthMap stays null.
   void findConnection(frame* testFrame) {
     join_all();   // :725 t_group.join_all()
     loopFrame& slot = loopFrameArray[currentArrayId];
@@ -521,6 +558,9 @@ class globalOptimize {
     slot.frameId = currentLoopFrame.frameId;
     slot.isValid = currentLoopFrame.isValid;
     std::memcpy(slot.image_histogram, currentLoopFrame.image_histogram, sizeof(slot.image_histogram));
+    if (!restoreConnection) return;
+    searchConnection(testFrame, test);
+    slot.isValid = false; slot.isStray = false; slot.frameId = 0;   // :919 resetArrayElement(currentArrayId)
   }
   ~globalOptimize() {
     try { join_all(); } catch (...) {}
@@ -720,6 +760,101 @@ class globalOptimize {
   std::thread t_group;
   std::string thread_error;
   bool fixed_grids_ = true;
+  depthMap* checkedDepthMap_ = nullptr;   // what checkConnection looked at last: its keyframe's slot is the tracking context's active one
+
+  // findConnection with restoreConnection on, behind the push of the stray frame: steps (a)-(f) above
+  void searchConnection(frame* testFrame, const TestFrame& test) {
+    lastRestore = RestoreRecord();
+    lastRestore.frameId = testFrame->frameId;
+    std::memset(&lastRestore.stats, 0, sizeof(lastRestore.stats));
+    if (rt->cfg.max_keyframes < 3) throw std::runtime_error("restoreConnection: the tracking runtime needs max_keyframes >= 3");
+    // (a) :776-913, the loop alone
+    loopFrameArray[nextArrayId].frameId = testFrame->frameId;
+    lastTestedLoopClosureArrayId = -1;
+    firstTestedLoopClosureArrayId = -1;
+    int num_matches = 0;
+    do {
+      const bool matchFound = findMatch(test, true);
+      if (num_matches > 0 && lastTestedLoopClosureArrayId == firstTestedLoopClosureArrayId) break;
+      if (matchFound) {
+        if (num_matches == 0) firstTestedLoopClosureArrayId = lastTestedLoopClosureArrayId;
+        num_matches++;
+        lastRestore.ids.push_back(loopClosureArrayId);
+        lastRestore.slots.push_back(loopFrameArray[loopClosureArrayId].kf_slot);
+      }
+    } while (lastTestedLoopClosureArrayId != -1);
+    const int B = (int)lastRestore.ids.size();
+    if (B == 0) return;
+    // (b) one batched constant-weight alignment from the zero pose
+    std::vector<int> fr((size_t)B, 0);
+    std::vector<float> init((size_t)B * 6, 0.0f);
+    lastRestore.poses.assign((size_t)B * 6, 0.0f);
+    ring.check(ellc_copy_slot(ring.ctx, 0, 0, 1, test.ring_slot), "ellc_copy_slot");
+    if (fixed_grids_) ring.check(ellc_ctx_set_grid_batch(ring.ctx, lc_grid_bucket(B)), "ellc_ctx_set_grid_batch");
+    ring.check(ellc_align(ring.ctx, B, lastRestore.slots.data(), fr.data(), init.data(), ELLC_MODE_ICA, 0, lastRestore.poses.data(), nullptr, nullptr), "ellc_align");
+    // (c) one trial propagation of all of them into the test frame
+    ellc_map_filter filter;   // the filter of ellc_main --map
+    filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+    lastRestore.T.assign((size_t)B * 12, 0.0f);
+    for (int b = 0; b < B; b++) {
+      float M[16];
+      ellc_se3_exp(&lastRestore.poses[(size_t)b * 6], M);
+      for (int k = 0; k < 12; k++) lastRestore.T[(size_t)b * 12 + k] = M[k];
+    }
+    lastRestore.records.assign((size_t)B, ellc_trial_propagation());
+    ring.check(ellc_keyframe_trial_propagate(ring.ctx, B, lastRestore.slots.data(), 0, fr.data(), lastRestore.T.data(), &filter, 1, lastRestore.records.data()),
+               "ellc_keyframe_trial_propagate");
+    // (d) descending n_targets, ties to the lower ring index
+    std::vector<int> order;
+    for (int b = 0; b < B; b++)
+      if (lastRestore.records[(size_t)b].n_targets > 0) order.push_back(b);
+    const RestoreRecord& lr = lastRestore;
+    std::sort(order.begin(), order.end(), [&lr](int x, int y) {
+      const int nx = lr.records[(size_t)x].n_targets, ny = lr.records[(size_t)y].n_targets;
+      return nx != ny ? nx > ny : lr.ids[(size_t)x] < lr.ids[(size_t)y];
+    });
+    // (e) adopt the first that gives a map
+    const int active = (checkedDepthMap_ && checkedDepthMap_->keyFrame && checkedDepthMap_->keyFrame->kf_slot >= 0) ? checkedDepthMap_->keyFrame->kf_slot : -1;
+    const int ns = active >= 0 ? rt->other_keyframe_slot(active) : 0, copy_slot = 2;
+    ellc_absorb_params params;
+    ellc_absorb_default_params(&params);
+    bool promoted = false;
+    for (size_t q = 0; q < order.size(); q++) {
+      const int b = order[q];
+      const loopFrame& m = loopFrameArray[lastRestore.ids[(size_t)b]];
+      rt->check(ellc_copy_slot_across(rt->ctx, 1, copy_slot, ring.ctx, 1, m.kf_slot), "ellc_copy_slot_across");
+      if (!promoted) rt->check(ellc_keyframe_from_frame(rt->ctx, ns, testFrame->slot), "ellc_keyframe_from_frame");
+      promoted = true;
+      float factor = 1.0f;
+      lastRestore.tried.push_back(lastRestore.ids[(size_t)b]);
+      rt->check(ellc_depth_restart_from_keyframes(rt->ctx, ns, 1, &copy_slot, &lastRestore.T[(size_t)b * 12], &filter, &params, &factor, &lastRestore.stats),
+                "ellc_depth_restart_from_keyframes");
+      depthMap* dm = new depthMap(*rt);
+      dm->keyFrame = testFrame;
+      dm->currentFrame = testFrame;
+      dm->depthScale = factor;
+      lastRestore.rescaleFactor = factor;
+      lastRestore.seedsAfter = dm->calculate_no_of_Seeds();
+      connectionLost = lastRestore.seedsAfter <= MIN_SEEDS_FOR_CONNECTION_LOST;   // checkConnection(temp_depthMap), :896
+      if (connectionLost) { delete dm; continue; }
+      // (f) GetImagePoseEstimate's poses (ImageFunc.cpp:305-306), then createKeyFrame's bookkeeping (:890)
+      const float* pose = &lastRestore.poses[(size_t)b * 6];
+      ellc_concatenate_relative_pose(pose, m.poseWrtOrigin, testFrame->poseWrtOrigin);
+      ellc_concatenate_relative_pose(pose, m.poseWrtWorld, testFrame->poseWrtWorld);
+      testFrame->parentKeyframeId = m.frameId;
+      testFrame->kf_slot = ns;
+      testFrame->isKeyframe = true;
+      testFrame->rescaleFactor = factor;
+      for (int i = 0; i < 6; i++) testFrame->poseWrtOrigin[i] = 0.0f;
+      temp_depthMap = dm;
+      lastRestore.chosen = lastRestore.ids[(size_t)b];
+      lastRestore.chosenFrameId = m.frameId;
+      lastRestore.newKeyframeSlot = ns;
+      return;
+    }
+    // nobody gave a map: the (empty) depth map goes back to the keyframe the caller's depthMap names
+    if (promoted && active >= 0) rt->check(ellc_depth_set_keyframe(rt->ctx, active), "ellc_depth_set_keyframe");
+  }
 
   // :40-100 (the histogram of the copy in the ring context: the same image)
   void calculateImageHistogram(const TestFrame& f) {
@@ -748,8 +883,9 @@ class globalOptimize {
     relative_view_angle = std::acos((v1[0] * v2[0] + v1[1] * v2[1] + v1[2] * v2[2]) / (mag1 * mag2));
     relative_view_angle = (relative_view_angle * 180) / 3.14f;   // sic: 3.14
   }
-  // :274-416 (strayFlag = false)
-  bool findMatch(const TestFrame& currentframe) {
+  // :274-416. strayFlag (findConnection's test frame: it has no pose to compare): no rotation statistics, and every entry that is old
+  // enough is handed out whatever its histogram distance (`matchValue <= MATCH_THRESHOLD || strayFlag`, :365)
+  bool findMatch(const TestFrame& currentframe, bool strayFlag = false) {
     const int RING = MAX_LOOP_ARRAY_LENGTH_SCALE_AVG;
     calculateImageHistogram(currentframe);
     int i;
@@ -771,9 +907,9 @@ class globalOptimize {
       // depth map to GetImagePoseEstimate; unreachable as shipped, FLAG_RESTORE_CONNECTION is off)
       if (!loopFrameArray[i].isStray && currentframe.frameId - loopFrameArray[i].frameId > 8) {   // MIN_MATCH_DIFFERENCE = KEYFRAME_PROPAGATE_INTERVAL
         matchValue = (float)ellc_kl_divergence(loopFrameArray[i].image_histogram, currentLoopFrame.image_histogram, 256);
-        calculateRotationStats(loopFrameArray[i].poseWrtWorld, currentLoopFrame.poseWrtWorld);
-        if (matchValue <= 0.1f) {                       // MATCH_THRESHOLD
-          if (relative_view_angle <= 10.0f) {           // MAX_REL_VIEW_ANGLE
+        if (!strayFlag) calculateRotationStats(loopFrameArray[i].poseWrtWorld, currentLoopFrame.poseWrtWorld);
+        if (matchValue <= 0.1f || strayFlag) {          // MATCH_THRESHOLD
+          if (strayFlag || relative_view_angle <= 10.0f) {   // MAX_REL_VIEW_ANGLE
             isloopClosureDetected = true;
             loopClosureArrayId = i;
             break;
