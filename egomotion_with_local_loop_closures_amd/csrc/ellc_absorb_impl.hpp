@@ -1,12 +1,10 @@
 // ellc_depth_absorb_keyframes (include/ellc_abi.h): the host side of the fold of keyframe slots into the live depth map.
 // Included at the end of ellc_hip.hip, behind ellc_fuse_impl.hpp and ellc_depth_impl.hpp: the render's validation, scratch and staging,
-// the fusion's scratch, scan kernels and list, and the depth map's regularisation and export are used as they are.
+// the fusion's scratch, scan kernels and list, and the depth map's regularisation and export are used as they are (the fold writes the
+// live map, so the render's enqueue / download / write-back steps do not apply).
 #pragma once
-#include "ellc_context.hpp"
+#include "ellc_fuse_impl.hpp"
 #include "ellc_kernels_absorb.hpp"
-#include <climits>
-#include <cmath>
-#include <cstring>
 
 using namespace ellc;
 
@@ -26,33 +24,32 @@ ellc_status absorb_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T1
   if (p->max_fold < 1 || p->max_fold > ELLC_FUSE_MAX_MERGE) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": max_fold out of range");
   if (p->src_validity < 0 || p->src_validity > 255) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": src_validity out of range");
   if (p->photo_gate < 0 || p->photo_gate > 1 || p->finalise < 0 || p->finalise > 1) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": photo_gate / finalise not 0 or 1");
-  ellc_status st = render_validate(c, who, B, kf_slots, T12, 0, f, p->agree_k2, restart_slot, !restart);   // (the new keyframe is no source)
-  if (st != ELLC_OK) return st;
+  ELLC_TRY(render_validate(c, who, B, kf_slots, T12, 0, f, p->agree_k2, restart_slot, !restart));   // (the new keyframe is no source)
   if (restart) {
     if (!c->kf_has_image[restart_slot]) return fail(c, ELLC_ERR_NOT_READY, std::string(who) + ": the new keyframe slot has no image");
   } else if (!c->dm_ready || c->dm_kf_slot < 0)
     return fail(c, ELLC_ERR_NOT_READY, std::string(who) + ": call ellc_depth_set_state and ellc_depth_set_keyframe first");
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
   const int K = restart ? restart_slot : c->dm_kf_slot;
-  if ((st = render_scratch(c)) != ELLC_OK) return st;
-  if ((st = fuse_scratch(c)) != ELLC_OK) return st;
+  ELLC_TRY(render_scratch(c));
+  ELLC_TRY(fuse_scratch(c));
   const size_t n0 = (size_t)c->geom_h[0].n, blocks0 = (n0 + 255) / 256;
   if (!c->absorb_stats_h) {
     if (!c->absorb_block_d) ELLC_HIP(c, hipMalloc(&c->absorb_block_d, (64 + blocks0 * ELLC_ABSORB_FOLD_COUNTS) * sizeof(int)));
     int32_t* sh = nullptr;
-    if ((st = host_alloc(c, &sh, 16)) != ELLC_OK) return st;
+    ELLC_TRY(host_alloc(c, &sh, 16));
     void* da = nullptr;
     ELLC_HIP(c, hipHostGetDevicePointer(&da, sh, 0));
     c->absorb_stats_dev_alias = (int32_t*)da;
     c->absorb_stats_h = sh;
   }
   // K's maxAbsGradient: the gate reads it, and so does the regularisation behind the fold (as ellc_depth_do_regularization builds it)
-  if ((p->photo_gate || p->finalise) && !c->kf_maxgrad_valid[K] && (st = build_maxgrad(c, true, K)) != ELLC_OK) return st;
+  if ((p->photo_gate || p->finalise) && !c->kf_maxgrad_valid[K]) ELLC_TRY(build_maxgrad(c, true, K));
   AbsorbArgs a;
   a.f.r = render_args(c, B, 0, f, p->agree_k2);
-  const size_t mask_words = (size_t)B * (size_t)a.f.r.m.tiles * 32;   // 8 steps x 4 waves per (request, tile)
-  if ((st = fuse_mask_reserve(c, mask_words)) != ELLC_OK) return st;
-  if ((st = render_stage(c, B, kf_slots, T12)) != ELLC_OK) return st;
+  const size_t mask_words = (size_t)B * (size_t)a.f.r.v.tiles * 32;   // 8 steps x 4 waves per (request, tile)
+  ELLC_TRY(fuse_mask_reserve(c, mask_words));
+  ELLC_TRY(render_stage(c, B, kf_slots, T12));
   a.f.mask = c->fuse_mask_d;
   a.f.cursor = c->fuse_cursor_d;
   a.f.tile_sums = c->fuse_tile_sums_d;
@@ -71,19 +68,20 @@ ellc_status absorb_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T1
   a.max_fold = p->max_fold;
   a.photo_gate = p->photo_gate;
   a.src_validity = p->src_validity;
-  const dim3 grd(a.f.r.m.tiles, B), blk(256);
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
+  const dim3 grd(a.f.r.v.tiles, B), blk(256);
+  LaunchTimer t(c, launches_ms);
+  ELLC_TRY(t.begin());
   ELLC_HIP(c, hipMemsetAsync(c->render_agree_d, 0, n0 * 4, c->stream));
   ELLC_HIP(c, hipMemsetAsync(a.mark_counts, 0, 4 * sizeof(int), c->stream));
   hipLaunchKernelGGL(absorb_mark, grd, blk, 0, c->stream, a);
-  hipLaunchKernelGGL(fuse_tile_sums, dim3(a.f.r.m.tiles), blk, 0, c->stream, a.f);
-  hipLaunchKernelGGL(fuse_offsets, dim3(a.f.r.m.tiles), blk, 0, c->stream, a.f);
+  hipLaunchKernelGGL(fuse_tile_sums, dim3(a.f.r.v.tiles), blk, 0, c->stream, a.f);
+  hipLaunchKernelGGL(fuse_offsets, dim3(a.f.r.v.tiles), blk, 0, c->stream, a.f);
   ELLC_HIP(c, hipGetLastError());
   ELLC_HIP(c, hipStreamSynchronize(c->stream));
   const long long total = c->fuse_totals_h[0];
   // nothing of the state has been touched yet
   if (total > (long long)INT_MAX) return fail(c, ELLC_ERR_CAPACITY, std::string(who) + ": more than 2^31 - 1 candidates");
-  if ((st = fuse_list_reserve(c, (size_t)total)) != ELLC_OK) return st;
+  ELLC_TRY(fuse_list_reserve(c, (size_t)total));
   a.f.list = c->fuse_list_d;
   a.f.list_cap = (unsigned)total;
   const int old_slot = c->dm_kf_slot;
@@ -104,19 +102,19 @@ ellc_status absorb_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T1
   hipLaunchKernelGGL(absorb_fold, dim3(a.f.r.blocks), blk, 0, c->stream, a);
   hipLaunchKernelGGL(absorb_finish, dim3(1), blk, 0, c->stream, a);
   if (hipGetLastError() != hipSuccess) return broken(fail(c, ELLC_ERR_HIP, std::string(who) + ": a launch failed"));
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
+  ELLC_TRY(t.end());
   float factor = 1.0f;
   if (p->finalise && restart) {   // createKeyFrame's tail, as ellc_depth_create_keyframe enqueues it
-    if ((st = do_create_keyframe_tail(c, &factor)) != ELLC_OK) return broken(st);
+    const ellc_status st = do_create_keyframe_tail(c, &factor);
+    if (st != ELLC_OK) return broken(st);
   } else if (p->finalise) {   // ellc_depth_do_regularization(ctx, 0) and ellc_depth_update_depth_image(ctx), as they enqueue them
-    if ((st = do_fill_regularize(c, 0)) != ELLC_OK) return st;
-    if ((st = do_update_depth_image(c)) != ELLC_OK) return st;
+    ELLC_TRY(do_fill_regularize(c, 0));
+    ELLC_TRY(do_update_depth_image(c));
   }
   if (hipStreamSynchronize(c->stream) != hipSuccess) return broken(fail(c, ELLC_ERR_HIP, std::string(who) + ": the stream failed"));
   if (rescale_factor) *rescale_factor = factor;
   if (out) std::memcpy(out, c->absorb_stats_h, sizeof(ellc_absorb_stats));
-  if (launches_ms) ELLC_HIP(c, hipEventElapsedTime(launches_ms, c->ev0, c->ev1));
-  return ELLC_OK;
+  return t.read();
 }
 
 }  // namespace
@@ -147,10 +145,7 @@ ellc_status ellc_depth_restart_from_keyframes(ellc_ctx* c, int new_kf_slot, int 
 #ifdef ELLC_DIAG_ABI
 ellc_status ellc_profile_depth_absorb(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
                                       const ellc_absorb_params* params, ellc_absorb_stats* out, float* launches_ms) {
-  float ms = 0.0f;
-  const ellc_status s = absorb_impl(c, B, kf_slots, T12, filter, params, out, &ms);
-  if (launches_ms) *launches_ms = ms;
-  return s;
+  return ring_profiled(launches_ms, [&](float* ms) { return absorb_impl(c, B, kf_slots, T12, filter, params, out, ms); });
 }
 #endif   // ELLC_DIAG_ABI
 

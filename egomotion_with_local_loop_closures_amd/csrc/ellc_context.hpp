@@ -70,6 +70,17 @@ inline GraphKey graph_key(const LaunchPlan& p, int grid_batch) {
   return GraphKey{p.B, p.nu, p.mode, p.save_weights ? 1 : 0, p.continuation, p.track, p.pollable, p.adaptive_first, grid_batch, p.dense, p.need, p.skip_count, p.set, p.row_taps};
 }
 
+// Staging and scratch of a call that reduces B (source, destination) pairs to one record each (ellc_ring_common.hpp: pair_reserve,
+// pair_run, pair_free). Not from the arena: they grow with the largest call.
+struct PairScratch {
+  int cap = 0;                                          // requests the staging holds
+  void *stage_h = nullptr, *stage_d = nullptr;          // pinned: [cap] requests as the pass kernel reads them, and the device copy
+  void *out_h = nullptr, *out_dev_alias = nullptr;      // pinned: [cap] records (the finish kernel writes them)
+  void* partials_d = nullptr;                           // [requests of one launch][tiles of the level] partial records
+  size_t partials_cap = 0;                              //   records it holds
+};
+void pair_free(PairScratch& s);
+
 }  // namespace ellc
 
 struct ellc_ctx {
@@ -255,29 +266,11 @@ struct ellc_ctx {
   // ellc_depth_absorb_keyframes: the render's and the fusion's scratch above and, of its own, allocated by the first call:
   void* absorb_block_d = nullptr;           // [64] words for absorb_mark's four counts, then [ceil(W*H / 256)][11] outcome counts per block of absorb_fold
   int32_t *absorb_stats_h = nullptr, *absorb_stats_dev_alias = nullptr;   // pinned: the sixteen words of ellc_absorb_stats (absorb_finish)
-  // ellc_keyframe_depth_consistency: staging and scratch of its own (not from the arena: they grow with the largest call)
-  int consist_cap = 0;                      // requests the staging holds
-  int* consist_stage_h = nullptr;           // pinned: [cap] source slots, [cap] destination slots, [cap][12] f32 transforms
-  int* consist_stage_d = nullptr;           //   and its device copy
-  void *consist_out_h = nullptr, *consist_out_dev_alias = nullptr;   // pinned: [cap] records (consist_finish writes them)
-  void* consist_partials_d = nullptr;       // [requests of one launch][tiles of the level] partial records
-  size_t consist_partials_cap = 0;          //   records it holds
-  // ellc_keyframe_trial_propagate: the same, of its own
-  int trial_cap = 0;                        // requests the staging holds
-  void* trial_req_h = nullptr;              // pinned: [cap] TrialReq (source slot, destination planes, transform)
-  void* trial_req_d = nullptr;              //   and its device copy
-  void *trial_out_h = nullptr, *trial_out_dev_alias = nullptr;   // pinned: [cap] records (trial_finish writes them)
-  void* trial_partials_d = nullptr;         // [requests of one launch][tiles of level 0] partial records
-  size_t trial_partials_cap = 0;            //   records it holds
+  // ellc_keyframe_depth_consistency, ellc_keyframe_sim3_step / _align, ellc_keyframe_trial_propagate: a PairScratch each, and the trial
+  // call's bitmaps
+  ellc::PairScratch consist, sim3, trial;
   unsigned* trial_bits_d = nullptr;         // [requests of one launch][ceil(W*H / 32)] one bit per target pixel
   size_t trial_bits_cap = 0;                //   words it holds
-  // ellc_keyframe_sim3_step / ellc_keyframe_sim3_align: the same, of their own
-  int sim3_cap = 0;
-  int* sim3_stage_h = nullptr;
-  int* sim3_stage_d = nullptr;
-  void *sim3_out_h = nullptr, *sim3_out_dev_alias = nullptr;
-  void* sim3_partials_d = nullptr;
-  size_t sim3_partials_cap = 0;
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

@@ -1,7 +1,8 @@
 // ellc_keyframe_fuse_depth (include/ellc_abi.h): the host side of the fused view.
-// Included at the end of ellc_hip.hip, behind ellc_render_impl.hpp: the render's validation, scratch, staging and kernels are used as they are.
+// Included at the end of ellc_hip.hip, behind ellc_render_impl.hpp: the render's validation, scratch, staging and its enqueue / download /
+// write-back steps are used as they are.
 #pragma once
-#include "ellc_context.hpp"
+#include "ellc_render_impl.hpp"
 #include "ellc_kernels_fuse.hpp"
 #include <climits>
 
@@ -36,29 +37,15 @@ ellc_status fuse_scratch(ellc_ctx* c) {
   return ELLC_OK;
 }
 
-// the bit per source pixel of every request: grown in front of a call's first enqueue (hipFree waits for what still reads the old one)
+// the bit per source pixel of every request: grown in front of a call's first enqueue
 ellc_status fuse_mask_reserve(ellc_ctx* c, size_t mask_words) {
-  if (mask_words > c->fuse_mask_cap) {
-    if (c->fuse_mask_d) (void)hipFree(c->fuse_mask_d);
-    c->fuse_mask_d = nullptr;
-    c->fuse_mask_cap = 0;
-    ELLC_HIP(c, hipMalloc(&c->fuse_mask_d, mask_words * sizeof(unsigned long long)));
-    c->fuse_mask_cap = mask_words;
-  }
-  return ELLC_OK;
+  return dev_grow(c, (void**)&c->fuse_mask_d, &c->fuse_mask_cap, mask_words, sizeof(unsigned long long));
 }
 
-// the list of candidate ids: grown once the call's total is known (nothing of this context is running: the stream was synchronised)
+// the list of candidate ids: grown once the call's total is known (nothing of this context is running: the stream was synchronised).
+// Headroom of a half: totals that creep up from call to call do not allocate every time.
 ellc_status fuse_list_reserve(ellc_ctx* c, size_t total) {
-  if (total > c->fuse_list_cap) {
-    if (c->fuse_list_d) (void)hipFree(c->fuse_list_d);
-    c->fuse_list_d = nullptr;
-    c->fuse_list_cap = 0;
-    const size_t cap = total + total / 2;   // headroom: totals that creep up from call to call do not allocate every time
-    ELLC_HIP(c, hipMalloc(&c->fuse_list_d, cap * sizeof(uint32_t)));
-    c->fuse_list_cap = cap;
-  }
-  return ELLC_OK;
+  return dev_grow(c, (void**)&c->fuse_list_d, &c->fuse_list_cap, total, sizeof(uint32_t), total / 2);
 }
 
 // launches_ms (the diagnostic hook only): device time from the preset of the keys to the end of fuse_finish, HIP events around them. The
@@ -70,18 +57,14 @@ ellc_status fuse_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float
   const ellc_status ok = render_validate(c, "ellc_keyframe_fuse_depth", B, kf_slots, T12, level, f, agree_k2, dst, true);
   if (ok != ELLC_OK) return ok;
   if (max_merge < 0 || max_merge > ELLC_FUSE_MAX_MERGE) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_fuse_depth: max_merge out of range");
-  const LevelGeom& g = c->geom_h[level];
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
-  ellc_status st = render_scratch(c);
-  if (st != ELLC_OK) return st;
-  const size_t n0 = (size_t)c->geom_h[0].n, n = (size_t)g.n;
-  if ((st = fuse_scratch(c)) != ELLC_OK) return st;
+  ELLC_TRY(render_scratch(c));
+  ELLC_TRY(fuse_scratch(c));
   FuseArgs a;
   a.r = render_args(c, B, level, f, agree_k2);
-  const size_t mask_words = (size_t)B * (size_t)a.r.m.tiles * 32;   // 8 steps x 4 waves per (request, tile)
-  if (max_merge > 0 && (st = fuse_mask_reserve(c, mask_words)) != ELLC_OK) return st;
-  st = render_stage(c, B, kf_slots, T12);
-  if (st != ELLC_OK) return st;
+  const size_t mask_words = (size_t)B * (size_t)a.r.v.tiles * 32;   // 8 steps x 4 waves per (request, tile)
+  if (max_merge > 0) ELLC_TRY(fuse_mask_reserve(c, mask_words));
+  ELLC_TRY(render_stage(c, B, kf_slots, T12));
   a.mask = c->fuse_mask_d;
   a.cursor = c->fuse_cursor_d;
   a.tile_sums = c->fuse_tile_sums_d;
@@ -91,23 +74,21 @@ ellc_status fuse_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float
   a.block_counts = c->fuse_block_counts_d;
   a.totals = c->fuse_totals_dev_alias;
   a.max_merge = max_merge;
-  const dim3 grd(a.r.m.tiles, B), blk(256);
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
-  ELLC_HIP(c, hipMemsetAsync(c->render_keys_d, 0xff, n * 8, c->stream));
-  hipLaunchKernelGGL(render_min, grd, blk, 0, c->stream, a.r);
-  hipLaunchKernelGGL(render_resolve, dim3(a.r.blocks), blk, 0, c->stream, a.r);
-  hipLaunchKernelGGL(render_finish, dim3(1), blk, 0, c->stream, a.r);
+  const dim3 grd(a.r.v.tiles, B), blk(256);
+  LaunchTimer t(c, launches_ms);
+  ELLC_TRY(t.begin());
+  ELLC_TRY(render_enqueue_view(c, a.r, grd));
   if (max_merge == 0) hipLaunchKernelGGL(render_agree, grd, blk, 0, c->stream, a.r);   // (without a merge nothing reads a list: the render's planes go out as they are)
   if (max_merge > 0) {
     hipLaunchKernelGGL(fuse_agree, grd, blk, 0, c->stream, a);
-    hipLaunchKernelGGL(fuse_tile_sums, dim3(a.r.m.tiles), blk, 0, c->stream, a);
-    hipLaunchKernelGGL(fuse_offsets, dim3(a.r.m.tiles), blk, 0, c->stream, a);
+    hipLaunchKernelGGL(fuse_tile_sums, dim3(a.r.v.tiles), blk, 0, c->stream, a);
+    hipLaunchKernelGGL(fuse_offsets, dim3(a.r.v.tiles), blk, 0, c->stream, a);
     ELLC_HIP(c, hipGetLastError());
     ELLC_HIP(c, hipStreamSynchronize(c->stream));
     const long long total = c->fuse_totals_h[0];
     // nothing of a slot has been touched yet
     if (total > (long long)INT_MAX) return fail(c, ELLC_ERR_CAPACITY, "ellc_keyframe_fuse_depth: more than 2^31 - 1 agreeing candidates");
-    if ((st = fuse_list_reserve(c, (size_t)total)) != ELLC_OK) return st;
+    ELLC_TRY(fuse_list_reserve(c, (size_t)total));
     a.list = c->fuse_list_d;
     a.list_cap = (unsigned)total;
     if (total > 0) hipLaunchKernelGGL(fuse_scatter, grd, blk, 0, c->stream, a);
@@ -115,30 +96,15 @@ ellc_status fuse_depth_impl(ellc_ctx* c, int B, const int* kf_slots, const float
   hipLaunchKernelGGL(fuse_merge, dim3(a.r.blocks), blk, 0, c->stream, a);
   hipLaunchKernelGGL(fuse_finish, dim3(1), blk, 0, c->stream, a);
   ELLC_HIP(c, hipGetLastError());
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
-  if (depth) ELLC_HIP(c, hipMemcpyAsync(depth, c->render_depth_d, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (var) ELLC_HIP(c, hipMemcpyAsync(var, c->render_var_d, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (source) ELLC_HIP(c, hipMemcpyAsync(source, c->render_source_d, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (agree) ELLC_HIP(c, hipMemcpyAsync(agree, c->render_agree_d, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (merged) ELLC_HIP(c, hipMemcpyAsync(merged, c->fuse_merged_d, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (intensity) ELLC_HIP(c, hipMemcpyAsync(intensity, c->render_intensity_d, n, hipMemcpyDeviceToHost, c->stream));
-  if (dst >= 0) {   // as the render's destination: the planes go from device to device, behind every kernel that read the slot
-    const KfLevelDev& k = c->kf_tab_h[dst];
-    invalidate_records(c, dst);
-    ELLC_HIP(c, hipMemcpyAsync(k.depth, c->render_depth_d, n0 * 4, hipMemcpyDeviceToDevice, c->stream));
-    ELLC_HIP(c, hipMemcpyAsync(k.var, c->render_var_d, n0 * 4, hipMemcpyDeviceToDevice, c->stream));
-    // a fused depth is > 0 exactly where a target has a winner (1 / id_t of positive terms): the count render_finish left
-    const ellc_status s = finish_depth_planes(c, dst, [&]() {
-      (void)hipStreamSynchronize(c->stream);
-      return (size_t)*c->render_nvalid_h;
-    });
-    if (s != ELLC_OK) return s;
-  }
+  ELLC_TRY(t.end());
+  ELLC_TRY(render_download(c, (size_t)a.r.n, depth, var, source, agree, intensity));
+  if (merged) ELLC_HIP(c, hipMemcpyAsync(merged, c->fuse_merged_d, (size_t)a.r.n * 4, hipMemcpyDeviceToHost, c->stream));
+  // a fused depth is > 0 exactly where a target has a winner (1 / id_t of positive terms), as a rendered one
+  if (dst >= 0) ELLC_TRY(render_store_dst(c, dst));
   ELLC_HIP(c, hipStreamSynchronize(c->stream));
   if (n_valid) *n_valid = *c->render_nvalid_h;
   if (n_fused) *n_fused = (int)c->fuse_totals_h[1];
-  if (launches_ms) ELLC_HIP(c, hipEventElapsedTime(launches_ms, c->ev0, c->ev1));
-  return ELLC_OK;
+  return t.read();
 }
 
 }  // namespace
@@ -156,11 +122,10 @@ ellc_status ellc_keyframe_fuse_depth(ellc_ctx* c, int B, const int* kf_slots, co
 ellc_status ellc_profile_fuse_depth(ellc_ctx* c, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* filter,
                                     float agree_k2, int max_merge, int dst_kf_slot, float* depth, float* var, int32_t* source, int32_t* agree,
                                     int32_t* merged, uint8_t* intensity, int* n_valid, int* n_fused, float* launches_ms) {
-  float ms = 0.0f;
-  const ellc_status s = fuse_depth_impl(c, B, kf_slots, T12, level, filter, agree_k2, max_merge, dst_kf_slot, depth, var, source, agree, merged,
-                                        intensity, n_valid, n_fused, &ms);
-  if (launches_ms) *launches_ms = ms;
-  return s;
+  return ring_profiled(launches_ms, [&](float* ms) {
+    return fuse_depth_impl(c, B, kf_slots, T12, level, filter, agree_k2, max_merge, dst_kf_slot, depth, var, source, agree, merged, intensity, n_valid,
+                           n_fused, ms);
+  });
 }
 #endif   // ELLC_DIAG_ABI
 

@@ -1240,19 +1240,10 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   if (c->fuse_list_d) (void)hipFree(c->fuse_list_d);
   if (c->fuse_mask_d) (void)hipFree(c->fuse_mask_d);
   if (c->absorb_block_d) (void)hipFree(c->absorb_block_d);
-  if (c->consist_partials_d) (void)hipFree(c->consist_partials_d);
-  if (c->consist_stage_d) (void)hipFree(c->consist_stage_d);
-  if (c->consist_stage_h) (void)hipHostFree(c->consist_stage_h);
-  if (c->consist_out_h) (void)hipHostFree(c->consist_out_h);
-  if (c->trial_partials_d) (void)hipFree(c->trial_partials_d);
+  ellc::pair_free(c->consist);
+  ellc::pair_free(c->sim3);
+  ellc::pair_free(c->trial);
   if (c->trial_bits_d) (void)hipFree(c->trial_bits_d);
-  if (c->trial_req_d) (void)hipFree(c->trial_req_d);
-  if (c->trial_req_h) (void)hipHostFree(c->trial_req_h);
-  if (c->trial_out_h) (void)hipHostFree(c->trial_out_h);
-  if (c->sim3_partials_d) (void)hipFree(c->sim3_partials_d);
-  if (c->sim3_stage_d) (void)hipFree(c->sim3_stage_d);
-  if (c->sim3_stage_h) (void)hipHostFree(c->sim3_stage_h);
-  if (c->sim3_out_h) (void)hipHostFree(c->sim3_out_h);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
   if (c->ingest_bgr) (void)hipFree(c->ingest_bgr);
   for (int p = 0; p < ellc_ctx::SETS; p++)
@@ -2738,6 +2729,7 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 
 #include "ellc_depth_impl.hpp"
 #include "ellc_ingest_impl.hpp"
+#include "ellc_ring_common.hpp"
 #include "ellc_map_impl.hpp"
 #include "ellc_render_impl.hpp"
 #include "ellc_fuse_impl.hpp"

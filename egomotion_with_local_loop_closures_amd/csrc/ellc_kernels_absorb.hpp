@@ -70,13 +70,13 @@ __device__ __forceinline__ bool absorb_gate(const LevelGeom& g, const uint8_t* k
 __global__ __launch_bounds__(256) void absorb_mark(AbsorbArgs a) {
   const RenderArgs& ra = a.f.r;
   const unsigned b = blockIdx.y;
-  const KfLevelDev& K = ra.m.kf_tab[ra.m.level * ra.m.max_kf + map_slot(ra.m, b)];
-  const LevelGeom& g = ra.m.geom[ra.m.level];
+  const KfLevelDev& K = ra.v.kf_tab[ra.v.level * ra.v.max_kf + map_slot(ra.stage, b)];
+  const LevelGeom& g = ra.v.geom[ra.v.level];
   const ELLC_GLOBAL float* depth = gptr(K.depth);
   const ELLC_GLOBAL float* var = gptr(K.var);
   const ELLC_GLOBAL uint8_t* img = gptr(K.img);
   const int cols = g.cols, rows = g.rows;
-  const RenderT T = render_transform(ra.m, b);
+  const RenderT T = render_T12(ra, b);
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
   int n_kept = 0, n_view = 0, n_int = 0, n_cand = 0;
 #pragma unroll
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void absorb_mark(AbsorbArgs a) {
     MapPixel p;
     RenderCand c;
     bool ok = false;
-    if (map_keep(ra.m, depth, var, cols, rows, i, p)) {
+    if (map_keep(ra.v, depth, var, cols, rows, i, p)) {
       n_kept++;
       if (render_candidate(g, T, b, i, p.x, p.y, p.Z, p.V, c)) {
         n_view++;
@@ -120,12 +120,12 @@ __global__ __launch_bounds__(256) void absorb_mark(AbsorbArgs a) {
 __global__ __launch_bounds__(256) void absorb_scatter(AbsorbArgs a) {
   const RenderArgs& ra = a.f.r;
   const unsigned b = blockIdx.y;
-  const KfLevelDev& K = ra.m.kf_tab[ra.m.level * ra.m.max_kf + map_slot(ra.m, b)];
-  const LevelGeom& g = ra.m.geom[ra.m.level];
+  const KfLevelDev& K = ra.v.kf_tab[ra.v.level * ra.v.max_kf + map_slot(ra.stage, b)];
+  const LevelGeom& g = ra.v.geom[ra.v.level];
   const ELLC_GLOBAL float* depth = gptr(K.depth);
   const ELLC_GLOBAL float* var = gptr(K.var);
   const int cols = g.cols;
-  const RenderT T = render_transform(ra.m, b);
+  const RenderT T = render_T12(ra, b);
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void absorb_scatter(AbsorbArgs a) {
 __global__ __launch_bounds__(256) void absorb_fold(AbsorbArgs a) {
   const RenderArgs& ra = a.f.r;
   const int t = (int)(blockIdx.x * 256u + threadIdx.x);
-  const LevelGeom& g = ra.m.geom[ra.m.level];
+  const LevelGeom& g = ra.v.geom[ra.v.level];
   int n[ELLC_ABSORB_FOLD_COUNTS];   // visited, created, merged, replaced, occluded, skipped, hit, touched, truncated, valid before, valid after
 #pragma unroll
   for (int k = 0; k < ELLC_ABSORB_FOLD_COUNTS; k++) n[k] = 0;
@@ -192,11 +192,11 @@ __global__ __launch_bounds__(256) void absorb_fold(AbsorbArgs a) {
           last = (long long)cid;
           const unsigned b = cid >> 24, i = cid & 0xffffffu;
           RenderCand cand;
-          bool have = b < (unsigned)ra.m.B && i < (unsigned)ra.n;   // (always: absorb_scatter wrote the id)
+          bool have = b < (unsigned)ra.B && i < (unsigned)ra.n;   // (always: absorb_scatter wrote the id)
           if (have) {
-            const KfLevelDev& K = ra.m.kf_tab[ra.m.level * ra.m.max_kf + ra.m.stage[b]];
+            const KfLevelDev& K = ra.v.kf_tab[ra.v.level * ra.v.max_kf + ra.stage[b]];
             const int y = (int)i / g.cols, x = (int)i - y * g.cols;
-            have = render_candidate(g, render_transform(ra.m, b), b, (int)i, x, y, K.depth[i], K.var[i], cand);   // (the same inputs gave it before)
+            have = render_candidate(g, render_T12(ra, b), b, (int)i, x, y, K.depth[i], K.var[i], cand);   // (the same inputs gave it before)
           }
           if (!have) {   // (cannot happen; counted as skipped so that the identity of the stats holds whatever happens)
             n[5]++;

@@ -1,10 +1,12 @@
 // ellc_keyframe_depth_consistency: one keyframe slot's semi-dense map against another's at a given transform (no reference counterpart:
 // GlobalOptimize.cpp:566-582 accepts every candidate of a loop closure unseen). A reduction, two launches, no waiting between blocks
-// and no atomics: consist_pass leaves one partial record per (request, tile), consist_finish sums a request's tiles. map_keep
-// (ellc_kernels_map.hpp) decides which source pixels take part, render_candidate (ellc_kernels_render.hpp) where they land.
+// and no atomics: consist_pass leaves one partial record per (request, tile), consist_finish sums a request's tiles
+// (ellc_pair_reduce.hpp holds the tail of both). map_keep (ellc_kernels_map.hpp) decides which source pixels take part,
+// render_candidate (ellc_kernels_render.hpp) where they land.
 #pragma once
 #include <float.h>
 #include "ellc_kernels_render.hpp"
+#include "ellc_pair_reduce.hpp"
 
 namespace ellc {
 
@@ -17,7 +19,7 @@ struct ConsistRec {
 };
 
 struct ConsistArgs {
-  MapArgs m;                 // geom, kf_tab, level, max_kf, tiles and the filter: what map_keep reads (its stage is not used here)
+  MapView v;                 // what map_keep reads
   const int* stage;          // [cap] source slot of every request, [cap] destination slot, [cap][12] f32 transforms (device copy of the pinned record)
   ConsistRec* partials;      // [requests of the launch][tiles]
   ConsistRec* out;           // pinned, through its device-side address: [B] records (consist_finish)
@@ -26,26 +28,21 @@ struct ConsistArgs {
   float agree_k2;
 };
 
-__device__ __forceinline__ ConsistRec consist_zero() {
-  ConsistRec r;
+__device__ __forceinline__ void rec_zero(ConsistRec& r) {
   r.sum_chi2 = r.sum_w_ss = r.sum_w_st = 0.0;
   r.sum_abs_di = r.sum_di2 = 0;
   r.n_kept = r.n_in_view = r.n_overlap = r.n_agree = r.n_in_front = r.n_behind = r.n_weighted = 0;
   r.pad_ = 0;
-  return r;
 }
 
-// a += b, field by field (one rounding per double field)
-__device__ __forceinline__ void consist_add(ConsistRec& a, const ConsistRec& b) {
+__device__ __forceinline__ void rec_add(ConsistRec& a, const ConsistRec& b) {
   a.sum_chi2 += b.sum_chi2; a.sum_w_ss += b.sum_w_ss; a.sum_w_st += b.sum_w_st;
   a.sum_abs_di += b.sum_abs_di; a.sum_di2 += b.sum_di2;
   a.n_kept += b.n_kept; a.n_in_view += b.n_in_view; a.n_overlap += b.n_overlap; a.n_agree += b.n_agree;
   a.n_in_front += b.n_in_front; a.n_behind += b.n_behind; a.n_weighted += b.n_weighted;
 }
 
-// The sum over the wave's 64 lanes, in every lane: a butterfly, so the order of the additions is fixed by the lane numbers alone
-// (lane l and lane l ^ m add the same two values: a + b == b + a, every lane ends with the same bits).
-__device__ __forceinline__ void consist_wave_sum(ConsistRec& r) {
+__device__ __forceinline__ void rec_wave_sum(ConsistRec& r) {
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) {
     ConsistRec o;
@@ -54,19 +51,18 @@ __device__ __forceinline__ void consist_wave_sum(ConsistRec& r) {
     o.n_kept = __shfl_xor(r.n_kept, m, 64); o.n_in_view = __shfl_xor(r.n_in_view, m, 64); o.n_overlap = __shfl_xor(r.n_overlap, m, 64);
     o.n_agree = __shfl_xor(r.n_agree, m, 64); o.n_in_front = __shfl_xor(r.n_in_front, m, 64); o.n_behind = __shfl_xor(r.n_behind, m, 64);
     o.n_weighted = __shfl_xor(r.n_weighted, m, 64);
-    consist_add(r, o);
+    rec_add(r, o);
   }
 }
 
 // grid (tiles of the level) x (requests of the launch), map_count's pixel layout: thread t of tile `local` owns pixels
-// local * ELLC_TILE + j * 256 + t and adds them in the order j = 0..7; the wave's lanes are summed by the butterfly, the four waves in
-// ascending order. The partition follows from the level's size alone.
+// local * ELLC_TILE + j * 256 + t and adds them in the order j = 0..7; pair_store_block adds the lanes and the waves.
 __global__ __launch_bounds__(256) void consist_pass(ConsistArgs a) {
   const unsigned b = (unsigned)a.first + blockIdx.y;
   const int src = __builtin_amdgcn_readfirstlane(a.stage[b]), dst = __builtin_amdgcn_readfirstlane(a.stage[(unsigned)a.cap + b]);
-  const KfLevelDev& S = a.m.kf_tab[a.m.level * a.m.max_kf + src];
-  const KfLevelDev& D = a.m.kf_tab[a.m.level * a.m.max_kf + dst];
-  const LevelGeom& g = a.m.geom[a.m.level];
+  const KfLevelDev& S = a.v.kf_tab[a.v.level * a.v.max_kf + src];
+  const KfLevelDev& D = a.v.kf_tab[a.v.level * a.v.max_kf + dst];
+  const LevelGeom& g = a.v.geom[a.v.level];
   const ELLC_GLOBAL float* depth = gptr(S.depth);
   const ELLC_GLOBAL float* var = gptr(S.var);
   const ELLC_GLOBAL uint8_t* img = gptr(S.img);
@@ -74,20 +70,16 @@ __global__ __launch_bounds__(256) void consist_pass(ConsistArgs a) {
   const ELLC_GLOBAL float* tvar = gptr(D.var);
   const ELLC_GLOBAL uint8_t* timg = gptr(D.img);
   const int cols = g.cols, rows = g.rows, sw = g.sw;
-  RenderT T;   // block-uniform: scalar loads
-  {
-    const float* Tp = (const float*)(a.stage + 2u * (unsigned)a.cap) + 12u * b;
-#pragma unroll
-    for (int k = 0; k < 12; k++) T.t[k] = Tp[k];
-  }
+  const RenderT T = load_T12((const float*)(a.stage + 2u * (unsigned)a.cap) + 12u * b);   // block-uniform: scalar loads
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
-  ConsistRec r = consist_zero();
+  ConsistRec r;
+  rec_zero(r);
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     const int i = base + j * 256;
     MapPixel p;
     RenderCand c;
-    if (!map_keep(a.m, depth, var, cols, rows, i, p)) continue;
+    if (!map_keep(a.v, depth, var, cols, rows, i, p)) continue;
     r.n_kept++;
     if (!render_candidate(g, T, 0u, i, p.x, p.y, p.Z, p.V, c)) continue;   // (the request number only enters the key, which is not used here)
     r.n_in_view++;
@@ -117,27 +109,11 @@ __global__ __launch_bounds__(256) void consist_pass(ConsistArgs a) {
       r.sum_w_st += (double)st;
     }
   }
-  consist_wave_sum(r);
-  __shared__ ConsistRec ws[4];
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ConsistRec t = ws[0];
-    consist_add(t, ws[1]);
-    consist_add(t, ws[2]);
-    consist_add(t, ws[3]);
-    a.partials[blockIdx.y * (unsigned)a.m.tiles + blockIdx.x] = t;
-  }
+  pair_store_block(r, a.partials + (blockIdx.y * (unsigned)a.v.tiles + blockIdx.x));
 }
 
-// One wave per request of the launch: lane l adds the tiles l, l + 64, ... in ascending order, the butterfly adds the lanes: the order
-// is fixed by the number of tiles alone (gn_quality_finish's discipline). The record goes to pinned host memory.
 __global__ __launch_bounds__(64) void consist_finish(ConsistArgs a) {
-  const ConsistRec* part = a.partials + blockIdx.x * (unsigned)a.m.tiles;
-  ConsistRec r = consist_zero();
-  for (int k = (int)threadIdx.x; k < a.m.tiles; k += 64) consist_add(r, part[k]);
-  consist_wave_sum(r);
-  if (threadIdx.x == 0) a.out[(unsigned)a.first + blockIdx.x] = r;
+  pair_finish(a.partials, a.v.tiles, a.out, a.first);
 }
 
 }  // namespace ellc

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void fuse_offsets(FuseArgs a) {
 
 // (request, tile, step j, wave) -> the word of the mask that holds the wave's 64 decisions of that step
 __device__ __forceinline__ unsigned fuse_mask_word(const FuseArgs& a, unsigned b, unsigned tile, int j) {
-  return ((b * (unsigned)a.r.m.tiles + tile) * 8u + (unsigned)j) * 4u + (threadIdx.x >> 6);
+  return ((b * (unsigned)a.r.v.tiles + tile) * 8u + (unsigned)j) * 4u + (threadIdx.x >> 6);
 }
 
 // render_agree (its grid, walk, test and count, through the same device functions: the agree plane is the render's) that also KEEPS what it
@@ -96,12 +96,12 @@ __device__ __forceinline__ unsigned fuse_mask_word(const FuseArgs& a, unsigned b
 // pixel a third time: map_keep's sixteen neighbour loads per centre are what the walks over the sources cost.
 __global__ __launch_bounds__(256) void fuse_agree(FuseArgs a) {
   const unsigned b = blockIdx.y;
-  const KfLevelDev& K = a.r.m.kf_tab[a.r.m.level * a.r.m.max_kf + map_slot(a.r.m, b)];
-  const LevelGeom& g = a.r.m.geom[a.r.m.level];
+  const KfLevelDev& K = a.r.v.kf_tab[a.r.v.level * a.r.v.max_kf + map_slot(a.r.stage, b)];
+  const LevelGeom& g = a.r.v.geom[a.r.v.level];
   const ELLC_GLOBAL float* depth = gptr(K.depth);
   const ELLC_GLOBAL float* var = gptr(K.var);
   const int cols = g.cols, rows = g.rows;
-  const RenderT T = render_transform(a.r.m, b);
+  const RenderT T = render_T12(a.r, b);
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void fuse_agree(FuseArgs a) {
     MapPixel p;
     RenderCand c;
     bool ok = false;
-    if (map_keep(a.r.m, depth, var, cols, rows, i, p) && render_candidate(g, T, b, i, p.x, p.y, p.Z, p.V, c)) {
+    if (map_keep(a.r.v, depth, var, cols, rows, i, p) && render_candidate(g, T, b, i, p.x, p.y, p.Z, p.V, c)) {
       const float zw = a.r.depth[(unsigned)c.target], vw = a.r.var[(unsigned)c.target];
       const float d = c.nid - 1.0f / zw;   // (1 / z' of the winner: the same division render_candidate made for it)
       ok = d * d <= a.r.agree_k2 * (c.nvar + vw);
@@ -123,12 +123,12 @@ __global__ __launch_bounds__(256) void fuse_agree(FuseArgs a) {
 // fuse_agree's grid and walk: every candidate it counted computes its target again and writes its id into the target's segment
 __global__ __launch_bounds__(256) void fuse_scatter(FuseArgs a) {
   const unsigned b = blockIdx.y;
-  const KfLevelDev& K = a.r.m.kf_tab[a.r.m.level * a.r.m.max_kf + map_slot(a.r.m, b)];
-  const LevelGeom& g = a.r.m.geom[a.r.m.level];
+  const KfLevelDev& K = a.r.v.kf_tab[a.r.v.level * a.r.v.max_kf + map_slot(a.r.stage, b)];
+  const LevelGeom& g = a.r.v.geom[a.r.v.level];
   const ELLC_GLOBAL float* depth = gptr(K.depth);
   const ELLC_GLOBAL float* var = gptr(K.var);
   const int cols = g.cols;
-  const RenderT T = render_transform(a.r.m, b);
+  const RenderT T = render_T12(a.r, b);
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void fuse_scatter(FuseArgs a) {
 // :1139; no contraction, correctly rounded divisions).
 __global__ __launch_bounds__(256) void fuse_merge(FuseArgs a) {
   const int t = (int)(blockIdx.x * 256u + threadIdx.x);
-  const LevelGeom& g = a.r.m.geom[a.r.m.level];
+  const LevelGeom& g = a.r.v.geom[a.r.v.level];
   bool fused = false;
   if (t < a.r.n) {
     // a target has a winner iff its depth is z' > 0 (render_resolve); its source is no sign to go by: request 128 and up set bit 31
@@ -194,11 +194,11 @@ __global__ __launch_bounds__(256) void fuse_merge(FuseArgs a) {
             visited++;
             last = (long long)c[j];
             const unsigned b = c[j] >> 24, i = c[j] & 0xffffffu;
-            if (b >= (unsigned)a.r.m.B || i >= (unsigned)a.r.n) continue;   // (cannot happen: fuse_scatter wrote the id)
-            const KfLevelDev& K = a.r.m.kf_tab[a.r.m.level * a.r.m.max_kf + a.r.m.stage[b]];
+            if (b >= (unsigned)a.r.B || i >= (unsigned)a.r.n) continue;   // (cannot happen: fuse_scatter wrote the id)
+            const KfLevelDev& K = a.r.v.kf_tab[a.r.v.level * a.r.v.max_kf + a.r.stage[b]];
             const int y = (int)i / g.cols, x = (int)i - y * g.cols;
             RenderCand cand;
-            if (!render_candidate(g, render_transform(a.r.m, b), b, (int)i, x, y, K.depth[i], K.var[i], cand)) continue;   // (the same inputs gave it before)
+            if (!render_candidate(g, render_T12(a.r, b), b, (int)i, x, y, K.depth[i], K.var[i], cand)) continue;   // (the same inputs gave it before)
             const float s = var_t + cand.nvar;
             if (!(s > 0.0f && s <= FLT_MAX)) continue;   // both variances 0, or their sum overflowed: skipped, not counted
             const float w = cand.nvar / s;

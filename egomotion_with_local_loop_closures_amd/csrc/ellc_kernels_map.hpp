@@ -16,24 +16,34 @@ struct MapRec {
   uint16_t source;
 };
 
-struct MapArgs {
+// what map_keep reads: the ring's tables, the level and the filter. Every ring kernel's arguments begin with one. (The kernels take
+// their arguments as one struct, which the kernel-argument preload leaves alone: the fields are scalar loads wherever they sit.)
+struct MapView {
   const LevelGeom* geom;
   const KfLevelDev* kf_tab;
-  const int* stage;          // [max_kf] keyframe slot of every request, then [max_kf][12] f32 transforms (device copy of the pinned record)
-  int* tile_counts;          // [B][tiles]: kept pixels per tile (map_count)
-  unsigned* tile_offsets;    // [B][tiles]: records in front of the tile, request-major (map_scan)
-  int* totals;               // pinned, through its device-side address: [max_kf] points per request, [max_kf] = their sum (map_scan)
-  MapRec* out;               // device staging of the records (map_scatter)
-  unsigned out_cap;          //   and how many it holds: the call's total
-  int level, max_kf, tiles, B;
+  int level, max_kf, tiles;
   float max_var;
   int min_support;
   float support_k2;
   int stride;
 };
 
+// ... and what the point export writes
+struct MapArgs {
+  MapView v;
+  const int* stage;          // [max_kf] keyframe slot of every request, then [max_kf][12] f32 transforms (device copy of the pinned record)
+  int* tile_counts;          // [B][tiles]: kept pixels per tile (map_count)
+  unsigned* tile_offsets;    // [B][tiles]: records in front of the tile, request-major (map_scan)
+  int* totals;               // pinned, through its device-side address: [max_kf] points per request, [max_kf] = their sum (map_scan)
+  MapRec* out;               // device staging of the records (map_scatter)
+  unsigned out_cap;          //   and how many it holds: the call's total
+  int B;
+};
+
+// the keyframe slot of request b in a [max_kf] slots, [max_kf][12] transforms record, and its transform
 // (block-uniform: through readfirstlane as prep_slot does, so that the slot's table entry stays in scalar registers)
-__device__ __forceinline__ int map_slot(const MapArgs& a, unsigned b) { return __builtin_amdgcn_readfirstlane(a.stage[b]); }
+__device__ __forceinline__ int map_slot(const int* stage, unsigned b) { return __builtin_amdgcn_readfirstlane(stage[b]); }
+__device__ __forceinline__ const float* map_T12(const int* stage, int max_kf, unsigned b) { return (const float*)(stage + max_kf) + 12u * b; }
 
 // a pixel that holds a hypothesis a point can be made of: NaN fails all three tests; updateDepthImage writes 1 / invDepthSmoothed
 // for any invDepthSmoothed >= -0.05 (DepthPropagation.cpp:1285-1289), so +inf and negative depths do occur
@@ -46,7 +56,7 @@ struct MapPixel {
 
 // THE rule, for map_count and map_scatter alike: is pixel i of the level kept, and what does its record need. The neighbours are read
 // from global memory (adjacent threads read the same lines) and only for a centre that passed every test of its own.
-__device__ __forceinline__ bool map_keep(const MapArgs& a, const ELLC_GLOBAL float* depth, const ELLC_GLOBAL float* var, int cols, int rows, int i, MapPixel& p) {
+__device__ __forceinline__ bool map_keep(const MapView& a, const ELLC_GLOBAL float* depth, const ELLC_GLOBAL float* var, int cols, int rows, int i, MapPixel& p) {
   if (i >= cols * rows) return false;
   const float Z = depth[(unsigned)i], V = var[(unsigned)i];
   if (!map_ok(Z, V)) return false;
@@ -77,8 +87,8 @@ __device__ __forceinline__ bool map_keep(const MapArgs& a, const ELLC_GLOBAL flo
 // and (j, wave, lane) is raster order).
 __global__ __launch_bounds__(256) void map_count(MapArgs a) {
   const int local = (int)blockIdx.x;
-  const KfLevelDev& K = a.kf_tab[a.level * a.max_kf + map_slot(a, blockIdx.y)];
-  const LevelGeom& g = a.geom[a.level];
+  const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + map_slot(a.stage, blockIdx.y)];
+  const LevelGeom& g = a.v.geom[a.v.level];
   const ELLC_GLOBAL float* depth = gptr(K.depth);
   const ELLC_GLOBAL float* var = gptr(K.var);
   const int cols = g.cols, rows = g.rows;
@@ -87,14 +97,14 @@ __global__ __launch_bounds__(256) void map_count(MapArgs a) {
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     MapPixel p;
-    c += map_keep(a, depth, var, cols, rows, base + j * 256, p) ? 1 : 0;
+    c += map_keep(a.v, depth, var, cols, rows, base + j * 256, p) ? 1 : 0;
   }
   __shared__ int ws[4];
   int tot;
   wave_inclusive_scan(c, tot);
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = tot;
   __syncthreads();
-  if (threadIdx.x == 0) a.tile_counts[blockIdx.y * (unsigned)a.tiles + (unsigned)local] = ws[0] + ws[1] + ws[2] + ws[3];
+  if (threadIdx.x == 0) a.tile_counts[blockIdx.y * (unsigned)a.v.tiles + (unsigned)local] = ws[0] + ws[1] + ws[2] + ws[3];
 }
 
 // One block: exclusive scan of the B x tiles counts in request-major order; points per request and their sum for the host. Thread t
@@ -105,7 +115,7 @@ __global__ __launch_bounds__(256) void map_count(MapArgs a) {
 __global__ __launch_bounds__(256) void map_scan(MapArgs a) {
   __shared__ int ws[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned N = (unsigned)a.B * (unsigned)a.tiles;
+  const unsigned N = (unsigned)a.B * (unsigned)a.v.tiles;
   const unsigned per = (N + 255u) / 256u;
   const unsigned i0 = min(N, threadIdx.x * per), i1 = min(N, i0 + per);
   int part = 0;
@@ -124,18 +134,18 @@ __global__ __launch_bounds__(256) void map_scan(MapArgs a) {
   }
   __syncthreads();   // the offsets the block's other threads wrote are read below
   for (int b = (int)threadIdx.x; b < a.B; b += 256) {
-    const unsigned s0 = a.tile_offsets[(unsigned)b * (unsigned)a.tiles];
-    const unsigned s1 = (b + 1 < a.B) ? a.tile_offsets[(unsigned)(b + 1) * (unsigned)a.tiles] : (unsigned)total;
+    const unsigned s0 = a.tile_offsets[(unsigned)b * (unsigned)a.v.tiles];
+    const unsigned s1 = (b + 1 < a.B) ? a.tile_offsets[(unsigned)(b + 1) * (unsigned)a.v.tiles] : (unsigned)total;
     a.totals[b] = (int)(s1 - s0);
   }
-  if (threadIdx.x == 0) a.totals[a.max_kf] = total;
+  if (threadIdx.x == 0) a.totals[a.v.max_kf] = total;
 }
 
 __global__ __launch_bounds__(256) void map_scatter(MapArgs a) {
   const int local = (int)blockIdx.x;
   const unsigned b = blockIdx.y;
-  const KfLevelDev K = a.kf_tab[a.level * a.max_kf + map_slot(a, b)];
-  const LevelGeom& g = a.geom[a.level];
+  const KfLevelDev K = a.v.kf_tab[a.v.level * a.v.max_kf + map_slot(a.stage, b)];
+  const LevelGeom& g = a.v.geom[a.v.level];
   const ELLC_GLOBAL float* depth = gptr(K.depth);
   const ELLC_GLOBAL float* var = gptr(K.var);
   const ELLC_GLOBAL uint8_t* img = gptr(K.img);
@@ -148,7 +158,7 @@ __global__ __launch_bounds__(256) void map_scatter(MapArgs a) {
   unsigned long long m[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) {
-    keep[j] = map_keep(a, depth, var, cols, rows, base + j * 256, p[j]);
+    keep[j] = map_keep(a.v, depth, var, cols, rows, base + j * 256, p[j]);
     m[j] = __ballot(keep[j]);
     if (lane == 0) cnt[j * 4 + wave] = __popcll(m[j]);
   }
@@ -159,9 +169,9 @@ __global__ __launch_bounds__(256) void map_scatter(MapArgs a) {
     if (lane < 32) cnt[lane] = inc - v;
   }
   __syncthreads();
-  const unsigned tile_off = a.tile_offsets[b * (unsigned)a.tiles + (unsigned)local];
+  const unsigned tile_off = a.tile_offsets[b * (unsigned)a.v.tiles + (unsigned)local];
   const float fx = g.fx, fy = g.fy, cx = g.cx, cy = g.cy;
-  const float* T = (const float*)(a.stage + a.max_kf) + 12u * b;   // block-uniform: scalar loads
+  const float* T = map_T12(a.stage, a.v.max_kf, b);   // block-uniform: scalar loads
   const float t0 = T[0], t1 = T[1], t2 = T[2], t3 = T[3], t4 = T[4], t5 = T[5], t6 = T[6], t7 = T[7], t8 = T[8], t9 = T[9], t10 = T[10], t11 = T[11];
   const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));

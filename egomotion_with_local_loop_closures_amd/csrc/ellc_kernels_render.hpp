@@ -12,7 +12,8 @@ namespace ellc {
 #define ELLC_RENDER_EMPTY 0xffffffffffffffffull   // what the key buffer is preset to: no candidate
 
 struct RenderArgs {
-  MapArgs m;                     // geom, kf_tab, stage (slots, then transforms), level, max_kf, tiles, B and the filter: what map_keep reads
+  MapView v;                     // what map_keep reads
+  const int* stage;              // [max_kf] keyframe slot of every request, then [max_kf][12] f32 transforms (map_slot, map_T12)
   unsigned long long* keys;      // [n of the level]: (bits(z') << 32) | (b << 24) | i of the best candidate so far (render_min)
   float* depth;                  // the five planes of the view, [n] each (render_resolve; agree counted up by render_agree)
   float* var;
@@ -21,7 +22,7 @@ struct RenderArgs {
   uint8_t* intensity;
   int* block_counts;             // [blocks of render_resolve] targets with a winner
   int* n_valid;                  // pinned, through its device-side address: their sum (render_finish)
-  int n, blocks;                 // pixels of the level, blocks of render_resolve
+  int n, blocks, B;              // pixels of the level, blocks of render_resolve, requests
   float agree_k2;
 };
 
@@ -29,13 +30,14 @@ struct RenderT {
   float t[12];
 };
 
-__device__ __forceinline__ RenderT render_transform(const MapArgs& a, unsigned b) {
-  const float* T = (const float*)(a.stage + a.max_kf) + 12u * b;
+// the twelve floats of a request's transform (block-uniform where the request is: scalar loads)
+__device__ __forceinline__ RenderT load_T12(const float* T) {
   RenderT r;
 #pragma unroll
   for (int k = 0; k < 12; k++) r.t[k] = T[k];
   return r;
 }
+__device__ __forceinline__ RenderT render_T12(const RenderArgs& a, unsigned b) { return load_T12(map_T12(a.stage, a.v.max_kf, b)); }
 
 struct RenderCand {
   int target;                // raster index in the view
@@ -76,19 +78,19 @@ __device__ __forceinline__ bool render_candidate(const LevelGeom& g, const Rende
 // is the order of its values: the nearest surface wins, ties go to the lower request, then to the lower raster index.
 __global__ __launch_bounds__(256) void render_min(RenderArgs a) {
   const unsigned b = blockIdx.y;
-  const KfLevelDev& K = a.m.kf_tab[a.m.level * a.m.max_kf + map_slot(a.m, b)];
-  const LevelGeom& g = a.m.geom[a.m.level];
+  const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + map_slot(a.stage, b)];
+  const LevelGeom& g = a.v.geom[a.v.level];
   const ELLC_GLOBAL float* depth = gptr(K.depth);
   const ELLC_GLOBAL float* var = gptr(K.var);
   const int cols = g.cols, rows = g.rows;
-  const RenderT T = render_transform(a.m, b);   // block-uniform: scalar loads
+  const RenderT T = render_T12(a, b);   // block-uniform: scalar loads
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     const int i = base + j * 256;
     MapPixel p;
     RenderCand c;
-    if (!map_keep(a.m, depth, var, cols, rows, i, p)) continue;
+    if (!map_keep(a.v, depth, var, cols, rows, i, p)) continue;
     if (!render_candidate(g, T, b, i, p.x, p.y, p.Z, p.V, c)) continue;
     unsigned long long* k = a.keys + (unsigned)c.target;   // (target < cols * rows: render_candidate's bounds test)
     // the keys only ever fall: a stored key that is already smaller (however stale the load) makes the atomic pointless
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(256) void render_min(RenderArgs a) {
 // one thread per target: the winner's planes, and how many targets of the block have one
 __global__ __launch_bounds__(256) void render_resolve(RenderArgs a) {
   const int t = (int)(blockIdx.x * 256u + threadIdx.x);
-  const LevelGeom& g = a.m.geom[a.m.level];
+  const LevelGeom& g = a.v.geom[a.v.level];
   bool won = false;
   if (t < a.n) {
     const unsigned long long key = a.keys[(unsigned)t];
@@ -110,11 +112,11 @@ __global__ __launch_bounds__(256) void render_resolve(RenderArgs a) {
     if (key != ELLC_RENDER_EMPTY) {
       const unsigned b = (unsigned)(key >> 24) & 0xffu;
       const int i = (int)(key & 0xffffffull);
-      const KfLevelDev& K = a.m.kf_tab[a.m.level * a.m.max_kf + a.m.stage[b]];
+      const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + a.stage[b]];
       const int y = i / g.cols, x = i - y * g.cols;
       RenderCand c;
       // (a key is only ever written for a pixel that gave a candidate: the same inputs give it again)
-      if (render_candidate(g, render_transform(a.m, b), b, i, x, y, K.depth[(unsigned)i], K.var[(unsigned)i], c)) {
+      if (render_candidate(g, render_T12(a, b), b, i, x, y, K.depth[(unsigned)i], K.var[(unsigned)i], c)) {
         won = true;
         z = c.z; nvar = c.nvar;
         src = (int32_t)(key & 0xffffffffull);
@@ -150,19 +152,19 @@ __global__ __launch_bounds__(256) void render_finish(RenderArgs a) {
 // winner's within agree_k2 standard deviations^2 (the winner agrees with itself: d = 0).
 __global__ __launch_bounds__(256) void render_agree(RenderArgs a) {
   const unsigned b = blockIdx.y;
-  const KfLevelDev& K = a.m.kf_tab[a.m.level * a.m.max_kf + map_slot(a.m, b)];
-  const LevelGeom& g = a.m.geom[a.m.level];
+  const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + map_slot(a.stage, b)];
+  const LevelGeom& g = a.v.geom[a.v.level];
   const ELLC_GLOBAL float* depth = gptr(K.depth);
   const ELLC_GLOBAL float* var = gptr(K.var);
   const int cols = g.cols, rows = g.rows;
-  const RenderT T = render_transform(a.m, b);
+  const RenderT T = render_T12(a, b);
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     const int i = base + j * 256;
     MapPixel p;
     RenderCand c;
-    if (!map_keep(a.m, depth, var, cols, rows, i, p)) continue;
+    if (!map_keep(a.v, depth, var, cols, rows, i, p)) continue;
     if (!render_candidate(g, T, b, i, p.x, p.y, p.Z, p.V, c)) continue;
     const float zw = a.depth[(unsigned)c.target], vw = a.var[(unsigned)c.target];
     const float d = c.nid - 1.0f / zw;   // (1 / z' of the winner: the same division render_candidate made for it)

@@ -6,6 +6,7 @@
 #pragma once
 #include <float.h>
 #include "ellc_kernels_render.hpp"
+#include "ellc_pair_reduce.hpp"
 
 namespace ellc {
 
@@ -18,7 +19,7 @@ struct Sim3Rec {
 };
 
 struct Sim3Args {
-  MapArgs m;                 // geom, kf_tab, level, max_kf, tiles and the filter: what map_keep reads (its stage is not used here)
+  MapView v;                 // what map_keep reads
   const int* stage;          // [cap] source slot of every request, [cap] destination slot, [cap][12] f32 transforms (device copy of the pinned record)
   Sim3Rec* partials;         // [requests of the launch][tiles]
   Sim3Rec* out;              // pinned, through its device-side address: [B] records (sim3_finish)
@@ -35,8 +36,11 @@ __device__ __forceinline__ constexpr int sim3_h(int i, int j) { return i * 7 - (
 // indices 2, 3 and 4, so H[2][6], H[3][6] and H[4][6] stay the zero they start as. They are kept out of the reductions.
 __device__ __forceinline__ constexpr bool sim3_never(int k) { return k == sim3_h(2, 6) || k == sim3_h(3, 6) || k == sim3_h(4, 6); }
 
-// a += b, field by field (one rounding per double field)
-__device__ __forceinline__ void sim3_add(Sim3Rec& a, const Sim3Rec& b) {
+// (one value-initialisation, not a loop over the fields: with the loop behind a call sim3_pass reloaded and reconverted the level's
+// size inside its pixel loop, 1 to 2 % of the step's device time)
+__device__ __forceinline__ void rec_zero(Sim3Rec& r) { r = Sim3Rec(); }
+
+__device__ __forceinline__ void rec_add(Sim3Rec& a, const Sim3Rec& b) {
 #pragma unroll
   for (int k = 0; k < ELLC_SIM3_SUMS; k++)
     if (!sim3_never(k)) a.s[k] += b.s[k];
@@ -44,9 +48,8 @@ __device__ __forceinline__ void sim3_add(Sim3Rec& a, const Sim3Rec& b) {
   for (int k = 0; k < 6; k++) a.n[k] += b.n[k];
 }
 
-// The sum over the wave's 64 lanes, in every lane: consist_wave_sum's butterfly (lane l and lane l ^ m add the same two values, so
-// every lane ends with the same bits and the order is fixed by the lane numbers alone).
-__device__ __forceinline__ void sim3_wave_sum(Sim3Rec& r) {
+// The butterfly of this record: the sums no term reaches stay out, and the exchanges go eight at a time.
+__device__ __forceinline__ void rec_wave_sum(Sim3Rec& r) {
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) {
 #pragma unroll
@@ -89,9 +92,9 @@ __device__ __forceinline__ float sim3_bilinear(float I00, float I01, float I10, 
 __global__ __launch_bounds__(256) void sim3_pass(Sim3Args a) {
   const unsigned b = (unsigned)a.first + blockIdx.y;
   const int src = __builtin_amdgcn_readfirstlane(a.stage[b]), dst = __builtin_amdgcn_readfirstlane(a.stage[(unsigned)a.cap + b]);
-  const KfLevelDev& S = a.m.kf_tab[a.m.level * a.m.max_kf + src];
-  const KfLevelDev& D = a.m.kf_tab[a.m.level * a.m.max_kf + dst];
-  const LevelGeom& g = a.m.geom[a.m.level];
+  const KfLevelDev& S = a.v.kf_tab[a.v.level * a.v.max_kf + src];
+  const KfLevelDev& D = a.v.kf_tab[a.v.level * a.v.max_kf + dst];
+  const LevelGeom& g = a.v.geom[a.v.level];
   const ELLC_GLOBAL float* depth = gptr(S.depth);
   const ELLC_GLOBAL float* var = gptr(S.var);
   const ELLC_GLOBAL uint8_t* img = gptr(S.img);
@@ -100,18 +103,10 @@ __global__ __launch_bounds__(256) void sim3_pass(Sim3Args a) {
   const ELLC_GLOBAL uint8_t* timg = gptr(D.img);
   const int cols = g.cols, rows = g.rows, sw = g.sw;
   const float fx = g.fx, fy = g.fy;
-  RenderT T;   // block-uniform: scalar loads
-  {
-    const float* Tp = (const float*)(a.stage + 2u * (unsigned)a.cap) + 12u * b;
-#pragma unroll
-    for (int k = 0; k < 12; k++) T.t[k] = Tp[k];
-  }
+  const RenderT T = load_T12((const float*)(a.stage + 2u * (unsigned)a.cap) + 12u * b);   // block-uniform: scalar loads
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
   Sim3Rec r;
-#pragma unroll
-  for (int k = 0; k < ELLC_SIM3_SUMS; k++) r.s[k] = 0.0;
-#pragma unroll
-  for (int k = 0; k < 6; k++) r.n[k] = 0;
+  rec_zero(r);
   const int idx_photo[6] = {0, 1, 2, 3, 4, 5}, idx_depth[4] = {0, 1, 5, 6};
 #pragma unroll 1
   for (int j = 0; j < 8; j++) {
@@ -122,7 +117,7 @@ __global__ __launch_bounds__(256) void sim3_pass(Sim3Args a) {
     float Jd[4] = {0.0f, 0.0f, 0.0f, 0.0f}, rd = 0.0f, wd = 0.0f;
     MapPixel p;
     RenderCand c;
-    if (map_keep(a.m, depth, var, cols, rows, i, p)) {
+    if (map_keep(a.v, depth, var, cols, rows, i, p)) {
       r.n[0]++;
       if (render_candidate(g, T, 0u, i, p.x, p.y, p.Z, p.V, c)) {   // (the request number only enters the key, which is not used here)
         r.n[1]++;
@@ -171,29 +166,20 @@ __global__ __launch_bounds__(256) void sim3_pass(Sim3Args a) {
     sim3_term(r, idx_depth, Jd, wd, rd);
     r.s[36] += (double)((rd * rd) * wd);
   }
-  sim3_wave_sum(r);
+  rec_wave_sum(r);
   __shared__ Sim3Rec ws[4];
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = r;
   __syncthreads();
-  // thread k adds field k of the four waves in ascending order (one thread adding whole records would hold four of them in registers)
-  Sim3Rec& out = a.partials[blockIdx.y * (unsigned)a.m.tiles + blockIdx.x];
+  // A block tail of its own, not pair_store_block: thread k adds field k of the four waves in ascending order (one thread adding whole
+  // records would hold four of them, 4 x 34 live doubles, in registers)
+  Sim3Rec& out = a.partials[blockIdx.y * (unsigned)a.v.tiles + blockIdx.x];
   const unsigned k = threadIdx.x;
   if (k < ELLC_SIM3_SUMS) out.s[k] = ((ws[0].s[k] + ws[1].s[k]) + ws[2].s[k]) + ws[3].s[k];
   else if (k < ELLC_SIM3_SUMS + 6) out.n[k - ELLC_SIM3_SUMS] = ws[0].n[k - ELLC_SIM3_SUMS] + ws[1].n[k - ELLC_SIM3_SUMS] + ws[2].n[k - ELLC_SIM3_SUMS] + ws[3].n[k - ELLC_SIM3_SUMS];
 }
 
-// One wave per request of the launch: lane l adds the tiles l, l + 64, ... in ascending order, the butterfly adds the lanes: the order
-// is fixed by the number of tiles alone (consist_finish's discipline). The record goes to pinned host memory.
 __global__ __launch_bounds__(64) void sim3_finish(Sim3Args a) {
-  const Sim3Rec* part = a.partials + blockIdx.x * (unsigned)a.m.tiles;
-  Sim3Rec r;
-#pragma unroll
-  for (int k = 0; k < ELLC_SIM3_SUMS; k++) r.s[k] = 0.0;
-#pragma unroll
-  for (int k = 0; k < 6; k++) r.n[k] = 0;
-  for (int k = (int)threadIdx.x; k < a.m.tiles; k += 64) sim3_add(r, part[k]);
-  sim3_wave_sum(r);
-  if (threadIdx.x == 0) a.out[(unsigned)a.first + blockIdx.x] = r;
+  pair_finish(a.partials, a.v.tiles, a.out, a.first);
 }
 
 }  // namespace ellc

@@ -2,11 +2,12 @@
 // be?", for B pairs in one call and without touching the live depth map. Steps 1-4 of ellc_depth_absorb_keyframes with the destination's
 // level-0 image and maxAbsGradient plane in K's role, as a reduction: map_keep, render_candidate, absorb_interior and absorb_photo decide
 // every source pixel (nothing of them is restated here). consist_pass's shape: trial_pass leaves one partial record per (request, tile),
-// trial_finish sums a request's tiles. The DISTINCT targets among the candidates are counted through one bit per (request, target) in
+// trial_finish sums a request's tiles (ellc_pair_reduce.hpp holds the tail of both). The DISTINCT targets among the candidates are counted through one bit per (request, target) in
 // device scratch: whoever finds its bit clear counts the target (an integer atomic OR: the total does not depend on the arrival order).
 // No waiting between blocks, integer atomics only, no floating-point atomics.
 #pragma once
 #include "ellc_kernels_absorb.hpp"
+#include "ellc_pair_reduce.hpp"
 
 namespace ellc {
 
@@ -27,7 +28,7 @@ struct TrialReq {
 };
 
 struct TrialArgs {
-  MapArgs m;                 // geom, kf_tab, level (0), max_kf, tiles and the filter: what map_keep reads (its stage is not used here)
+  MapView v;                 // what map_keep reads (level 0)
   const TrialReq* req;       // [B]
   unsigned* bits;            // [requests of the launch][words]: one bit per target pixel, zero in front of trial_pass
   TrialRec* partials;        // [requests of the launch][tiles]
@@ -37,60 +38,54 @@ struct TrialArgs {
   int photo_gate;
 };
 
-__device__ __forceinline__ TrialRec trial_zero() {
-  TrialRec r;
+__device__ __forceinline__ void rec_zero(TrialRec& r) {
   r.sum_r2 = r.sum_abs_r = 0.0;
   r.n_kept = r.n_in_view = r.n_interior = r.n_low_grad = r.n_candidates = r.n_targets = 0;
   r.reserved[0] = r.reserved[1] = 0;
-  return r;
 }
 
-// a += b, field by field (one rounding per double field)
-__device__ __forceinline__ void trial_add(TrialRec& a, const TrialRec& b) {
+__device__ __forceinline__ void rec_add(TrialRec& a, const TrialRec& b) {
   a.sum_r2 += b.sum_r2; a.sum_abs_r += b.sum_abs_r;
   a.n_kept += b.n_kept; a.n_in_view += b.n_in_view; a.n_interior += b.n_interior; a.n_low_grad += b.n_low_grad;
   a.n_candidates += b.n_candidates; a.n_targets += b.n_targets;
 }
 
-// consist_wave_sum's butterfly: the order of the additions is fixed by the lane numbers alone, every lane ends with the same bits
-__device__ __forceinline__ void trial_wave_sum(TrialRec& r) {
+__device__ __forceinline__ void rec_wave_sum(TrialRec& r) {
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) {
     TrialRec o;
     o.sum_r2 = __shfl_xor(r.sum_r2, m, 64); o.sum_abs_r = __shfl_xor(r.sum_abs_r, m, 64);
     o.n_kept = __shfl_xor(r.n_kept, m, 64); o.n_in_view = __shfl_xor(r.n_in_view, m, 64); o.n_interior = __shfl_xor(r.n_interior, m, 64);
     o.n_low_grad = __shfl_xor(r.n_low_grad, m, 64); o.n_candidates = __shfl_xor(r.n_candidates, m, 64); o.n_targets = __shfl_xor(r.n_targets, m, 64);
-    trial_add(r, o);
+    rec_add(r, o);
   }
 }
 
 // grid (tiles of level 0) x (requests of the launch), map_count's pixel layout: thread t of tile `local` owns pixels
-// local * ELLC_TILE + j * 256 + t and adds them in the order j = 0..7; the wave's lanes are summed by the butterfly, the four waves in
-// ascending order through LDS. The partition follows from the level's size alone.
+// local * ELLC_TILE + j * 256 + t and adds them in the order j = 0..7; pair_store_block adds the lanes and the waves.
 __global__ __launch_bounds__(256) void trial_pass(TrialArgs a) {
   const unsigned b = (unsigned)a.first + blockIdx.y;
   const TrialReq& q = a.req[b];
   const int src = __builtin_amdgcn_readfirstlane(q.src);
-  const KfLevelDev& S = a.m.kf_tab[a.m.level * a.m.max_kf + src];
-  const LevelGeom& g = a.m.geom[a.m.level];
+  const KfLevelDev& S = a.v.kf_tab[a.v.level * a.v.max_kf + src];
+  const LevelGeom& g = a.v.geom[a.v.level];
   const ELLC_GLOBAL float* depth = gptr(S.depth);
   const ELLC_GLOBAL float* var = gptr(S.var);
   const ELLC_GLOBAL uint8_t* img = gptr(S.img);
   const uint8_t* dimg = q.dst_img;
   const float* dgrad = q.dst_maxgrad;
   const int cols = g.cols, rows = g.rows;
-  RenderT T;   // block-uniform: scalar loads
-#pragma unroll
-  for (int k = 0; k < 12; k++) T.t[k] = q.T[k];
+  const RenderT T = load_T12(q.T);   // block-uniform: scalar loads
   unsigned* bits = a.bits + (size_t)blockIdx.y * a.words;
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
-  TrialRec r = trial_zero();
+  TrialRec r;
+  rec_zero(r);
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     const int i = base + j * 256;
     MapPixel p;
     RenderCand c;
-    if (!map_keep(a.m, depth, var, cols, rows, i, p)) continue;
+    if (!map_keep(a.v, depth, var, cols, rows, i, p)) continue;
     r.n_kept++;
     if (!render_candidate(g, T, 0u, i, p.x, p.y, p.Z, p.V, c)) continue;   // (the request number only enters the key, which is not used here)
     r.n_in_view++;
@@ -108,27 +103,11 @@ __global__ __launch_bounds__(256) void trial_pass(TrialArgs a) {
     const unsigned old = __hip_atomic_fetch_or(bits + ((unsigned)c.target >> 5), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     r.n_targets += (old & bit) ? 0 : 1;   // exactly one candidate of a target finds the bit clear, whoever arrives first
   }
-  trial_wave_sum(r);
-  __shared__ TrialRec ws[4];
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    TrialRec t = ws[0];
-    trial_add(t, ws[1]);
-    trial_add(t, ws[2]);
-    trial_add(t, ws[3]);
-    a.partials[blockIdx.y * (unsigned)a.m.tiles + blockIdx.x] = t;
-  }
+  pair_store_block(r, a.partials + (blockIdx.y * (unsigned)a.v.tiles + blockIdx.x));
 }
 
-// One wave per request of the launch: lane l adds the tiles l, l + 64, ... in ascending order, the butterfly adds the lanes: the order
-// is fixed by the number of tiles alone (consist_finish's discipline). The record goes to pinned host memory.
 __global__ __launch_bounds__(64) void trial_finish(TrialArgs a) {
-  const TrialRec* part = a.partials + blockIdx.x * (unsigned)a.m.tiles;
-  TrialRec r = trial_zero();
-  for (int k = (int)threadIdx.x; k < a.m.tiles; k += 64) trial_add(r, part[k]);
-  trial_wave_sum(r);
-  if (threadIdx.x == 0) a.out[(unsigned)a.first + blockIdx.x] = r;
+  pair_finish(a.partials, a.v.tiles, a.out, a.first);
 }
 
 }  // namespace ellc

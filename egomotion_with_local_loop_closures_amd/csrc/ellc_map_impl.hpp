@@ -1,11 +1,8 @@
 // ellc_keyframe_map_points (include/ellc_abi.h): the host side of the map export.
-// Included at the end of ellc_hip.hip (the library is one translation unit).
+// Included at the end of ellc_hip.hip behind ellc_ring_common.hpp: its refusals, view, timer and grow-only buffer are used here.
 #pragma once
-#include "ellc_context.hpp"
-#include "ellc_kernels_map.hpp"
+#include "ellc_ring_common.hpp"
 #include <climits>
-#include <cmath>
-#include <cstring>
 
 using namespace ellc;
 
@@ -19,19 +16,15 @@ namespace {
 // launches_ms (the diagnostic hook only): device time of the three launches, HIP events around count + scan and around the scatter
 ellc_status map_points_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* f, ellc_map_point* out,
                             int capacity, int* counts, int* total, float* launches_ms) {
+  const char* who = "ellc_keyframe_map_points";
   if (!c) return ELLC_ERR_BAD_ARG;
-  // validated first: a refused call leaves the context as it was
   if (!kf_slots || !T12 || !f) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_map_points: null pointer");
   if (B < 1 || B > c->cfg.max_keyframes || B > 65535) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_map_points: B out of range");
   if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_map_points: level out of range");
   if (out && capacity < 0) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_map_points: negative capacity");
-  if (f->min_support < 0 || f->min_support > 8 || f->stride < 1 || !(f->support_k2 >= 0.0f) || !std::isfinite(f->support_k2) || std::isnan(f->max_var))
-    return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_map_points: filter out of range");
-  for (int b = 0; b < B; b++)
-    if (!slot_ok(kf_slots[b], c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_map_points: slot index out of range");
-  for (int b = 0; b < B; b++)
-    if (!c->kf_has_image[kf_slots[b]] || !c->kf_has_depth[kf_slots[b]])
-      return fail(c, ELLC_ERR_NOT_READY, "ellc_keyframe_map_points: keyframe slot lacks image or depth");
+  ELLC_TRY(ring_check_filter(c, who, f));
+  ELLC_TRY(ring_check_slots(c, who, B, kf_slots, c->cfg.max_keyframes));
+  ELLC_TRY(ring_check_ready(c, who, B, kf_slots));
   const LevelGeom& g = c->geom_h[level];
   if ((long long)B * g.n > (long long)INT_MAX) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_map_points: B x pixels of the level does not fit the int total");
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
@@ -54,58 +47,40 @@ ellc_status map_points_impl(ellc_ctx* c, int B, const int* kf_slots, const float
   std::memcpy(c->map_stage_h + MK, T12, (size_t)B * 12 * sizeof(float));
   ELLC_HIP(c, hipMemcpyAsync(c->map_stage_d, c->map_stage_h, (size_t)13 * MK * sizeof(int), hipMemcpyHostToDevice, c->stream));
   MapArgs a;
-  a.geom = c->geom_d;
-  a.kf_tab = c->kf_tab_d;
+  a.v = ring_view(c, level, f);
   a.stage = c->map_stage_d;
   a.tile_counts = c->map_tile_counts_d;
   a.tile_offsets = c->map_tile_offsets_d;
   a.totals = c->map_totals_dev_alias;
   a.out = nullptr;
   a.out_cap = 0u;
-  a.level = level;
-  a.max_kf = MK;
-  a.tiles = c->tile_begin[level + 1] - c->tile_begin[level];
   a.B = B;
-  a.max_var = f->max_var;
-  a.min_support = f->min_support;
-  a.support_k2 = f->support_k2;
-  a.stride = f->stride;
-  const dim3 grd(a.tiles, B), blk(256);
-  float ms_a = 0.0f, ms_b = 0.0f;
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
+  const dim3 grd(a.v.tiles, B), blk(256);
+  LaunchTimer t(c, launches_ms);   // two windows: count + scan, and the scatter
+  ELLC_TRY(t.begin());
   hipLaunchKernelGGL(map_count, grd, blk, 0, c->stream, a);
   hipLaunchKernelGGL(map_scan, dim3(1), blk, 0, c->stream, a);
   ELLC_HIP(c, hipGetLastError());
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
+  ELLC_TRY(t.end());
   ELLC_HIP(c, hipStreamSynchronize(c->stream));
-  if (launches_ms) ELLC_HIP(c, hipEventElapsedTime(&ms_a, c->ev0, c->ev1));
+  ELLC_TRY(t.read());
   const int sum = c->map_totals_h[MK];
   if (counts) std::memcpy(counts, c->map_totals_h, (size_t)B * sizeof(int));
   if (total) *total = sum;
-  if (launches_ms) *launches_ms = ms_a;
   if (!out) return ELLC_OK;   // the sizing call
   if (sum > capacity) return fail(c, ELLC_ERR_CAPACITY, "ellc_keyframe_map_points: more points than the buffer holds");
   if (sum == 0) return ELLC_OK;
-  if ((size_t)sum > c->map_out_cap) {   // (nothing of this context is running: the stream was synchronised above)
-    if (c->map_out_d) (void)hipFree(c->map_out_d);
-    c->map_out_d = nullptr;
-    c->map_out_cap = 0;
-    ELLC_HIP(c, hipMalloc(&c->map_out_d, (size_t)sum * sizeof(MapRec)));
-    c->map_out_cap = (size_t)sum;
-  }
+  // (nothing of this context is running: the stream was synchronised above)
+  ELLC_TRY(dev_grow(c, &c->map_out_d, &c->map_out_cap, (size_t)sum, sizeof(MapRec)));
   a.out = (MapRec*)c->map_out_d;
   a.out_cap = (unsigned)sum;
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
+  ELLC_TRY(t.begin());
   hipLaunchKernelGGL(map_scatter, grd, blk, 0, c->stream, a);
   ELLC_HIP(c, hipGetLastError());
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
+  ELLC_TRY(t.end());
   ELLC_HIP(c, hipMemcpyAsync(out, c->map_out_d, (size_t)sum * sizeof(MapRec), hipMemcpyDeviceToHost, c->stream));
   ELLC_HIP(c, hipStreamSynchronize(c->stream));
-  if (launches_ms) {
-    ELLC_HIP(c, hipEventElapsedTime(&ms_b, c->ev0, c->ev1));
-    *launches_ms = ms_a + ms_b;
-  }
-  return ELLC_OK;
+  return t.read();
 }
 
 }  // namespace
@@ -120,10 +95,7 @@ ellc_status ellc_keyframe_map_points(ellc_ctx* c, int B, const int* kf_slots, co
 #ifdef ELLC_DIAG_ABI
 ellc_status ellc_profile_map_points(ellc_ctx* c, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* filter,
                                     ellc_map_point* out, int capacity, int* counts, int* total, float* launches_ms) {
-  float ms = 0.0f;
-  const ellc_status s = map_points_impl(c, B, kf_slots, T12, level, filter, out, capacity, counts, total, &ms);
-  if (launches_ms) *launches_ms = ms;
-  return s;
+  return ring_profiled(launches_ms, [&](float* ms) { return map_points_impl(c, B, kf_slots, T12, level, filter, out, capacity, counts, total, ms); });
 }
 #endif   // ELLC_DIAG_ABI
 

@@ -1,0 +1,179 @@
+// The host scaffold of the calls over the keyframe ring's semi-dense maps (ellc_keyframe_map_points, _render_depth, _fuse_depth,
+// _depth_consistency, _sim3_step / _align, _trial_propagate, ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes): what they
+// refuse alike, the view map_keep reads, the timing window of the diagnostic hooks, grow-only buffers and the launch loop of the pair
+// reductions. Included at the end of ellc_hip.hip in front of the *_impl.hpp of those calls (the library is one translation unit).
+// A new call of the family supplies a record type with rec_zero / rec_add / rec_wave_sum (ellc_pair_reduce.hpp), a pass kernel and a
+// finish kernel over them, and its own list of refusals in its own order.
+#pragma once
+#include "ellc_context.hpp"
+#include "ellc_kernels_map.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace ellc;
+
+#define ELLC_TRY(expr)                   \
+  do {                                   \
+    const ellc_status s__ = (expr);      \
+    if (s__ != ELLC_OK) return s__;      \
+  } while (0)
+
+namespace ellc {
+
+void pair_free(PairScratch& s) {
+  if (s.partials_d) (void)hipFree(s.partials_d);
+  if (s.stage_d) (void)hipFree(s.stage_d);
+  if (s.stage_h) (void)hipHostFree(s.stage_h);
+  if (s.out_h) (void)hipHostFree(s.out_h);
+  s = PairScratch();
+}
+
+}  // namespace ellc
+
+namespace {
+
+// ---- refusals: validated first, a refused call leaves the context as it was (the message is composed only when a call is refused)
+
+ellc_status ring_check_filter(ellc_ctx* c, const char* who, const ellc_map_filter* f) {
+  if (f->min_support < 0 || f->min_support > 8 || f->stride < 1 || !(f->support_k2 >= 0.0f) || !std::isfinite(f->support_k2) || std::isnan(f->max_var))
+    return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": filter out of range");
+  return ELLC_OK;
+}
+
+ellc_status ring_check_slots(ellc_ctx* c, const char* who, int B, const int* slots, int n_slots) {
+  for (int b = 0; b < B; b++)
+    if (!slot_ok(slots[b], n_slots)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": slot index out of range");
+  return ELLC_OK;
+}
+
+ellc_status ring_check_ready(ellc_ctx* c, const char* who, int B, const int* slots) {
+  for (int b = 0; b < B; b++)
+    if (!c->kf_has_image[slots[b]] || !c->kf_has_depth[slots[b]]) return fail(c, ELLC_ERR_NOT_READY, std::string(who) + ": keyframe slot lacks image or depth");
+  return ELLC_OK;
+}
+
+// what map_keep reads on `level` under filter f
+MapView ring_view(const ellc_ctx* c, int level, const ellc_map_filter* f) {
+  MapView v;
+  v.geom = c->geom_d;
+  v.kf_tab = c->kf_tab_d;
+  v.level = level;
+  v.max_kf = c->cfg.max_keyframes;
+  v.tiles = c->tile_begin[level + 1] - c->tile_begin[level];
+  v.max_var = f->max_var;
+  v.min_support = f->min_support;
+  v.support_k2 = f->support_k2;
+  v.stride = f->stride;
+  return v;
+}
+
+// ---- timing (the diagnostic hooks only): HIP events around a window of launches; read() adds the window's device time to *out, so a
+// call with several windows reports their sum. out == nullptr: nothing is recorded.
+struct LaunchTimer {
+  ellc_ctx* c;
+  float* out;
+  LaunchTimer(ellc_ctx* c_, float* out_) : c(c_), out(out_) {
+    if (out) *out = 0.0f;
+  }
+  ellc_status begin() {
+    if (out) ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
+    return ELLC_OK;
+  }
+  ellc_status end() {
+    if (out) ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
+    return ELLC_OK;
+  }
+  ellc_status read() {   // (behind a synchronisation of the stream)
+    float ms = 0.0f;
+    if (out) ELLC_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (out) *out += ms;
+    return ELLC_OK;
+  }
+};
+
+// the body of an ellc_profile_* twin: the call with its timing on, whether or not the caller wants the figure
+template <class Call>
+ellc_status ring_profiled(float* launches_ms, Call call) {
+  float ms = 0.0f;
+  const ellc_status s = call(&ms);
+  if (launches_ms) *launches_ms = ms;
+  return s;
+}
+
+// ---- a device buffer of its own that only grows: `need` elements of `elem` bytes, `extra` more when it has to be allocated anew.
+// (hipFree waits for what still reads the old one)
+ellc_status dev_grow(ellc_ctx* c, void** p, size_t* cap, size_t need, size_t elem, size_t extra = 0) {
+  if (need <= *cap) return ELLC_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  ELLC_HIP(c, hipMalloc(p, (need + extra) * elem));
+  *cap = need + extra;
+  return ELLC_OK;
+}
+
+// ---- pair reductions: B requests, one record each, in launches of at most per_launch requests
+
+// requests per launch when one request's scratch takes `bytes_each` of a budget
+int pair_per_launch(int B, size_t budget, size_t bytes_each) { return (int)std::min<size_t>((size_t)B, std::max<size_t>(1, budget / bytes_each)); }
+
+// room for B staged requests of stage_bytes each, B records of rec_bytes and `partials` partial records
+// (nothing of the call is in flight when its buffers grow: the call is synchronous)
+ellc_status pair_reserve(ellc_ctx* c, PairScratch& s, int B, size_t stage_bytes, size_t rec_bytes, size_t partials) {
+  if (B > s.cap) {
+    if (s.stage_h) (void)hipHostFree(s.stage_h);
+    if (s.out_h) (void)hipHostFree(s.out_h);
+    if (s.stage_d) (void)hipFree(s.stage_d);
+    s.stage_h = s.out_h = s.stage_d = s.out_dev_alias = nullptr;
+    s.cap = 0;
+    ELLC_HIP(c, hipHostMalloc(&s.stage_h, (size_t)B * stage_bytes, hipHostMallocDefault));
+    ELLC_HIP(c, hipHostMalloc(&s.out_h, (size_t)B * rec_bytes, hipHostMallocDefault));
+    ELLC_HIP(c, hipMalloc(&s.stage_d, (size_t)B * stage_bytes));
+    ELLC_HIP(c, hipHostGetDevicePointer(&s.out_dev_alias, s.out_h, 0));
+    s.cap = B;
+  }
+  return dev_grow(c, &s.partials_d, &s.partials_cap, partials, rec_bytes);
+}
+
+// the [cap] source slots, [cap] destination slots, [cap][12] f32 transforms record, staged and on its way to the device
+// (requests beyond B are never read: blockIdx.y < B)
+ellc_status pair_stage_slots(ellc_ctx* c, PairScratch& s, int B, const int* src, const int* dst, const float* T12) {
+  int* h = (int*)s.stage_h;
+  std::memcpy(h, src, (size_t)B * sizeof(int));
+  std::memcpy(h + s.cap, dst, (size_t)B * sizeof(int));
+  std::memcpy(h + 2 * (size_t)s.cap, T12, (size_t)B * 12 * sizeof(float));
+  ELLC_HIP(c, hipMemcpyAsync(s.stage_d, s.stage_h, (size_t)14 * s.cap * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  return ELLC_OK;
+}
+
+struct RingNoStep {
+  ellc_status operator()(int) const { return ELLC_OK; }
+};
+
+// The launches of a pair call and its records: per chunk of per_launch requests pre(n), the pass kernel over (tiles, n) blocks and
+// the finish kernel over n waves; then `enqueued(B)` (what has to follow the launches in stream order), the synchronisation and the B
+// records into `out`. Args holds partials, out and first. (A record depends on its own request only: the split does not enter it.)
+template <class Args, class Pre = RingNoStep, class Post = RingNoStep>
+ellc_status pair_run(ellc_ctx* c, PairScratch& s, int B, int per_launch, void (*pass)(Args), void (*finish)(Args), Args a, void* out,
+                     float* launches_ms, Pre pre = Pre(), Post enqueued = Post()) {
+  a.partials = (decltype(a.partials))s.partials_d;
+  a.out = (decltype(a.out))s.out_dev_alias;
+  LaunchTimer t(c, launches_ms);
+  ELLC_TRY(t.begin());
+  for (int first = 0; first < B; first += per_launch) {
+    const int n = std::min(per_launch, B - first);
+    a.first = first;
+    ELLC_TRY(pre(n));
+    hipLaunchKernelGGL(pass, dim3(a.v.tiles, n), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(finish, dim3(n), dim3(64), 0, c->stream, a);
+  }
+  ELLC_HIP(c, hipGetLastError());
+  ELLC_TRY(t.end());
+  ELLC_TRY(enqueued(B));
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  std::memcpy(out, s.out_h, (size_t)B * sizeof(*a.out));
+  return t.read();
+}
+
+}  // namespace

@@ -1,11 +1,8 @@
 // ellc_keyframe_sim3_step, ellc_keyframe_sim3_align, ellc_sim3_solve, ellc_sim3_apply (include/ellc_abi.h): the host side of the
-// Sim(3) refinement. Included at the end of ellc_hip.hip (the library is one translation unit).
+// Sim(3) refinement. Included at the end of ellc_hip.hip behind ellc_ring_common.hpp: its refusals, view and pair reduction are used here.
 #pragma once
-#include "ellc_context.hpp"
+#include "ellc_ring_common.hpp"
 #include "ellc_kernels_sim3.hpp"
-#include <algorithm>
-#include <cmath>
-#include <cstring>
 #include <vector>
 
 using namespace ellc;
@@ -29,96 +26,33 @@ ellc_status sim3_validate(ellc_ctx* c, const char* who, int B, const int* src, c
   if (B < 1 || B > SIM3_MAX_B) return fail(c, ELLC_ERR_BAD_ARG, w + ": B out of range");
   if (level_lo < 0 || level_hi >= c->L || level_lo > level_hi) return fail(c, ELLC_ERR_BAD_ARG, w + ": level out of range");
   if (c->geom_h[level_lo].n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, w + ": more than 2^24 pixels on the level");
-  if (f->min_support < 0 || f->min_support > 8 || f->stride < 1 || !(f->support_k2 >= 0.0f) || !std::isfinite(f->support_k2) || std::isnan(f->max_var))
-    return fail(c, ELLC_ERR_BAD_ARG, w + ": filter out of range");
+  ELLC_TRY(ring_check_filter(c, who, f));
   if (!std::isfinite(p->sigma_i2) || !std::isfinite(p->huber_k) || !std::isfinite(p->gate_k2) || !std::isfinite(p->depth_weight) ||
       !(p->sigma_i2 > 0.0f) || !(p->huber_k > 0.0f) || !(p->gate_k2 >= 0.0f) || !(p->depth_weight >= 0.0f))
     return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
-  for (int b = 0; b < B; b++)
-    if (!slot_ok(src[b], c->cfg.max_keyframes) || !slot_ok(dst[b], c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, w + ": slot index out of range");
-  for (int b = 0; b < B; b++)
-    if (!c->kf_has_image[src[b]] || !c->kf_has_depth[src[b]] || !c->kf_has_image[dst[b]] || !c->kf_has_depth[dst[b]])
-      return fail(c, ELLC_ERR_NOT_READY, w + ": keyframe slot lacks image or depth");
-  return ELLC_OK;
+  ELLC_TRY(ring_check_slots(c, who, B, src, c->cfg.max_keyframes));
+  ELLC_TRY(ring_check_slots(c, who, B, dst, c->cfg.max_keyframes));
+  ELLC_TRY(ring_check_ready(c, who, B, src));
+  return ring_check_ready(c, who, B, dst);
 }
 
 // One evaluation of B validated requests on `level`, behind ELLC_ENTER; synchronous. launches_ms (the diagnostic hook only): device
 // time of the launches, HIP events around them.
 ellc_status sim3_evaluate(ellc_ctx* c, int B, const int* src, const int* dst, const float* T12, int level, const ellc_map_filter* f,
                           const ellc_sim3_params* p, ellc_sim3_normal* out, float* launches_ms) {
-  const int tiles = c->tile_begin[level + 1] - c->tile_begin[level];
-  const int per_launch = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, SIM3_SCRATCH_BYTES / ((size_t)tiles * sizeof(Sim3Rec))));
-  // (nothing of this call is in flight when its buffers grow: the call is synchronous)
-  if (B > c->sim3_cap) {
-    if (c->sim3_stage_h) (void)hipHostFree(c->sim3_stage_h);
-    if (c->sim3_out_h) (void)hipHostFree(c->sim3_out_h);
-    if (c->sim3_stage_d) (void)hipFree(c->sim3_stage_d);
-    c->sim3_stage_h = nullptr; c->sim3_out_h = nullptr; c->sim3_stage_d = nullptr; c->sim3_out_dev_alias = nullptr;
-    c->sim3_cap = 0;
-    void *sh = nullptr, *oh = nullptr, *sd = nullptr, *da = nullptr;
-    ELLC_HIP(c, hipHostMalloc(&sh, (size_t)14 * B * sizeof(int), hipHostMallocDefault));
-    c->sim3_stage_h = (int*)sh;
-    ELLC_HIP(c, hipHostMalloc(&oh, (size_t)B * sizeof(Sim3Rec), hipHostMallocDefault));
-    c->sim3_out_h = oh;
-    ELLC_HIP(c, hipMalloc(&sd, (size_t)14 * B * sizeof(int)));
-    c->sim3_stage_d = (int*)sd;
-    ELLC_HIP(c, hipHostGetDevicePointer(&da, oh, 0));
-    c->sim3_out_dev_alias = da;
-    c->sim3_cap = B;
-  }
-  const size_t need = (size_t)per_launch * tiles;
-  if (need > c->sim3_partials_cap) {
-    if (c->sim3_partials_d) (void)hipFree(c->sim3_partials_d);
-    c->sim3_partials_d = nullptr;
-    c->sim3_partials_cap = 0;
-    ELLC_HIP(c, hipMalloc(&c->sim3_partials_d, need * sizeof(Sim3Rec)));
-    c->sim3_partials_cap = need;
-  }
-  const int cap = c->sim3_cap;
-  std::memcpy(c->sim3_stage_h, src, (size_t)B * sizeof(int));
-  std::memcpy(c->sim3_stage_h + cap, dst, (size_t)B * sizeof(int));
-  std::memcpy(c->sim3_stage_h + 2 * (size_t)cap, T12, (size_t)B * 12 * sizeof(float));
-  // (requests beyond B are never read: blockIdx.y < B)
-  ELLC_HIP(c, hipMemcpyAsync(c->sim3_stage_d, c->sim3_stage_h, (size_t)14 * cap * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  Sim3Args a;
-  a.m.geom = c->geom_d;
-  a.m.kf_tab = c->kf_tab_d;
-  a.m.stage = nullptr;
-  a.m.tile_counts = nullptr;
-  a.m.tile_offsets = nullptr;
-  a.m.totals = nullptr;
-  a.m.out = nullptr;
-  a.m.out_cap = 0u;
-  a.m.level = level;
-  a.m.max_kf = c->cfg.max_keyframes;
-  a.m.tiles = tiles;
-  a.m.B = B;
-  a.m.max_var = f->max_var;
-  a.m.min_support = f->min_support;
-  a.m.support_k2 = f->support_k2;
-  a.m.stride = f->stride;
-  a.stage = c->sim3_stage_d;
-  a.partials = (Sim3Rec*)c->sim3_partials_d;
-  a.out = (Sim3Rec*)c->sim3_out_dev_alias;
-  a.cap = cap;
+  Sim3Args a{};
+  a.v = ring_view(c, level, f);
+  const int per_launch = pair_per_launch(B, SIM3_SCRATCH_BYTES, (size_t)a.v.tiles * sizeof(Sim3Rec));
+  ELLC_TRY(pair_reserve(c, c->sim3, B, 14 * sizeof(int), sizeof(Sim3Rec), (size_t)per_launch * a.v.tiles));
+  ELLC_TRY(pair_stage_slots(c, c->sim3, B, src, dst, T12));
+  a.stage = (const int*)c->sim3.stage_d;
+  a.cap = c->sim3.cap;
   a.w0 = 1.0f / p->sigma_i2;
   a.sp = sqrtf(a.w0);
   a.huber_k = p->huber_k;
   a.gate_k2 = p->gate_k2;
   a.depth_weight = p->depth_weight;
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev0, c->stream));
-  for (int first = 0; first < B; first += per_launch) {   // (a record depends on its own request only: the split does not enter it)
-    const int n = std::min(per_launch, B - first);
-    a.first = first;
-    hipLaunchKernelGGL(sim3_pass, dim3(tiles, n), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(sim3_finish, dim3(n), dim3(64), 0, c->stream, a);
-  }
-  ELLC_HIP(c, hipGetLastError());
-  if (launches_ms) ELLC_HIP(c, hipEventRecord(c->ev1, c->stream));
-  ELLC_HIP(c, hipStreamSynchronize(c->stream));
-  std::memcpy(out, c->sim3_out_h, (size_t)B * sizeof(Sim3Rec));
-  if (launches_ms) ELLC_HIP(c, hipEventElapsedTime(launches_ms, c->ev0, c->ev1));
-  return ELLC_OK;
+  return pair_run(c, c->sim3, B, per_launch, sim3_pass, sim3_finish, a, out, launches_ms);
 }
 
 ellc_status sim3_step_impl(ellc_ctx* c, int B, const int* src, const int* dst, const float* T12, int level, const ellc_map_filter* f,
@@ -313,10 +247,7 @@ ellc_status ellc_keyframe_sim3_align(ellc_ctx* c, int B, const int* src_kf_slots
 #ifdef ELLC_DIAG_ABI
 ellc_status ellc_profile_sim3_step(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,
                                    const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out, float* launches_ms) {
-  float ms = 0.0f;
-  const ellc_status s = sim3_step_impl(c, B, src_kf_slots, dst_kf_slots, T12, level, filter, params, out, &ms);
-  if (launches_ms) *launches_ms = ms;
-  return s;
+  return ring_profiled(launches_ms, [&](float* ms) { return sim3_step_impl(c, B, src_kf_slots, dst_kf_slots, T12, level, filter, params, out, ms); });
 }
 #endif   // ELLC_DIAG_ABI
 
