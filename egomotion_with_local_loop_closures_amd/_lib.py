@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "ellc_histogram", "ellc_kl_divergence", "ellc_copy_slot", "ellc_copy_slot_across", "ellc_keyframe_map_points", "ellc_keyframe_render_depth", "ellc_keyframe_fuse_depth",
     "ellc_depth_absorb_keyframes", "ellc_absorb_default_params", "ellc_keyframe_trial_propagate", "ellc_depth_restart_from_keyframes",
     "ellc_keyframe_depth_consistency", "ellc_keyframe_sim3_step", "ellc_keyframe_sim3_align", "ellc_sim3_default_params", "ellc_sim3_solve", "ellc_sim3_apply",
+    "ellc_keyframe_light_step", "ellc_keyframe_sim3_step_lit", "ellc_keyframe_sim3_align_lit", "ellc_light_default_params", "ellc_light_solve",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
     "ellc_gather_start", "ellc_gather_finish", "ellc_gather_results",
@@ -36,6 +37,7 @@ DIAG_SYMBOLS = [
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
     "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
     "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_fuse_depth", "ellc_profile_depth_absorb", "ellc_profile_trial_propagate", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
+    "ellc_profile_light_step", "ellc_profile_sim3_step_lit",
 ]
 
 
@@ -88,6 +90,18 @@ class EllcSim3Normal(C.Structure):
     _fields_ = [("H", C.c_double * 28), ("b", C.c_double * 7), ("chi2_photo", C.c_double), ("chi2_depth", C.c_double),
                 ("n_kept", C.c_int32), ("n_in_view", C.c_int32), ("n_photo", C.c_int32), ("n_photo_huber", C.c_int32),
                 ("n_depth", C.c_int32), ("n_depth_gated", C.c_int32)]
+
+
+class EllcLightNormal(C.Structure):
+    """ellc_light_normal: what ellc_keyframe_light_step returns per request (72 bytes)."""
+    _fields_ = [("sum_w", C.c_double), ("sum_w_s", C.c_double), ("sum_w_t", C.c_double), ("sum_w_ss", C.c_double), ("sum_w_st", C.c_double),
+                ("sum_w_tt", C.c_double), ("chi2_photo", C.c_double),
+                ("n_kept", C.c_int32), ("n_in_view", C.c_int32), ("n_photo", C.c_int32), ("n_photo_huber", C.c_int32)]
+
+
+class EllcLightParams(C.Structure):
+    """ellc_light_params: what ellc_light_solve accepts (12 bytes)."""
+    _fields_ = [("gain_min", C.c_float), ("gain_max", C.c_float), ("min_pixels", C.c_int32)]
 
 
 class EllcAbsorbParams(C.Structure):
@@ -173,6 +187,8 @@ def _bind(path, symbols, what):
     if hasattr(h, "ellc_sim3_apply"):
         h.ellc_sim3_apply.restype = None
         h.ellc_sim3_default_params.restype = None
+    if hasattr(h, "ellc_light_default_params"):
+        h.ellc_light_default_params.restype = None
     if hasattr(h, "ellc_absorb_default_params"):
         h.ellc_absorb_default_params.restype = None
     for name in symbols:

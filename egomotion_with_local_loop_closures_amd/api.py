@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -10,6 +10,7 @@ ARITH_EXACT = 0
 ARITH_FAST = 1
 ERR_CAPACITY = -5
 MAP_POINT_DTYPE = np.dtype(EllcMapPoint)   # x y z var (f32), px py (u16), intensity support (u8), source (u16): 24 bytes
+LIGHT_NORMAL_DTYPE = np.dtype(EllcLightNormal)   # sum_w, sum_w_s, sum_w_t, sum_w_ss, sum_w_st, sum_w_tt, chi2_photo (f64), four int32 counts: 72 bytes
 SIM3_NORMAL_DTYPE = np.dtype(EllcSim3Normal)   # H (28 f64), b (7 f64), chi2_photo, chi2_depth (f64), six int32 counts: 320 bytes
 HYP_FIELDS = ("invDepth", "invDepthSmoothed", "variance", "varianceSmoothed", "validity", "blacklisted", "valid")
 
@@ -525,6 +526,67 @@ class Context:
             res["trace_rec"] = [tR[b, :n[b]].copy() for b in range(B)]
         return res
 
+    # ---- affine brightness in the Sim(3) refinement: Ip = gain * Is + offset, a light is (gain, offset) per pair, None means (1, 0)
+    @staticmethod
+    def _lights(lights, B):
+        return None if lights is None else np.ascontiguousarray(lights, np.float32).reshape(B, 2)
+
+    def light_step(self, src_slots, dst_slots, Ts, lights=None, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None, _fn=None, _tail=()):
+        """The normal equations of the weighted fit of Iw on Is (ellc_keyframe_light_step) over the photometric pixels of sim3_step at
+        Ts[b], the Huber weights taken at lights[b]. params: as sim3_step (sigma_i2 and huber_k are read). Returns a structured array
+        of B ellc_light_normal records: sum_w, sum_w_s, sum_w_t, sum_w_ss, sum_w_st, sum_w_tt, chi2_photo (f64), n_kept, n_in_view,
+        n_photo, n_photo_huber (int32). light_solve turns a record into a light."""
+        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
+        li = self._lights(lights, B)
+        out = np.zeros(B, LIGHT_NORMAL_DTYPE)
+        name = "ellc_keyframe_light_step" if _fn is None else _fn
+        self._ck(getattr(self._l, name)(self.h, B, _p(src), _p(dst), _p(T), _p(li), int(level), C.byref(flt), C.byref(prm), _p(out), *_tail), name)
+        return out
+
+    def sim3_step_lit(self, src_slots, dst_slots, Ts, lights=None, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None, _fn=None,
+                      _tail=()):
+        """sim3_step with the photometric residual taken against gain * Is + offset (ellc_keyframe_sim3_step_lit); lights None, or (1, 0)
+        for a pair, gives sim3_step's bytes."""
+        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
+        li = self._lights(lights, B)
+        out = np.zeros(B, SIM3_NORMAL_DTYPE)
+        name = "ellc_keyframe_sim3_step_lit" if _fn is None else _fn
+        self._ck(getattr(self._l, name)(self.h, B, _p(src), _p(dst), _p(T), _p(li), int(level), C.byref(flt), C.byref(prm), _p(out), *_tail), name)
+        return out
+
+    def sim3_align_lit(self, src_slots, dst_slots, Ts, lights=None, level_from=0, level_to=0, max_iter=10, eps=1e-4, max_var=0.0, min_support=0,
+                       support_k2=1.0, stride=1, params=None, light_params=None, trace=False):
+        """sim3_align's loop with the light fitted before every Gauss-Newton step (ellc_keyframe_sim3_align_lit): per evaluation the
+        light record at (T, l), l' = light_solve of it, the Sim(3) record at (T, l'). light_params: dict of gain_min, gain_max,
+        min_pixels (defaults 0.25, 4, 16). Returns dict(T, light = [B][2] f32, rec, light_rec, iters) and, with trace=True, trace_T,
+        trace_light, trace_rec, trace_light_rec per pair in order of evaluation (the final evaluation included)."""
+        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
+        li = self._lights(lights, B)
+        lp = _as_light_params(light_params)
+        n_levels = max(int(level_from) - int(level_to) + 1, 1)
+        cap = n_levels * max(int(max_iter), 1) + 1
+        T_out = np.zeros((B, 12), np.float32)
+        l_out = np.zeros((B, 2), np.float32)
+        out = np.zeros(B, SIM3_NORMAL_DTYPE)
+        lrec = np.zeros(B, LIGHT_NORMAL_DTYPE)
+        iters = np.zeros((B, n_levels), np.int32)
+        tT = np.zeros((B, cap, 12), np.float32) if trace else None
+        tR = np.zeros((B, cap), SIM3_NORMAL_DTYPE) if trace else None
+        tL = np.zeros((B, cap, 2), np.float32) if trace else None
+        tLR = np.zeros((B, cap), LIGHT_NORMAL_DTYPE) if trace else None
+        self._ck(self._l.ellc_keyframe_sim3_align_lit(self.h, B, _p(src), _p(dst), _p(T), _p(li), int(level_from), int(level_to), C.byref(flt),
+                                                      C.byref(prm), C.byref(lp), int(max_iter), C.c_float(eps), _p(T_out), _p(l_out), _p(out), _p(lrec),
+                                                      _p(iters), _p(tT), _p(tR), _p(tL), _p(tLR), cap if trace else 0),
+                 "ellc_keyframe_sim3_align_lit")
+        res = dict(T=T_out, light=l_out, rec=out, light_rec=lrec, iters=iters)
+        if trace:
+            n = [int((tR[b]["n_kept"] >= 0).sum()) for b in range(B)]
+            res["trace_T"] = [tT[b, :n[b]].copy() for b in range(B)]
+            res["trace_rec"] = [tR[b, :n[b]].copy() for b in range(B)]
+            res["trace_light"] = [tL[b, :n[b]].copy() for b in range(B)]
+            res["trace_light_rec"] = [tLR[b, :n[b]].copy() for b in range(B)]
+        return res
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -702,6 +764,20 @@ class Context:
                  "ellc_profile_sim3_step")
         return out, ms.value
 
+    def profile_light_step(self, src_slots, dst_slots, Ts, lights=None, **kw):
+        """light_step through ellc_profile_light_step: (records, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_light_step")
+        ms = C.c_float(0)
+        out = self.light_step(src_slots, dst_slots, Ts, lights, _fn="ellc_profile_light_step", _tail=(C.byref(ms),), **kw)
+        return out, ms.value
+
+    def profile_sim3_step_lit(self, src_slots, dst_slots, Ts, lights=None, **kw):
+        """sim3_step_lit through ellc_profile_sim3_step_lit: (records, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_sim3_step_lit")
+        ms = C.c_float(0)
+        out = self.sim3_step_lit(src_slots, dst_slots, Ts, lights, _fn="ellc_profile_sim3_step_lit", _tail=(C.byref(ms),), **kw)
+        return out, ms.value
+
     def profile_calibrate_read(self, nbytes, reps=10):
         self._need_diag("ellc_profile_calibrate_read")
         ms = C.c_float(0)
@@ -777,6 +853,31 @@ def sim3_params(sigma_i2=None, huber_k=None, gate_k2=None, depth_weight=None):
         if v is not None:
             setattr(p, k, v)
     return p
+
+
+def light_params(gain_min=None, gain_max=None, min_pixels=None):
+    """ellc_light_params: the library's defaults (ellc_light_default_params) with the given fields replaced."""
+    p = EllcLightParams()
+    _lib.lib().ellc_light_default_params(C.byref(p))
+    for k, v in (("gain_min", gain_min), ("gain_max", gain_max), ("min_pixels", min_pixels)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def _as_light_params(p):
+    return p if isinstance(p, EllcLightParams) else light_params(**(p or {}))
+
+
+def light_solve(rec, light_in=None, params=None):
+    """ellc_light_solve of one ellc_light_normal record (a row of light_step's array): (light f32 [2], refused). params: an
+    ellc_light_params (light_params()) or a dict of its fields; light_in None means (1, 0)."""
+    r = np.ascontiguousarray(np.asarray(rec, LIGHT_NORMAL_DTYPE).reshape(1))
+    p = _as_light_params(params)
+    li = None if light_in is None else np.ascontiguousarray(light_in, np.float32).reshape(2)
+    out = np.zeros(2, np.float32)
+    refused = _lib.lib().ellc_light_solve(_p(r), C.byref(p), _p(li), _p(out))
+    return out, bool(refused)
 
 
 def absorb_params(agree_k2=None, max_fold=None, photo_gate=None, src_validity=None, finalise=None):

@@ -269,6 +269,7 @@ struct ellc_ctx {
   // ellc_keyframe_depth_consistency, ellc_keyframe_sim3_step / _align, ellc_keyframe_trial_propagate: a PairScratch each, and the trial
   // call's bitmaps
   ellc::PairScratch consist, sim3, trial;
+  ellc::PairScratch light, sim3l;           // ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit (both through ellc_keyframe_sim3_align_lit too)
   unsigned* trial_bits_d = nullptr;         // [requests of one launch][ceil(W*H / 32)] one bit per target pixel
   size_t trial_bits_cap = 0;                //   words it holds
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each

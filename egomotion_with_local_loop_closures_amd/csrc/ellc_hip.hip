@@ -1243,6 +1243,8 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   ellc::pair_free(c->consist);
   ellc::pair_free(c->sim3);
   ellc::pair_free(c->trial);
+  ellc::pair_free(c->light);
+  ellc::pair_free(c->sim3l);
   if (c->trial_bits_d) (void)hipFree(c->trial_bits_d);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
   if (c->ingest_bgr) (void)hipFree(c->ingest_bgr);
@@ -2737,3 +2739,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 #include "ellc_sim3_impl.hpp"
 #include "ellc_absorb_impl.hpp"
 #include "ellc_trial_impl.hpp"
+#include "ellc_light_impl.hpp"

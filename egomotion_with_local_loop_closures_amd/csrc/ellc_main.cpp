@@ -32,6 +32,9 @@
 //                    chi2_photo chi2_depth iters" - the similarity transform from the candidate's camera into the pushed keyframe's,
 //                    refined over seven parameters from the pose the batch returned (ellc_keyframe_sim3_align;
 //                    globalOptimize::refineMatchSim3); every other file is unchanged. With --world > 1 every rank computes the whole batch
+// --match-light      (LC mode, with --match-sim3 only: a usage error otherwise) the refinement fits an affine brightness between the
+//                    pair before every step (ellc_keyframe_sim3_align_lit; globalOptimize::matchAffineLight) and every line of the
+//                    --match-sim3 file ends in " gain offset"; without the flag every output file is as before
 // --map FILE         (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
 //                    level 0, no variance test, at least 3 supporting neighbours, support_k2 1, every pixel), written as binary PLY
 //                    (x y z float, intensity uchar, var float); every other file is unchanged
@@ -72,7 +75,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -80,7 +83,7 @@ int main(int argc, char** argv) {
   bool lc = false;
   int levels = 4;
   std::string save_mats, replicate, init_poses;
-  bool bgr = false, undistort = true, no_fused = false;
+  bool bgr = false, undistort = true, no_fused = false, match_light = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
   std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
   for (int i = 6; i < argc; i++) {
@@ -101,6 +104,7 @@ int main(int argc, char** argv) {
     else if (a == "--match-quality" && i + 1 < argc) match_quality = argv[++i];
     else if (a == "--match-geometry" && i + 1 < argc) match_geometry = argv[++i];
     else if (a == "--match-sim3" && i + 1 < argc) match_sim3 = argv[++i];
+    else if (a == "--match-light") match_light = true;
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (a == "--fuse" && i + 1 < argc) fuse_file = argv[++i];
@@ -109,6 +113,10 @@ int main(int argc, char** argv) {
     else if (a == "--restore-connection" && i + 1 < argc) restore_connection = argv[++i];
     else if (!a.empty() && a[0] >= '0' && a[0] <= '9') levels = std::atoi(a.c_str());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return -1; }
+  }
+  if (match_light && match_sim3.empty()) {
+    std::fprintf(stderr, "--match-light needs --match-sim3 PATH: the light is fitted inside the Sim(3) refinement and reported in its file\n");
+    return -1;
   }
   if (!match_quality.empty() && world > 1) {
     std::fprintf(stderr, "--match-quality is for a single process: with --world > 1 the ranks exchange poses only (8 floats per alignment)\n");
@@ -185,6 +193,7 @@ int main(int argc, char** argv) {
       globalOptimizeLoop->match_sim3_file.open(match_sim3.c_str());
       if (!globalOptimizeLoop->match_sim3_file) { std::fprintf(stderr, "cannot open %s\n", match_sim3.c_str()); return -1; }
       globalOptimizeLoop->refineMatchSim3 = true;
+      globalOptimizeLoop->matchAffineLight = match_light;
     }
     if (lc && !absorb_matches.empty()) {
       globalOptimizeLoop->absorb_file.open(absorb_matches.c_str());

@@ -1,5 +1,5 @@
 // The host scaffold of the calls over the keyframe ring's semi-dense maps (ellc_keyframe_map_points, _render_depth, _fuse_depth,
-// _depth_consistency, _sim3_step / _align, _trial_propagate, ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes): what they
+// _depth_consistency, _sim3_step / _align, _light_step, _sim3_step_lit / _align_lit, _trial_propagate, ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes): what they
 // refuse alike, the view map_keep reads, the timing window of the diagnostic hooks, grow-only buffers and the launch loop of the pair
 // reductions. Included at the end of ellc_hip.hip in front of the *_impl.hpp of those calls (the library is one translation unit).
 // A new call of the family supplies a record type with rec_zero / rec_add / rec_wave_sum (ellc_pair_reduce.hpp), a pass kernel and a
@@ -137,13 +137,17 @@ ellc_status pair_reserve(ellc_ctx* c, PairScratch& s, int B, size_t stage_bytes,
 }
 
 // the [cap] source slots, [cap] destination slots, [cap][12] f32 transforms record, staged and on its way to the device
-// (requests beyond B are never read: blockIdx.y < B)
-ellc_status pair_stage_slots(ellc_ctx* c, PairScratch& s, int B, const int* src, const int* dst, const float* T12) {
+// (requests beyond B are never read: blockIdx.y < B). extra (may be NULL; then extra_words is 0): a further block of extra_words
+// 4-byte words a request behind the 14, [cap][extra_words], for a call whose requests carry more than slots and a transform; the
+// call has reserved 14 + extra_words words a request.
+ellc_status pair_stage_slots(ellc_ctx* c, PairScratch& s, int B, const int* src, const int* dst, const float* T12, const void* extra = nullptr,
+                             int extra_words = 0) {
   int* h = (int*)s.stage_h;
   std::memcpy(h, src, (size_t)B * sizeof(int));
   std::memcpy(h + s.cap, dst, (size_t)B * sizeof(int));
   std::memcpy(h + 2 * (size_t)s.cap, T12, (size_t)B * 12 * sizeof(float));
-  ELLC_HIP(c, hipMemcpyAsync(s.stage_d, s.stage_h, (size_t)14 * s.cap * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (extra) std::memcpy(h + 14 * (size_t)s.cap, extra, (size_t)B * extra_words * sizeof(int));
+  ELLC_HIP(c, hipMemcpyAsync(s.stage_d, s.stage_h, (size_t)(14 + extra_words) * s.cap * sizeof(int), hipMemcpyHostToDevice, c->stream));
   return ELLC_OK;
 }
 

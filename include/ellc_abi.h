@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 18   /* ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 19   /* ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -686,6 +686,83 @@ ellc_status ellc_keyframe_sim3_align(ellc_ctx* ctx, int B, const int* src_kf_slo
                                      int level_from, int level_to, const ellc_map_filter* filter, const ellc_sim3_params* params,
                                      int max_iter, float eps, float* T12_out, ellc_sim3_normal* out, int* iters_out,
                                      float* trace_T12, ellc_sim3_normal* trace_rec, int trace_capacity);
+
+/* ---- affine brightness in the Sim(3) refinement (v19) --------------------------------------------------------------
+ * Everything above takes a surface to have the same grey value in both keyframes. Between the two ends of a loop closure the
+ * camera's exposure has usually moved. The model here is Ip = gain * Is + offset in f32 (the product rounded, then the sum: two
+ * roundings, no contraction), Is the source's grey value as f32; the photometric residual becomes rp = Iw - Ip. A light of (1, 0)
+ * gives Ip == Is bit for bit. A LIGHT is two f32 per pair, light[2 * b] the gain and light[2 * b + 1] the offset; a NULL light
+ * means (1, 0) for every pair; a given light must be finite.
+ *
+ * ellc_keyframe_light_step: the normal equations of the weighted straight-line fit of Iw on Is for request b at T = T12 + 12 * b
+ * and light_in, over exactly the photometric pixels of ellc_keyframe_sim3_step: rules 1 to 3 of its comment apply word for word
+ * (n_kept, n_in_view, n_photo; Iw, Is). rp = Iw - Ip at light_in; e, wp and n_photo_huber as in rule 3 with that rp; of `params`
+ * only sigma_i2 and huber_k are read (all four are validated). wIs = wp * Is and wIw = wp * Iw in f32; the six products below
+ * are exact in double, so every term is known exactly. The record is a function of its own request alone, in the sense and by the
+ * means of ellc_keyframe_sim3_step (2048-pixel tiles, fixed order, double); its scratch and staging are its own. Synchronous;
+ * 1 <= B <= 2048; a refused call changes nothing and writes nothing. Errors: those of ellc_keyframe_sim3_step, and
+ * ELLC_ERR_BAD_ARG for a given light with a value that is not finite. */
+typedef struct {
+  double  sum_w;          /* sum (double)wp */
+  double  sum_w_s;        /* sum (double)wIs,             wIs = wp * Is in f32 */
+  double  sum_w_t;        /* sum (double)wIw,             wIw = wp * Iw in f32 */
+  double  sum_w_ss;       /* sum (double)wIs * (double)Is   (exact product) */
+  double  sum_w_st;       /* sum (double)wIs * (double)Iw   (exact product) */
+  double  sum_w_tt;       /* sum (double)wIw * (double)Iw   (exact product) */
+  double  chi2_photo;     /* sum (double)((rp * rp) * wp) at light_in */
+  int32_t n_kept, n_in_view, n_photo, n_photo_huber;   /* as in ellc_sim3_normal, n_photo_huber at light_in */
+} ellc_light_normal;      /* 72 bytes, every field naturally aligned */
+
+ellc_status ellc_keyframe_light_step(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12,
+                                     const float* light_in, int level, const ellc_map_filter* filter, const ellc_sim3_params* params,
+                                     ellc_light_normal* out);
+
+/* ellc_keyframe_sim3_step with rule 3's residual replaced by rp = Iw - Ip at `light`; nothing else differs (the Jacobian is that
+ * of Iw). light NULL, or (1, 0) for a pair, gives that pair the bytes of ellc_keyframe_sim3_step. Errors: those of
+ * ellc_keyframe_sim3_step, and ELLC_ERR_BAD_ARG for a given light with a value that is not finite. */
+ellc_status ellc_keyframe_sim3_step_lit(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12,
+                                        const float* light, int level, const ellc_map_filter* filter, const ellc_sim3_params* params,
+                                        ellc_sim3_normal* out);
+
+/* Host only, no device work (like ellc_sim3_solve). The fit of one record, in double:
+ *   det = sum_w * sum_w_ss - sum_w_s^2;  gain = (sum_w * sum_w_st - sum_w_s * sum_w_t) / det;
+ *   offset = (sum_w_t - gain * sum_w_s) / sum_w.
+ * It is ACCEPTED iff n_photo >= min_pixels, det > 1e-10 * sum_w * sum_w_ss, gain_min <= gain <= gain_max and |offset| <= 255
+ * (NaN fails every test). An accepted solve rounds both values to f32 once, stores them in light_out[0..1] and returns 0; a
+ * refused one stores light_in's bits and returns 1. light_in may be NULL, meaning (1, 0); light_out may be light_in. The
+ * defaults are design choices: a factor of four either way is more than the histogram gate of a loop closure lets through.
+ * The device entry points that take an ellc_light_params refuse (ELLC_ERR_BAD_ARG) a value that is not finite,
+ * !(0 < gain_min <= 1 <= gain_max) and min_pixels outside 2..2^30; ellc_light_solve itself checks nothing. */
+typedef struct {
+  float   gain_min, gain_max;   /* 0 < gain_min <= 1 <= gain_max */
+  int32_t min_pixels;           /* 2..2^30: photometric pixels a fit needs; 2^30 refuses every fit (at most 2^24 pixels a level) */
+} ellc_light_params;            /* 12 bytes */
+void ellc_light_default_params(ellc_light_params* params);   /* {0.25f, 4.0f, 16} */
+int  ellc_light_solve(const ellc_light_normal* n, const ellc_light_params* params, const float* light_in, float* light_out);
+
+/* ellc_keyframe_sim3_align's loop with the light fitted before every Gauss-Newton step. Pair b starts at T12_in + 12 * b and the
+ * light light_in + 2 * b (light_in NULL: (1, 0)). ONE EVALUATION of an active pair at (T, l) is, in this order:
+ *   1. the light record at (T, l)                 (ellc_keyframe_light_step);
+ *   2. l' = ellc_light_solve of it with light_params and l (a refused solve keeps l);
+ *   3. the Sim(3) record at (T, l')               (ellc_keyframe_sim3_step_lit);
+ *   4. the trace entry: T, l', the light record, the Sim(3) record.
+ * The pair carries l' on, across levels too. The solve of the Sim(3) record, the update of T, when a pair leaves a level, the
+ * launches without the pairs that have left, the final evaluation (it fills out[b], light_rec_out[b], and its l' goes to
+ * light_out + 2 * b) and iters_out are ellc_keyframe_sim3_align's. A pair's sequence of T's and lights depends on nothing but
+ * its own inputs. With min_pixels = 2^30 (every fit refused) and light_in NULL, the T's, the Sim(3) records and the iteration
+ * counts are ellc_keyframe_sim3_align's bit for bit.
+ *   trace_T12 / trace_rec / trace_light / trace_light_rec (each may be NULL): as in ellc_keyframe_sim3_align, entry
+ * b * trace_capacity + e; trace_light holds two f32 an entry. Unused entries: twelve zeros, two zeros, and records that are all
+ * zero but for n_kept = -1. trace_capacity must be at least n_levels * max_iter + 1 when any of the four is given.
+ *   light_rec_out may be NULL; T12_out, out and light_out may not. Everything is kept aside until the call has succeeded: a
+ * refused or failed call writes nothing. Errors: those of ellc_keyframe_sim3_align, a light_in with a value that is not finite,
+ * the refusals of ellc_light_params above, light_params or light_out NULL. */
+ellc_status ellc_keyframe_sim3_align_lit(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12_in,
+                                         const float* light_in, int level_from, int level_to, const ellc_map_filter* filter,
+                                         const ellc_sim3_params* params, const ellc_light_params* light_params, int max_iter, float eps,
+                                         float* T12_out, float* light_out, ellc_sim3_normal* out, ellc_light_normal* light_rec_out,
+                                         int* iters_out, float* trace_T12, ellc_sim3_normal* trace_rec, float* trace_light,
+                                         ellc_light_normal* trace_light_rec, int trace_capacity);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

@@ -447,13 +447,19 @@ class globalOptimize {
   // is the cube root of the determinant of its 3x3 block, rec the record at T, iters the updates over all levels - and match_sim3_file
   // (when open) gets "frameId kfId scale tx ty tz wx wy wz n_photo n_depth chi2_photo chi2_depth iters" per line, (wx, wy, wz) the
   // rotation vector of the 3x3 block over the scale. Every rank of a sharded run computes the whole batch, as for the geometry.
+  // matchAffineLight (off by default: nothing changes; it needs refineMatchSim3): the refinement fits an affine brightness between the
+  // pair before every step (ellc_keyframe_sim3_align_lit from the light (1, 0), the default ellc_light_params): the two ends of a loop
+  // closure lie far apart in time and cameras adjust their exposure. gain and offset are the light the loop ended with (1 and 0
+  // without matchAffineLight), and each line of match_sim3_file ends in " gain offset".
   struct MatchSim3 {
     ellc_sim3_normal rec;
     float T[12];
     double scale;
     int iters;
+    float gain, offset;
   };
   bool refineMatchSim3 = false;
+  bool matchAffineLight = false;
   std::vector<MatchSim3> lastMatchSim3;
   std::ofstream match_sim3_file;
   // What a closed loop teaches, kept in the TRACKING context (ellc_depth_absorb_keyframes): every candidate of the push's batch is folded
@@ -1029,9 +1035,19 @@ class globalOptimize {
         const int level_from = ring.cfg.levels > 1 ? 1 : 0, n_levels = level_from + 1;
         std::vector<ellc_sim3_normal> normal((size_t)B);
         std::vector<int> iters((size_t)B * n_levels);
-        ring.check(ellc_keyframe_sim3_align(ring.ctx, B, kf.data(), dst.data(), T.data(), level_from, 0, &filter, &params, 10, 1e-4f, Tout.data(),
-                                            normal.data(), iters.data(), nullptr, nullptr, 0),
-                   "ellc_keyframe_sim3_align");
+        std::vector<float> light((size_t)B * 2);
+        for (int b = 0; b < B; b++) { light[(size_t)b * 2] = 1.0f; light[(size_t)b * 2 + 1] = 0.0f; }
+        if (matchAffineLight) {
+          ellc_light_params light_params;
+          ellc_light_default_params(&light_params);
+          ring.check(ellc_keyframe_sim3_align_lit(ring.ctx, B, kf.data(), dst.data(), T.data(), nullptr, level_from, 0, &filter, &params, &light_params, 10,
+                                                  1e-4f, Tout.data(), light.data(), normal.data(), nullptr, iters.data(), nullptr, nullptr, nullptr, nullptr, 0),
+                     "ellc_keyframe_sim3_align_lit");
+        } else {
+          ring.check(ellc_keyframe_sim3_align(ring.ctx, B, kf.data(), dst.data(), T.data(), level_from, 0, &filter, &params, 10, 1e-4f, Tout.data(),
+                                              normal.data(), iters.data(), nullptr, nullptr, 0),
+                     "ellc_keyframe_sim3_align");
+        }
         lastMatchSim3.assign((size_t)B, MatchSim3());
         for (int b = 0; b < B; b++) {
           MatchSim3& q = lastMatchSim3[(size_t)b];
@@ -1043,6 +1059,8 @@ class globalOptimize {
           q.scale = std::cbrt(det);
           q.iters = 0;
           for (int l = 0; l < n_levels; l++) q.iters += iters[(size_t)b * n_levels + l];
+          q.gain = light[(size_t)b * 2];
+          q.offset = light[(size_t)b * 2 + 1];
         }
       }
       for (int b = 0; b < B; b++) {
@@ -1072,7 +1090,9 @@ class globalOptimize {
           }
           match_sim3_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << (m.frameId + rt->BATCH_START_ID - 1) << " " << q.scale << " " << q.T[3]
                           << " " << q.T[7] << " " << q.T[11] << " " << w6[0] << " " << w6[1] << " " << w6[2] << " " << q.rec.n_photo << " "
-                          << q.rec.n_depth << " " << q.rec.chi2_photo << " " << q.rec.chi2_depth << " " << q.iters << "\n";
+                          << q.rec.n_depth << " " << q.rec.chi2_photo << " " << q.rec.chi2_depth << " " << q.iters;
+          if (matchAffineLight) match_sim3_file << " " << q.gain << " " << q.offset;
+          match_sim3_file << "\n";
         }
         if (collectMatchGeometry && match_geometry_file.is_open()) {
           const MatchGeometry& q = lastMatchGeometry[(size_t)b];

@@ -1,0 +1,436 @@
+"""ellc_keyframe_light_step / ellc_keyframe_sim3_step_lit / ellc_keyframe_sim3_align_lit (ABI v19) against tests/light_reference.py,
+on the world, batch and shapes of tests/test_gpu_sim3.py (whose helpers are used, not copied). The reference is fed the slots' planes
+as read back, so the new kernels and the loop around them are the only thing under test: integer fields are compared with ==, each
+double sum against the exactly rounded sum of the same exactly known terms, the loop link by link from its traces, and the recovery
+of a known similarity under a changed exposure against the reference's own alternating loop and against the loop without a light."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import light_reference as LR
+import sim3_reference as S
+import test_gpu_sim3 as G
+from egomotion_with_local_loop_closures_amd import synth
+from helpers import gpu_problem
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+FILTERS, BATCH, SHAPES, fkw = G.FILTERS, G.BATCH, G.SHAPES, G.fkw
+BAD_ARG, NOT_READY = G.BAD_ARG, G.NOT_READY
+LIGHTS = [(1.0, 0.0), (0.8, 25.0), (1.25, -20.0), (0.7993, 25.22)]
+LIGHT_IDS = ["unit", "dim", "bright", "fitted"]
+EPS, MAX_ITER = G.EPS, G.MAX_ITER
+FROZEN = dict(min_pixels=1 << 30)
+
+
+def lights_of(light, n):
+    return np.tile(np.asarray(light, F), (n, 1))
+
+
+def reference(world, src, dst, level, T, flt, light, params=None):
+    """light_reference.step of one request, computed once per world and left unchanged (both records come from one walk)."""
+    key = ("light", src, dst, level, np.asarray(T, F).tobytes(), tuple(flt), np.asarray(light, F).tobytes(), tuple(sorted((params or {}).items())))
+    if key not in world["refs"]:
+        world["refs"][key] = LR.step(G.planes_of(world, src, level), G.planes_of(world, dst, level), G.intr_of(world, level), T, flt, params, light)
+    return world["refs"][key]
+
+
+def check_light_against(got, ref, what):
+    """One light record against the reference: integers with ==, each of the seven double sums within n 2^-52 sum |term| of the exactly
+    rounded sum. Returns the largest distance / bound."""
+    for k in LR.LIGHT_INT_FIELDS:
+        assert int(got[k]) == ref[k], (what, k, int(got[k]), ref[k])
+    worst = 0.0
+    for name, want, bound in LR.light_sums_of(ref):
+        dist = abs(float(got[name]) - want)
+        assert dist <= bound, (what, name, float(got[name]), want, dist, bound)
+        if bound > 0:
+            worst = max(worst, dist / bound)
+    return worst
+
+
+@pytest.fixture(scope="module", params=list(SHAPES))
+def world(request, ellc):
+    wd = G.make_world(ellc, request.param)
+    yield wd
+    wd["ctx"].close()
+
+
+@pytest.fixture(scope="module")
+def world64(ellc):
+    wd = G.make_world(ellc, "64x48")
+    yield wd
+    wd["ctx"].close()
+
+
+@pytest.mark.parametrize("flt", FILTERS, ids=["all", "filtered"])
+@pytest.mark.parametrize("light", LIGHTS, ids=LIGHT_IDS)
+def test_steps_against_the_reference(world, flt, light):
+    """Both calls, every level, the six pairs; and the two calls against each other at the same T and light: the four counts with ==,
+    chi2_photo within its bound (each is within half of it of the exactly rounded sum)."""
+    ctx = world["ctx"]
+    src, dst, Ts = G.batch_args(world)
+    li = lights_of(light, len(BATCH))
+    worst = 0.0
+    for level in range(world["L"]):
+        got_l = ctx.light_step(src, dst, Ts, li, level=level, **fkw(flt))
+        got_s = ctx.sim3_step_lit(src, dst, Ts, li, level=level, **fkw(flt))
+        refs = [reference(world, s, d, level, world["Ts"][t], flt, light) for s, d, t in BATCH]
+        for b, ref in enumerate(refs):
+            what = "%s level %d filter %s light %s pair %d->%d" % (world["shape"], level, flt, light, src[b], dst[b])
+            worst = max(worst, check_light_against(got_l[b], ref, what))
+            G.check_against(got_s[b], ref, what, quiet=True)
+            for k in LR.LIGHT_INT_FIELDS:
+                assert int(got_l[b][k]) == int(got_s[b][k]), (what, k)
+            bound = ref["n_chi2_photo"] * 2.0 ** -52 * ref["abs_chi2_photo"]
+            assert abs(float(got_l[b]["chi2_photo"]) - float(got_s[b]["chi2_photo"])) <= bound, what
+        assert sum(r["n_photo"] for r in refs) > 0 and sum(r["n_photo_huber"] for r in refs) > 0
+    print(world["shape"], flt, light, "largest distance / bound of the light sums %.3g" % worst)
+    if light == LIGHTS[1]:   # other parameters reach both kernels
+        other = dict(sigma_i2=4.0, huber_k=3.0, gate_k2=0.5, depth_weight=2.5)
+        got_l = ctx.light_step(src, dst, Ts, li, level=0, params=other, **fkw(flt))
+        got_s = ctx.sim3_step_lit(src, dst, Ts, li, level=0, params=other, **fkw(flt))
+        for b, (s, d, t) in enumerate(BATCH):
+            ref = reference(world, s, d, 0, world["Ts"][t], flt, light, other)
+            check_light_against(got_l[b], ref, "other parameters %d" % b)
+            G.check_against(got_s[b], ref, "other parameters %d" % b, quiet=True)
+
+
+def test_unit_light_gives_the_bytes_of_sim3_step(world):
+    ctx = world["ctx"]
+    src, dst, Ts = G.batch_args(world)
+    n = len(BATCH)
+    for flt in FILTERS:
+        for level in range(world["L"]):
+            plain = ctx.sim3_step(src, dst, Ts, level=level, **fkw(flt))
+            assert int(plain["n_photo"].sum()) > 0
+            assert ctx.sim3_step_lit(src, dst, Ts, None, level=level, **fkw(flt)).tobytes() == plain.tobytes(), (flt, level)
+            assert ctx.sim3_step_lit(src, dst, Ts, lights_of((1.0, 0.0), n), level=level, **fkw(flt)).tobytes() == plain.tobytes(), (flt, level)
+            mixed = lights_of((1.0, 0.0), n); mixed[1::2] = (0.8, 25.0)   # a pair's record does not see its neighbours' lights
+            got = ctx.sim3_step_lit(src, dst, Ts, mixed, level=level, **fkw(flt))
+            assert got[0::2].tobytes() == plain[0::2].tobytes() and (level > 0 or got[1::2].tobytes() != plain[1::2].tobytes()), (flt, level)
+            assert ctx.light_step(src, dst, Ts, None, level=level, **fkw(flt)).tobytes() == \
+                ctx.light_step(src, dst, Ts, lights_of((1.0, 0.0), n), level=level, **fkw(flt)).tobytes()
+
+
+def mixed_lights(n):
+    return np.stack([np.asarray(LIGHTS[b % len(LIGHTS)], F) for b in range(n)])
+
+
+def test_a_record_is_a_function_of_its_own_inputs(world):
+    ctx = world["ctx"]
+    src, dst, Ts = G.batch_args(world)
+    n = len(BATCH)
+    li = mixed_lights(n)
+    for name in ("light_step", "sim3_step_lit"):
+        call = getattr(ctx, name)
+        for level in range(world["L"]):
+            whole = call(src, dst, Ts, li, level=level, **fkw(FILTERS[1]))
+            assert int(whole["n_photo"].sum()) > 0
+            for b in range(n):   # each request alone
+                one = call(src[b:b + 1], dst[b:b + 1], Ts[b:b + 1], li[b:b + 1], level=level, **fkw(FILTERS[1]))
+                assert one.tobytes() == whole[b:b + 1].tobytes(), (name, level, b)
+            rev = call(src[::-1], dst[::-1], Ts[::-1], li[::-1], level=level, **fkw(FILTERS[1]))
+            assert rev[::-1].tobytes() == whole.tobytes(), (name, level)
+            twice = call(src * 2, dst * 2, np.concatenate([Ts, Ts]), np.concatenate([li, li]), level=level, **fkw(FILTERS[1]))
+            assert twice[:n].tobytes() == whole.tobytes() and twice[n:].tobytes() == whole.tobytes(), (name, level)
+
+
+@pytest.mark.parametrize("shape", ["64x48", "131x67"])
+def test_another_configuration_gives_the_same_bytes(ellc, shape):
+    one = G.make_world(ellc, shape, arith=ellc.ARITH_EXACT)
+    two = G.make_world(ellc, shape, arith=ellc.ARITH_FAST, grid_batch=4, max_batch=7)
+    try:
+        src, dst, Ts = G.batch_args(one)
+        li = mixed_lights(len(BATCH))
+        for level in range(one["L"]):
+            for name in ("light_step", "sim3_step_lit"):
+                a = getattr(one["ctx"], name)(src, dst, Ts, li, level=level, **fkw(FILTERS[0]))
+                b = getattr(two["ctx"], name)(src, dst, Ts, li, level=level, **fkw(FILTERS[0]))
+                assert int(a["n_photo"].sum()) > 0 and a.tobytes() == b.tobytes(), (name, level)
+    finally:
+        one["ctx"].close(); two["ctx"].close()
+
+
+def test_2048_requests_in_one_call(world64):
+    """The largest batch: the nine ordered pairs of the three scenes at three transforms and four lights, over and over (period 36)."""
+    ctx = world64["ctx"]
+    pairs = [(s, d) for s in range(3) for d in range(3)]
+    src = [pairs[b % 9][0] for b in range(2048)]
+    dst = [pairs[b % 9][1] for b in range(2048)]
+    Ts = np.stack([world64["Ts"][b % 3] for b in range(2048)])
+    li = np.stack([np.asarray(LIGHTS[b % 4], F) for b in range(2048)])
+    for name in ("light_step", "sim3_step_lit"):
+        got = getattr(ctx, name)(src, dst, Ts, li, **fkw(FILTERS[0]))
+        assert got.shape == (2048,)
+        for b in range(0, 36, 5):
+            ref = reference(world64, src[b], dst[b], 0, Ts[b], FILTERS[0], LIGHTS[b % 4])
+            if name == "light_step":
+                check_light_against(got[b], ref, "request %d of 2048" % b)
+            else:
+                G.check_against(got[b], ref, "request %d of 2048" % b, quiet=True)
+        for b in range(36, 2048):
+            assert got[b:b + 1].tobytes() == got[b % 36:b % 36 + 1].tobytes(), (name, b)
+        small = getattr(ctx, name)(src[:36], dst[:36], Ts[:36], li[:36], **fkw(FILTERS[0]))   # after the staging has grown: the same bytes
+        assert small.tobytes() == got[:36].tobytes(), name
+
+
+PATTERN = 0xA5
+GOOD_PARAMS = (16.0, 1.345, 9.0, 1.0)
+GOOD_LIGHT_PARAMS = (0.25, 4.0, 16)
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def raw_step(ctx, ellc, which, src, dst, T, light=(1.0, 0.0), level=0, flt=(0.0, 0, 1.0, 1), params=GOOD_PARAMS, null=None, B=None):
+    """(status, out untouched?) of ellc_keyframe_light_step / ellc_keyframe_sim3_step_lit, not raised. light: one light for every request,
+    an [n][2] array, or None for a NULL pointer; null: which other pointer argument to pass as NULL."""
+    s = np.ascontiguousarray(src, np.int32).reshape(-1)
+    d = np.ascontiguousarray(dst, np.int32).reshape(-1)
+    B = s.size if B is None else B
+    n = max(s.size, abs(B), 1)
+    Tn = np.ascontiguousarray(np.tile(np.asarray(T, F).reshape(-1)[:12], n))
+    li = None if light is None else np.ascontiguousarray(np.broadcast_to(np.asarray(light, F), (n, 2)))
+    f = ellc._lib.EllcMapFilter(flt[0], int(flt[1]), flt[2], int(flt[3]))
+    prm = ellc._lib.EllcSim3Params(*params)
+    size = 72 if which == "light" else 320
+    out = np.full(size * n, PATTERN, np.uint8)
+    fn = ctx._l.ellc_keyframe_light_step if which == "light" else ctx._l.ellc_keyframe_sim3_step_lit
+    st = fn(ctx.h, B, None if null == "src" else _p(s), None if null == "dst" else _p(d), None if null == "T" else _p(Tn), _p(li), int(level),
+            None if null == "filter" else C.byref(f), None if null == "params" else C.byref(prm), None if null == "out" else _p(out))
+    return st, bool((out == PATTERN).all())
+
+
+def raw_align(ctx, ellc, T, light=(1.0, 0.0), level_from=0, level_to=0, max_iter=10, eps=1e-4, params=GOOD_PARAMS, light_params=GOOD_LIGHT_PARAMS,
+              trace_capacity=None, null=None, src=(0,), dst=(1,)):
+    """(status, every output untouched?) of ellc_keyframe_sim3_align_lit for one pair, not raised."""
+    s = np.ascontiguousarray(src, np.int32); d = np.ascontiguousarray(dst, np.int32)
+    Tn = np.ascontiguousarray(T, F).reshape(12)
+    li = None if light is None else np.ascontiguousarray(light, F).reshape(2)
+    f = ellc._lib.EllcMapFilter(0.0, 0, 1.0, 1)
+    prm = ellc._lib.EllcSim3Params(*params)
+    lp = ellc._lib.EllcLightParams(*light_params)
+    cap = 64 * 8 + 1
+    outs = dict(T=np.full(48, PATTERN, np.uint8), light=np.full(8, PATTERN, np.uint8), rec=np.full(320, PATTERN, np.uint8), lrec=np.full(72, PATTERN, np.uint8),
+                iters=np.full(4 * 8, PATTERN, np.uint8), tT=np.full(48 * cap, PATTERN, np.uint8), tR=np.full(320 * cap, PATTERN, np.uint8),
+                tL=np.full(8 * cap, PATTERN, np.uint8), tLR=np.full(72 * cap, PATTERN, np.uint8))
+    st = ctx._l.ellc_keyframe_sim3_align_lit(ctx.h, 1, _p(s), _p(d), _p(Tn), _p(li), int(level_from), int(level_to), C.byref(f), C.byref(prm),
+                                             None if null == "light_params" else C.byref(lp), int(max_iter), C.c_float(eps),
+                                             None if null == "T_out" else _p(outs["T"]), None if null == "light_out" else _p(outs["light"]),
+                                             None if null == "out" else _p(outs["rec"]), None if null == "light_rec_out" else _p(outs["lrec"]),
+                                             _p(outs["iters"]), _p(outs["tT"]), _p(outs["tR"]), _p(outs["tL"]), _p(outs["tLR"]),
+                                             cap if trace_capacity is None else trace_capacity)
+    return st, all(bool((a == PATTERN).all()) for k, a in outs.items() if k != "lrec" or null != "light_rec_out")
+
+
+def test_refused_calls_write_nothing_and_touch_no_slot(world64, ellc):
+    ctx, T = world64["ctx"], world64["Ts"][1]
+
+    def snapshot():
+        out = []
+        for s in range(4):
+            for l in range(world64["L"]):
+                d, v = ctx.keyframe_depth_level(s, l)
+                out.append(d.tobytes() + v.tobytes() + ctx.image_level(True, s, l)[0].tobytes())
+        return out
+
+    before = snapshot()
+    N = G.N_SLOTS
+    for which in ("light", "sim3"):
+        def refused(code, src=(0,), dst=(1,), **kw):
+            st, untouched = raw_step(ctx, ellc, which, list(src), list(dst), T, **kw)
+            assert st == code and untouched, (which, st, code, untouched, src, dst, kw)
+
+        def accepted(src=(0,), dst=(1,), **kw):
+            st, untouched = raw_step(ctx, ellc, which, list(src), list(dst), T, **kw)
+            assert st == 0 and not untouched, (which, st, src, dst, kw)
+
+        accepted(); accepted(light=None); accepted(light=(0.0, 0.0)); accepted(light=(-2.0, 300.0))   # any finite light is taken
+        # the light: a value that is not finite, in the gain or the offset, of the first request or a later one
+        for bad in (np.nan, np.inf, -np.inf):
+            refused(BAD_ARG, light=(bad, 0.0)); refused(BAD_ARG, light=(1.0, bad))
+            refused(BAD_ARG, src=(0, 0), dst=(1, 1), light=np.array([[1.0, 0.0], [1.0, bad]], F))
+        # what ellc_keyframe_sim3_step refuses
+        refused(BAD_ARG, B=0); refused(BAD_ARG, B=-1); refused(BAD_ARG, src=[0] * 2049, dst=[1] * 2049)
+        refused(BAD_ARG, src=(-1,)); refused(BAD_ARG, src=(N,)); refused(BAD_ARG, src=(0, N), dst=(1, 1))
+        refused(BAD_ARG, dst=(-1,)); refused(BAD_ARG, dst=(N,)); refused(BAD_ARG, src=(0, 0), dst=(1, N))
+        refused(BAD_ARG, level=-1); refused(BAD_ARG, level=world64["L"])
+        for null in ("src", "dst", "T", "filter", "params"):
+            refused(BAD_ARG, null=null)
+        assert raw_step(ctx, ellc, which, [0], [1], T, null="out")[0] == BAD_ARG
+        refused(BAD_ARG, flt=(0.0, -1, 1.0, 1)); refused(BAD_ARG, flt=(0.0, 9, 1.0, 1)); refused(BAD_ARG, flt=(0.0, 0, 1.0, 0))
+        refused(BAD_ARG, flt=(0.0, 0, -1.0, 1)); refused(BAD_ARG, flt=(0.0, 0, np.inf, 1)); refused(BAD_ARG, flt=(0.0, 0, np.nan, 1))
+        refused(BAD_ARG, flt=(np.nan, 0, 1.0, 1))
+        for k in range(4):   # every parameter: NaN, inf, negative; sigma_i2 and huber_k also 0
+            for bad in (np.nan, np.inf, -1.0) + ((0.0,) if k < 2 else ()):
+                refused(BAD_ARG, params=GOOD_PARAMS[:k] + (bad,) + GOOD_PARAMS[k + 1:])
+        accepted(params=(1e-3, 1e-3, 0.0, 0.0))
+        refused(NOT_READY, src=(G.IMAGE_ONLY_SLOT,)); refused(NOT_READY, dst=(G.IMAGE_ONLY_SLOT,))
+        refused(NOT_READY, src=(0, G.IMAGE_ONLY_SLOT), dst=(1, 1)); refused(NOT_READY, src=(0, 0), dst=(1, G.IMAGE_ONLY_SLOT))
+    with pytest.raises(ellc.EllcError):
+        ctx.light_step([G.IMAGE_ONLY_SLOT], [0], [T])
+    with pytest.raises(ellc.EllcError):
+        ctx.sim3_step_lit([0], [1], [T], [[np.nan, 0.0]])
+    # the loop: its own refusals, those of the light and of the light's parameters
+    assert raw_align(ctx, ellc, T) == (0, False) and raw_align(ctx, ellc, T, light=None) == (0, False)
+    assert raw_align(ctx, ellc, T, null="light_rec_out") == (0, False)
+    for kw in (dict(level_from=0, level_to=1), dict(level_from=world64["L"], level_to=0), dict(level_to=-1), dict(max_iter=0), dict(max_iter=65),
+               dict(eps=-1.0), dict(eps=np.nan), dict(eps=np.inf), dict(trace_capacity=10), dict(level_from=1, trace_capacity=20),
+               dict(params=(0.0, 1.345, 9.0, 1.0)), dict(src=(N,)), dict(null="T_out"), dict(null="out"), dict(null="light_out"), dict(null="light_params"),
+               dict(light=(np.nan, 0.0)), dict(light=(1.0, np.inf)),
+               dict(light_params=(np.nan, 4.0, 16)), dict(light_params=(0.25, np.inf, 16)), dict(light_params=(0.0, 4.0, 16)),
+               dict(light_params=(-0.5, 4.0, 16)), dict(light_params=(1.5, 4.0, 16)), dict(light_params=(0.25, 0.5, 16)),
+               dict(light_params=(0.25, 4.0, 1)), dict(light_params=(0.25, 4.0, 0)), dict(light_params=(0.25, 4.0, -5)),
+               dict(light_params=(0.25, 4.0, (1 << 30) + 1))):
+        st, untouched = raw_align(ctx, ellc, T, **kw)
+        assert st == BAD_ARG and untouched, (kw, st, untouched)
+    st, untouched = raw_align(ctx, ellc, T, dst=(G.IMAGE_ONLY_SLOT,))
+    assert st == NOT_READY and untouched
+    assert raw_align(ctx, ellc, T, trace_capacity=11) == (0, False) and raw_align(ctx, ellc, T, level_from=1, trace_capacity=21) == (0, False)
+    assert raw_align(ctx, ellc, T, light_params=(1.0, 1.0, 2)) == (0, False) and raw_align(ctx, ellc, T, light_params=(0.25, 4.0, 1 << 30)) == (0, False)
+    # an all-zero depth as source: nothing is kept, both records are all zero
+    assert not any(ctx.light_step([G.ZERO_SLOT], [0], [T], [[0.8, 25.0]]).tobytes())
+    assert not any(ctx.sim3_step_lit([G.ZERO_SLOT], [0], [T], [[0.8, 25.0]]).tobytes())
+    # the context still answers as before, and no plane of any slot has changed
+    src, dst, Ts = G.batch_args(world64)
+    got = ctx.light_step(src, dst, Ts, lights_of(LIGHTS[1], len(BATCH)), **fkw(FILTERS[0]))
+    for b, (s, d, t) in enumerate(BATCH):
+        check_light_against(got[b], reference(world64, s, d, 0, world64["Ts"][t], FILTERS[0], LIGHTS[1]), "after the refusals %d" % b)
+    assert snapshot() == before
+
+
+def test_the_loop_link_by_link(world, ellc):
+    """From the traces: every light record is light_step's at the traced T and the PREVIOUS light, every light is light_solve of it,
+    every Sim(3) record is sim3_step_lit's at that T and light, every next T is sim3_apply(sim3_solve(record), T) bit for bit;
+    iters, T, light and both final records agree with the traces; a pair carries its light across the levels."""
+    ctx, L = world["ctx"], world["L"]
+    batch = BATCH + [(0, G.ZERO_SLOT, 1)]
+    src, dst, Ts = G.batch_args(world, batch)
+    n = len(batch)
+    start = mixed_lights(n)
+    res = ctx.sim3_align_lit(src, dst, Ts, start, level_from=L - 1, level_to=0, max_iter=MAX_ITER, eps=EPS, trace=True, **fkw(FILTERS[0]))
+    by_level = {l: [] for l in range(L)}   # (pair, entry, the light the entry started from) of every evaluation, by the level the replay puts it on
+    updates = accepted = 0
+    for b in range(n):
+        tT, tR, tL, tLR = res["trace_T"][b], res["trace_rec"][b], res["trace_light"][b], res["trace_light_rec"][b]
+        assert tT[0].tobytes() == Ts[b].tobytes() and len(tT) == len(tR) == len(tL) == len(tLR)
+        e, prev = 0, start[b]
+        for k, level in enumerate(range(L - 1, -1, -1)):
+            made = 0
+            while True:
+                by_level[level].append((b, e, prev))
+                light, refused = ellc.light_solve(tLR[e], prev)
+                assert light.tobytes() == tL[e].tobytes(), (b, level, e, light, tL[e])
+                accepted += not refused
+                prev = tL[e]
+                xi, singular = ellc.sim3_solve(tR[e])
+                T_next = tT[e] if singular else ellc.sim3_apply(xi, tT[e])
+                e += 1
+                assert e < len(tT), (b, level)
+                assert tT[e].tobytes() == T_next.tobytes(), (b, level, e)
+                if singular:
+                    break
+                made += 1
+                updates += 1
+                if np.abs(xi).max() <= EPS or made >= MAX_ITER:
+                    break
+            assert int(res["iters"][b, k]) == made, (b, level)
+        by_level[0].append((b, e, prev))   # the final evaluation
+        assert e == len(tT) - 1, (b, e, len(tT))
+        light, _ = ellc.light_solve(tLR[e], prev)
+        assert light.tobytes() == tL[e].tobytes() == res["light"][b].tobytes(), b
+        assert tT[e].tobytes() == res["T"][b].tobytes() and tR[e].tobytes() == res["rec"][b:b + 1].tobytes(), b
+        assert tLR[e].tobytes() == res["light_rec"][b:b + 1].tobytes(), b
+    for level, entries in by_level.items():   # one call per level and kind: records do not depend on the batch
+        s_ = [src[b] for b, _, _ in entries]; d_ = [dst[b] for b, _, _ in entries]
+        T_ = np.stack([res["trace_T"][b][e] for b, e, _ in entries])
+        got_l = ctx.light_step(s_, d_, T_, np.stack([np.asarray(p, F) for _, _, p in entries]), level=level, **fkw(FILTERS[0]))
+        got_s = ctx.sim3_step_lit(s_, d_, T_, np.stack([res["trace_light"][b][e] for b, e, _ in entries]), level=level, **fkw(FILTERS[0]))
+        for k, (b, e, _) in enumerate(entries):
+            assert got_l[k:k + 1].tobytes() == res["trace_light_rec"][b][e:e + 1].tobytes(), (level, b, e)
+            assert got_s[k:k + 1].tobytes() == res["trace_rec"][b][e:e + 1].tobytes(), (level, b, e)
+    print(world["shape"], "updates checked", updates, "light solves accepted", accepted, "iters", res["iters"].tolist(), "lights", res["light"].tolist())
+    assert updates > 0 and accepted > 0
+    # without traces, without light_rec_out: the same T, lights and records; and a pair alone
+    plain = ctx.sim3_align_lit(src, dst, Ts, start, level_from=L - 1, level_to=0, max_iter=MAX_ITER, eps=EPS, **fkw(FILTERS[0]))
+    assert plain["T"].tobytes() == res["T"].tobytes() and plain["rec"].tobytes() == res["rec"].tobytes() and plain["light"].tobytes() == res["light"].tobytes()
+    one = ctx.sim3_align_lit(src[1:2], dst[1:2], Ts[1:2], start[1:2], level_from=L - 1, level_to=0, max_iter=MAX_ITER, eps=EPS, **fkw(FILTERS[0]))
+    assert one["T"].tobytes() == res["T"][1:2].tobytes() and one["light"].tobytes() == res["light"][1:2].tobytes()
+    assert one["iters"].tolist() == res["iters"][1:2].tolist()
+
+
+def test_a_frozen_light_is_sim3_align(world):
+    """min_pixels = 2^30 refuses every fit: with light_in NULL the T's, records, iteration counts and traces are ellc_keyframe_sim3_align's
+    bit for bit, and the light stays (1, 0)."""
+    ctx, L = world["ctx"], world["L"]
+    batch = BATCH + [(0, G.ZERO_SLOT, 1)]
+    src, dst, Ts = G.batch_args(world, batch)
+    kw = dict(level_from=L - 1, level_to=0, max_iter=MAX_ITER, eps=EPS, trace=True, **fkw(FILTERS[0]))
+    want = ctx.sim3_align(src, dst, Ts, **kw)
+    got = ctx.sim3_align_lit(src, dst, Ts, None, light_params=FROZEN, **kw)
+    assert int(want["iters"].sum()) > 0
+    assert got["T"].tobytes() == want["T"].tobytes() and got["rec"].tobytes() == want["rec"].tobytes() and got["iters"].tolist() == want["iters"].tolist()
+    assert got["light"].tobytes() == lights_of((1.0, 0.0), len(batch)).tobytes()
+    for b in range(len(batch)):
+        assert got["trace_T"][b].tobytes() == want["trace_T"][b].tobytes() and got["trace_rec"][b].tobytes() == want["trace_rec"][b].tobytes(), b
+        assert got["trace_light"][b].tobytes() == lights_of((1.0, 0.0), len(want["trace_T"][b])).tobytes(), b
+    # a frozen light that is not (1, 0) stays what it was given as
+    kept = ctx.sim3_align_lit(src, dst, Ts, lights_of(LIGHTS[1], len(batch)), light_params=FROZEN, level_from=0, level_to=0, max_iter=2, eps=EPS, **fkw(FILTERS[0]))
+    assert kept["light"].tobytes() == lights_of(LIGHTS[1], len(batch)).tobytes()
+
+
+EXPOSURES = [(0.8, 25.0), (1.25, -20.0), (0.6, 40.0)]
+# 23x17 is left out: on its 169 pixels the alternating reference misses the 1 % scale condition even on the unaltered image
+# (0.8 to 2.5 %), so there is no input on which the bar below could be set.
+RECOVERY_CASES = [("64x48", [0]), ("64x48", [1, 0]), ("131x67", [0])]
+
+
+@pytest.mark.parametrize("exposure", EXPOSURES, ids=["dim", "bright", "dimmer"])
+@pytest.mark.parametrize("shape,levels", RECOVERY_CASES, ids=["64x48-l0", "64x48-l10", "131x67-l0"])
+def test_recovery_under_a_changed_exposure(ellc, shape, levels, exposure):
+    """The inputs of test_gpu_sim3.test_recovery_of_a_known_similarity with the destination's image replaced by clip(rint(g I + o)).
+    Condition on the inputs: the reference's own alternating loop (numpy solve, scipy expm) ends within 1 % of the scale. Bar: the
+    library's scale, rotation and translation errors exceed that loop's by no more than a tenth of them (test_gpu_sim3's margin and
+    reason: the order of the double sums and one f32 ulp of T per update). Need: on the same inputs the loop without a light
+    (ellc_keyframe_sim3_align) ends with a rotation error above ten times the alternating reference's."""
+    w, h, L = SHAPES[shape]
+    g, o = exposure
+    scenes = synth.make_shared_frame_batch(w, h, 2, 21, rot=0.02, trans=0.04)
+    ctx = gpu_problem(ellc, w, h, L, scenes, max_keyframes=5)
+    try:
+        rigid = np.linalg.inv(synth.se3_exp(scenes[1]["xi_true"].astype(np.float64))) @ synth.se3_exp(scenes[0]["xi_true"].astype(np.float64))
+        world = dict(ctx=ctx, planes={}, intrinsics=scenes[0]["intrinsics"])
+        DST = 4
+        altered = np.clip(np.rint(g * np.asarray(scenes[1]["kf_image"], np.float64) + o), 0, 255).astype(np.uint8)
+        ctx.keyframe_upload(DST, altered)
+        ctx.keyframe_set_depth(DST, scenes[1]["depth0"], scenes[1]["var0"])
+        cases = []
+        for slot, k in ((2, 2.0), (3, 0.5)):
+            ctx.keyframe_upload(slot, scenes[0]["kf_image"])
+            ctx.keyframe_set_depth(slot, scenes[0]["depth0"] * np.float32(k), scenes[0]["var0"] / np.float32(k * k))
+            T_true = rigid[:3].copy(); T_true[:, :3] /= k
+            for sign, sigma in ((1.0, 0.1), (-1.0, -0.08)):
+                xi = sign * G.XI_START; xi[6] = sigma
+                cases.append((slot, k, T_true, S.apply(xi, T_true.astype(F).reshape(12))))
+        kw = dict(level_from=levels[0], level_to=0, max_iter=MAX_ITER, eps=EPS, **fkw(G.RECOVERY_FILTER))
+        src, dst, T0s = [c[0] for c in cases], [DST] * len(cases), np.stack([c[3] for c in cases])
+        res = ctx.sim3_align_lit(src, dst, T0s, None, **kw)
+        blind = ctx.sim3_align(src, dst, T0s, **kw)
+        for n, (slot, k, T_true, T0) in enumerate(cases):
+            T_ref, l_ref, iters_ref, share = LR.align(lambda s, l: G.planes_of(world, s, l), slot, DST, lambda l: G.intr_of(world, l), T0, levels,
+                                                      G.RECOVERY_FILTER, max_iter=MAX_ITER, eps=EPS)
+            e_ref, e_gpu, e_blind = S.sim3_errors(T_ref, T_true), S.sim3_errors(res["T"][n], T_true), S.sim3_errors(blind["T"][n], T_true)
+            print("%s levels %s exposure %s k %.1f: reference scale %.3g rot %.3g trans %.3g light (%.4f, %.3f) huber share %.3f iters %s | library scale "
+                  "%.3g rot %.3g trans %.3g light %s iters %s | without a light scale %.3g rot %.3g trans %.3g" % (
+                      (shape, levels, exposure, k) + e_ref + (float(l_ref[0]), float(l_ref[1]), share, iters_ref) + e_gpu +
+                      (res["light"][n].tolist(), res["iters"][n].tolist()) + e_blind))
+            assert e_ref[0] <= 0.01, ("the reference's own alternating loop misses the scale", shape, levels, exposure, k, e_ref)
+            for name, a, b in zip(("scale", "rotation", "translation"), e_gpu, e_ref):
+                assert a <= 1.1 * b, (name, shape, levels, exposure, k, a, b)
+            assert e_blind[1] > 10 * e_ref[1], ("the loop without a light does as well", shape, levels, exposure, k, e_blind, e_ref)
+    finally:
+        ctx.close()
