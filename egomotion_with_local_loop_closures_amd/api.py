@@ -496,11 +496,44 @@ class Context:
         in its 3x3 block. params: dict of sigma_i2, huber_k, gate_k2, depth_weight (defaults 16, 1.345, 9, 1). Returns a structured
         array of B ellc_sim3_normal records: H (28, upper triangle by rows), b (7), chi2_photo, chi2_depth (f64), n_kept, n_in_view,
         n_photo, n_photo_huber, n_depth, n_depth_gated (int32). A step solves H xi = -b (sim3_solve) and T <- sim3_apply(xi, T)."""
+        return self._pair_step("ellc_keyframe_sim3_step", SIM3_NORMAL_DTYPE, (), src_slots, dst_slots, Ts, level, max_var, min_support, support_k2, stride,
+                               params)
+
+    def _pair_step(self, name, dtype, lights, src_slots, dst_slots, Ts, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None, tail=()):
+        """The pair steps that return one record a pair (sim3_step, light_step, sim3_step_lit and their ellc_profile_* twins): entry
+        point `name`, records of `dtype`; lights is () for the call that takes no light, (lights,) for the others; tail follows `out`."""
         B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
-        out = np.zeros(B, SIM3_NORMAL_DTYPE)
-        self._ck(self._l.ellc_keyframe_sim3_step(self.h, B, _p(src), _p(dst), _p(T), int(level), C.byref(flt), C.byref(prm), _p(out)),
-                 "ellc_keyframe_sim3_step")
+        li = [self._lights(l, B) for l in lights]
+        out = np.zeros(B, dtype)
+        self._ck(getattr(self._l, name)(self.h, B, _p(src), _p(dst), _p(T), *[_p(l) for l in li], int(level), C.byref(flt), C.byref(prm), _p(out), *tail),
+                 name)
         return out
+
+    def _align(self, name, lit, src_slots, dst_slots, Ts, lights, level_from, level_to, max_iter, eps, max_var, min_support, support_k2, stride, params,
+               light_params, trace):
+        """sim3_align (lit false: no light, no light parameters, no light outputs or traces) and sim3_align_lit: the outputs, the
+        traces, the call, and each pair's traces cut to the evaluations it had (n_kept >= 0 in its trace_rec)."""
+        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
+        n_levels = max(int(level_from) - int(level_to) + 1, 1)
+        cap = n_levels * max(int(max_iter), 1) + 1
+        res = dict(T=np.zeros((B, 12), np.float32), rec=np.zeros(B, SIM3_NORMAL_DTYPE), iters=np.zeros((B, n_levels), np.int32))
+        tr = dict(trace_T=np.zeros((B, cap, 12), np.float32), trace_rec=np.zeros((B, cap), SIM3_NORMAL_DTYPE)) if trace else {}
+        fixed = (int(level_from), int(level_to), C.byref(flt), C.byref(prm))
+        if lit:
+            li = self._lights(lights, B)
+            lp = _as_light_params(light_params)
+            res.update(light=np.zeros((B, 2), np.float32), light_rec=np.zeros(B, LIGHT_NORMAL_DTYPE))
+            if trace:
+                tr.update(trace_light=np.zeros((B, cap, 2), np.float32), trace_light_rec=np.zeros((B, cap), LIGHT_NORMAL_DTYPE))
+            args = (_p(li),) + fixed + (C.byref(lp), int(max_iter), C.c_float(eps), _p(res["T"]), _p(res["light"]), _p(res["rec"]), _p(res["light_rec"]),
+                                        _p(res["iters"]), _p(tr.get("trace_T")), _p(tr.get("trace_rec")), _p(tr.get("trace_light")), _p(tr.get("trace_light_rec")))
+        else:
+            args = fixed + (int(max_iter), C.c_float(eps), _p(res["T"]), _p(res["rec"]), _p(res["iters"]), _p(tr.get("trace_T")), _p(tr.get("trace_rec")))
+        self._ck(getattr(self._l, name)(self.h, B, _p(src), _p(dst), _p(T), *args, cap if trace else 0), name)
+        if trace:
+            n = [int((tr["trace_rec"][b]["n_kept"] >= 0).sum()) for b in range(B)]
+            res.update({k: [t[b, :n[b]].copy() for b in range(B)] for k, t in tr.items()})
+        return res
 
     def sim3_align(self, src_slots, dst_slots, Ts, level_from=0, level_to=0, max_iter=10, eps=1e-4, max_var=0.0, min_support=0, support_k2=1.0,
                    stride=1, params=None, trace=False):
@@ -508,51 +541,27 @@ class Context:
         max_iter updates per level, a pair leaving a level when max |xi_i| <= eps or its system is singular. Returns dict(T = [B][12]
         f32, rec = the records at those T, iters = [B][levels visited] updates per level) and, with trace=True, trace_T / trace_rec:
         per pair the T of every evaluation in order and its record (the final evaluation included)."""
-        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
-        n_levels = max(int(level_from) - int(level_to) + 1, 1)
-        cap = n_levels * max(int(max_iter), 1) + 1
-        T_out = np.zeros((B, 12), np.float32)
-        out = np.zeros(B, SIM3_NORMAL_DTYPE)
-        iters = np.zeros((B, n_levels), np.int32)
-        tT = np.zeros((B, cap, 12), np.float32) if trace else None
-        tR = np.zeros((B, cap), SIM3_NORMAL_DTYPE) if trace else None
-        self._ck(self._l.ellc_keyframe_sim3_align(self.h, B, _p(src), _p(dst), _p(T), int(level_from), int(level_to), C.byref(flt), C.byref(prm),
-                                                  int(max_iter), C.c_float(eps), _p(T_out), _p(out), _p(iters), _p(tT), _p(tR), cap if trace else 0),
-                 "ellc_keyframe_sim3_align")
-        res = dict(T=T_out, rec=out, iters=iters)
-        if trace:
-            n = [int((tR[b]["n_kept"] >= 0).sum()) for b in range(B)]
-            res["trace_T"] = [tT[b, :n[b]].copy() for b in range(B)]
-            res["trace_rec"] = [tR[b, :n[b]].copy() for b in range(B)]
-        return res
+        return self._align("ellc_keyframe_sim3_align", False, src_slots, dst_slots, Ts, None, level_from, level_to, max_iter, eps, max_var, min_support,
+                           support_k2, stride, params, None, trace)
 
     # ---- affine brightness in the Sim(3) refinement: Ip = gain * Is + offset, a light is (gain, offset) per pair, None means (1, 0)
     @staticmethod
     def _lights(lights, B):
         return None if lights is None else np.ascontiguousarray(lights, np.float32).reshape(B, 2)
 
-    def light_step(self, src_slots, dst_slots, Ts, lights=None, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None, _fn=None, _tail=()):
+    def light_step(self, src_slots, dst_slots, Ts, lights=None, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None):
         """The normal equations of the weighted fit of Iw on Is (ellc_keyframe_light_step) over the photometric pixels of sim3_step at
         Ts[b], the Huber weights taken at lights[b]. params: as sim3_step (sigma_i2 and huber_k are read). Returns a structured array
         of B ellc_light_normal records: sum_w, sum_w_s, sum_w_t, sum_w_ss, sum_w_st, sum_w_tt, chi2_photo (f64), n_kept, n_in_view,
         n_photo, n_photo_huber (int32). light_solve turns a record into a light."""
-        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
-        li = self._lights(lights, B)
-        out = np.zeros(B, LIGHT_NORMAL_DTYPE)
-        name = "ellc_keyframe_light_step" if _fn is None else _fn
-        self._ck(getattr(self._l, name)(self.h, B, _p(src), _p(dst), _p(T), _p(li), int(level), C.byref(flt), C.byref(prm), _p(out), *_tail), name)
-        return out
+        return self._pair_step("ellc_keyframe_light_step", LIGHT_NORMAL_DTYPE, (lights,), src_slots, dst_slots, Ts, level, max_var, min_support, support_k2,
+                               stride, params)
 
-    def sim3_step_lit(self, src_slots, dst_slots, Ts, lights=None, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None, _fn=None,
-                      _tail=()):
+    def sim3_step_lit(self, src_slots, dst_slots, Ts, lights=None, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None):
         """sim3_step with the photometric residual taken against gain * Is + offset (ellc_keyframe_sim3_step_lit); lights None, or (1, 0)
         for a pair, gives sim3_step's bytes."""
-        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
-        li = self._lights(lights, B)
-        out = np.zeros(B, SIM3_NORMAL_DTYPE)
-        name = "ellc_keyframe_sim3_step_lit" if _fn is None else _fn
-        self._ck(getattr(self._l, name)(self.h, B, _p(src), _p(dst), _p(T), _p(li), int(level), C.byref(flt), C.byref(prm), _p(out), *_tail), name)
-        return out
+        return self._pair_step("ellc_keyframe_sim3_step_lit", SIM3_NORMAL_DTYPE, (lights,), src_slots, dst_slots, Ts, level, max_var, min_support,
+                               support_k2, stride, params)
 
     def sim3_align_lit(self, src_slots, dst_slots, Ts, lights=None, level_from=0, level_to=0, max_iter=10, eps=1e-4, max_var=0.0, min_support=0,
                        support_k2=1.0, stride=1, params=None, light_params=None, trace=False):
@@ -560,32 +569,8 @@ class Context:
         light record at (T, l), l' = light_solve of it, the Sim(3) record at (T, l'). light_params: dict of gain_min, gain_max,
         min_pixels (defaults 0.25, 4, 16). Returns dict(T, light = [B][2] f32, rec, light_rec, iters) and, with trace=True, trace_T,
         trace_light, trace_rec, trace_light_rec per pair in order of evaluation (the final evaluation included)."""
-        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
-        li = self._lights(lights, B)
-        lp = _as_light_params(light_params)
-        n_levels = max(int(level_from) - int(level_to) + 1, 1)
-        cap = n_levels * max(int(max_iter), 1) + 1
-        T_out = np.zeros((B, 12), np.float32)
-        l_out = np.zeros((B, 2), np.float32)
-        out = np.zeros(B, SIM3_NORMAL_DTYPE)
-        lrec = np.zeros(B, LIGHT_NORMAL_DTYPE)
-        iters = np.zeros((B, n_levels), np.int32)
-        tT = np.zeros((B, cap, 12), np.float32) if trace else None
-        tR = np.zeros((B, cap), SIM3_NORMAL_DTYPE) if trace else None
-        tL = np.zeros((B, cap, 2), np.float32) if trace else None
-        tLR = np.zeros((B, cap), LIGHT_NORMAL_DTYPE) if trace else None
-        self._ck(self._l.ellc_keyframe_sim3_align_lit(self.h, B, _p(src), _p(dst), _p(T), _p(li), int(level_from), int(level_to), C.byref(flt),
-                                                      C.byref(prm), C.byref(lp), int(max_iter), C.c_float(eps), _p(T_out), _p(l_out), _p(out), _p(lrec),
-                                                      _p(iters), _p(tT), _p(tR), _p(tL), _p(tLR), cap if trace else 0),
-                 "ellc_keyframe_sim3_align_lit")
-        res = dict(T=T_out, light=l_out, rec=out, light_rec=lrec, iters=iters)
-        if trace:
-            n = [int((tR[b]["n_kept"] >= 0).sum()) for b in range(B)]
-            res["trace_T"] = [tT[b, :n[b]].copy() for b in range(B)]
-            res["trace_rec"] = [tR[b, :n[b]].copy() for b in range(B)]
-            res["trace_light"] = [tL[b, :n[b]].copy() for b in range(B)]
-            res["trace_light_rec"] = [tLR[b, :n[b]].copy() for b in range(B)]
-        return res
+        return self._align("ellc_keyframe_sim3_align_lit", True, src_slots, dst_slots, Ts, lights, level_from, level_to, max_iter, eps, max_var,
+                           min_support, support_k2, stride, params, light_params, trace)
 
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
@@ -757,25 +742,23 @@ class Context:
     def profile_sim3_step(self, src_slots, dst_slots, Ts, level=0, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None):
         """sim3_step through ellc_profile_sim3_step: (records, launches_ms), the device time of the launches."""
         self._need_diag("ellc_profile_sim3_step")
-        B, src, dst, T, flt, prm = self._sim3_args(src_slots, dst_slots, Ts, max_var, min_support, support_k2, stride, params)
-        out = np.zeros(B, SIM3_NORMAL_DTYPE)
         ms = C.c_float(0)
-        self._ck(self._l.ellc_profile_sim3_step(self.h, B, _p(src), _p(dst), _p(T), int(level), C.byref(flt), C.byref(prm), _p(out), C.byref(ms)),
-                 "ellc_profile_sim3_step")
+        out = self._pair_step("ellc_profile_sim3_step", SIM3_NORMAL_DTYPE, (), src_slots, dst_slots, Ts, level, max_var, min_support, support_k2, stride,
+                              params, tail=(C.byref(ms),))
         return out, ms.value
 
     def profile_light_step(self, src_slots, dst_slots, Ts, lights=None, **kw):
         """light_step through ellc_profile_light_step: (records, launches_ms), the device time of the launches."""
         self._need_diag("ellc_profile_light_step")
         ms = C.c_float(0)
-        out = self.light_step(src_slots, dst_slots, Ts, lights, _fn="ellc_profile_light_step", _tail=(C.byref(ms),), **kw)
+        out = self._pair_step("ellc_profile_light_step", LIGHT_NORMAL_DTYPE, (lights,), src_slots, dst_slots, Ts, tail=(C.byref(ms),), **kw)
         return out, ms.value
 
     def profile_sim3_step_lit(self, src_slots, dst_slots, Ts, lights=None, **kw):
         """sim3_step_lit through ellc_profile_sim3_step_lit: (records, launches_ms), the device time of the launches."""
         self._need_diag("ellc_profile_sim3_step_lit")
         ms = C.c_float(0)
-        out = self.sim3_step_lit(src_slots, dst_slots, Ts, lights, _fn="ellc_profile_sim3_step_lit", _tail=(C.byref(ms),), **kw)
+        out = self._pair_step("ellc_profile_sim3_step_lit", SIM3_NORMAL_DTYPE, (lights,), src_slots, dst_slots, Ts, tail=(C.byref(ms),), **kw)
         return out, ms.value
 
     def profile_calibrate_read(self, nbytes, reps=10):

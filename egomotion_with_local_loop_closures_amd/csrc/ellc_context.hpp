@@ -266,10 +266,9 @@ struct ellc_ctx {
   // ellc_depth_absorb_keyframes: the render's and the fusion's scratch above and, of its own, allocated by the first call:
   void* absorb_block_d = nullptr;           // [64] words for absorb_mark's four counts, then [ceil(W*H / 256)][11] outcome counts per block of absorb_fold
   int32_t *absorb_stats_h = nullptr, *absorb_stats_dev_alias = nullptr;   // pinned: the sixteen words of ellc_absorb_stats (absorb_finish)
-  // ellc_keyframe_depth_consistency, ellc_keyframe_sim3_step / _align, ellc_keyframe_trial_propagate: a PairScratch each, and the trial
-  // call's bitmaps
-  ellc::PairScratch consist, sim3, trial;
-  ellc::PairScratch light, sim3l;           // ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit (both through ellc_keyframe_sim3_align_lit too)
+  // ellc_keyframe_depth_consistency, ellc_keyframe_sim3_step / _step_lit / _align / _align_lit, ellc_keyframe_trial_propagate,
+  // ellc_keyframe_light_step (through ellc_keyframe_sim3_align_lit too): a PairScratch each, and the trial call's bitmaps
+  ellc::PairScratch consist, sim3, trial, light;
   unsigned* trial_bits_d = nullptr;         // [requests of one launch][ceil(W*H / 32)] one bit per target pixel
   size_t trial_bits_cap = 0;                //   words it holds
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each

@@ -1244,7 +1244,6 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   ellc::pair_free(c->sim3);
   ellc::pair_free(c->trial);
   ellc::pair_free(c->light);
-  ellc::pair_free(c->sim3l);
   if (c->trial_bits_d) (void)hipFree(c->trial_bits_d);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
   if (c->ingest_bgr) (void)hipFree(c->ingest_bgr);

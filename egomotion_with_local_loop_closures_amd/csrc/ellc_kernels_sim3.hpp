@@ -3,6 +3,8 @@
 // intent only). consist_pass / consist_finish's shape: two launches, no waiting between blocks and no atomics. sim3_pass leaves one
 // partial record per (request, tile), sim3_finish sums a request's tiles. map_keep (ellc_kernels_map.hpp) decides which source pixels
 // take part, render_candidate (ellc_kernels_render.hpp) where they land and what their point in the destination's camera is.
+// ellc_keyframe_sim3_step_lit is the same pair of kernels: every request carries a light (gain, offset) in the staging, and the plain
+// call stages (1, 0), for which gain * Is + offset is Is exactly.
 #pragma once
 #include <float.h>
 #include "ellc_kernels_render.hpp"
@@ -20,7 +22,7 @@ struct Sim3Rec {
 
 struct Sim3Args {
   MapView v;                 // what map_keep reads
-  const int* stage;          // [cap] source slot of every request, [cap] destination slot, [cap][12] f32 transforms (device copy of the pinned record)
+  const int* stage;          // [cap] source slots, [cap] destination slots, [cap][12] f32 transforms, [cap][2] f32 lights (device copy of the pinned record)
   Sim3Rec* partials;         // [requests of the launch][tiles]
   Sim3Rec* out;              // pinned, through its device-side address: [B] records (sim3_finish)
   int cap;                   // requests the staging holds
@@ -86,6 +88,28 @@ __device__ __forceinline__ float sim3_bilinear(float I00, float I01, float I10, 
   return top + ay * gy;
 }
 
+// Rule 3's tap test and taps for a candidate c of source pixel p: whether (u, v) has four taps in the destination's image, and then
+// Iw, its two gradients and Is, the source's grey value, all f32 - for sim3_pass and light_pass.
+__device__ __forceinline__ bool sim3_photo_taps(const RenderCand& c, const MapPixel& p, const ELLC_GLOBAL uint8_t* img, const ELLC_GLOBAL uint8_t* timg,
+                                                int cols, int rows, int sw, float& Iw, float& gx, float& gy, float& Is) {
+  if (!(c.u >= 0.0f && c.v >= 0.0f)) return false;   // (NaN fails; u < cols and v < rows by render_candidate's bounds test, so the casts are in range)
+  const int x0 = (int)c.u, y0 = (int)c.v;
+  if (!(x0 + 1 < cols && y0 + 1 < rows)) return false;
+  const unsigned t0 = (unsigned)(y0 * sw + x0);
+  const float I00 = (float)timg[t0], I01 = (float)timg[t0 + 1u], I10 = (float)timg[t0 + (unsigned)sw], I11 = (float)timg[t0 + (unsigned)sw + 1u];
+  Is = (float)img[(unsigned)(p.y * sw + p.x)];
+  const float ax = c.u - (float)x0, ay = c.v - (float)y0;
+  Iw = sim3_bilinear(I00, I01, I10, I11, ax, ay, gx, gy);
+  return true;
+}
+
+// The light of request b in a 16-word staging: [cap][2] f32 (gain, offset) behind the 14 words of pair_stage_slots
+__device__ __forceinline__ void load_light(const int* stage, int cap, unsigned b, float& gain, float& offset) {
+  const float* l = (const float*)(stage + 14u * (unsigned)cap) + 2u * b;   // block-uniform: scalar loads
+  gain = l[0];
+  offset = l[1];
+}
+
 // grid (tiles of the level) x (requests of the launch), map_count's pixel layout: thread t of tile `local` owns pixels
 // local * ELLC_TILE + j * 256 + t and adds them in the order j = 0..7; the wave's lanes are summed by the butterfly, the four waves in
 // ascending order. The partition follows from the level's size alone.
@@ -104,6 +128,8 @@ __global__ __launch_bounds__(256) void sim3_pass(Sim3Args a) {
   const int cols = g.cols, rows = g.rows, sw = g.sw;
   const float fx = g.fx, fy = g.fy;
   const RenderT T = load_T12((const float*)(a.stage + 2u * (unsigned)a.cap) + 12u * b);   // block-uniform: scalar loads
+  float gain, offset;
+  load_light(a.stage, a.cap, b, gain, offset);
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
   Sim3Rec r;
   rec_zero(r);
@@ -121,27 +147,20 @@ __global__ __launch_bounds__(256) void sim3_pass(Sim3Args a) {
       r.n[0]++;
       if (render_candidate(g, T, 0u, i, p.x, p.y, p.Z, p.V, c)) {   // (the request number only enters the key, which is not used here)
         r.n[1]++;
-        // the photometric term: the four taps of the destination's image around (u, v), where they exist
-        if (c.u >= 0.0f && c.v >= 0.0f) {   // (NaN fails; u < cols and v < rows by render_candidate's bounds test, so the casts are in range)
-          const int x0 = (int)c.u, y0 = (int)c.v;
-          if (x0 + 1 < cols && y0 + 1 < rows) {
-            r.n[2]++;
-            const unsigned t0 = (unsigned)(y0 * sw + x0);
-            const float I00 = (float)timg[t0], I01 = (float)timg[t0 + 1u], I10 = (float)timg[t0 + (unsigned)sw], I11 = (float)timg[t0 + (unsigned)sw + 1u];
-            const float Is = (float)img[(unsigned)(p.y * sw + p.x)];
-            const float ax = c.u - (float)x0, ay = c.v - (float)y0;
-            float gx, gy;
-            const float Iw = sim3_bilinear(I00, I01, I10, I11, ax, ay, gx, gy);
-            rp = Iw - Is;
-            const float A = (gx * fx) * c.nid, Bv = (gy * fy) * c.nid;
-            const float Cq = -(((A * c.x) + (Bv * c.y)) * c.nid);
-            Jp[0] = Cq * c.y - Bv * c.z; Jp[1] = A * c.z - Cq * c.x; Jp[2] = Bv * c.x - A * c.y; Jp[3] = A; Jp[4] = Bv; Jp[5] = Cq;
-            const float e = fabsf(rp) * a.sp;
-            wp = a.w0;
-            if (!(e <= a.huber_k)) {
-              wp = a.w0 * (a.huber_k / e);
-              r.n[3]++;
-            }
+        // the photometric term, where the destination's image has four taps around (u, v): the residual is taken against the request's
+        // light, gain * Is + offset; the Jacobian is that of Iw
+        float Iw, gx, gy, Is;
+        if (sim3_photo_taps(c, p, img, timg, cols, rows, sw, Iw, gx, gy, Is)) {
+          r.n[2]++;
+          rp = Iw - (gain * Is + offset);
+          const float A = (gx * fx) * c.nid, Bv = (gy * fy) * c.nid;
+          const float Cq = -(((A * c.x) + (Bv * c.y)) * c.nid);
+          Jp[0] = Cq * c.y - Bv * c.z; Jp[1] = A * c.z - Cq * c.x; Jp[2] = Bv * c.x - A * c.y; Jp[3] = A; Jp[4] = Bv; Jp[5] = Cq;
+          const float e = fabsf(rp) * a.sp;
+          wp = a.w0;
+          if (!(e <= a.huber_k)) {
+            wp = a.w0 * (a.huber_k / e);
+            r.n[3]++;
           }
         }
         // the depth term: the target of the destination's map, where it holds a hypothesis

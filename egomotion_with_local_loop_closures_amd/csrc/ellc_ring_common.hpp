@@ -137,9 +137,9 @@ ellc_status pair_reserve(ellc_ctx* c, PairScratch& s, int B, size_t stage_bytes,
 }
 
 // the [cap] source slots, [cap] destination slots, [cap][12] f32 transforms record, staged and on its way to the device
-// (requests beyond B are never read: blockIdx.y < B). extra (may be NULL; then extra_words is 0): a further block of extra_words
-// 4-byte words a request behind the 14, [cap][extra_words], for a call whose requests carry more than slots and a transform; the
-// call has reserved 14 + extra_words words a request.
+// (requests beyond B are never read: blockIdx.y < B). extra_words > 0: a further block of extra_words 4-byte words a request behind
+// the 14, [cap][extra_words], for a call whose requests carry more than slots and a transform; the call has reserved 14 + extra_words
+// words a request. It is copied from `extra`, or with extra NULL the caller has written it into stage_h itself.
 ellc_status pair_stage_slots(ellc_ctx* c, PairScratch& s, int B, const int* src, const int* dst, const float* T12, const void* extra = nullptr,
                              int extra_words = 0) {
   int* h = (int*)s.stage_h;

@@ -1,8 +1,9 @@
-// ellc_keyframe_sim3_step, ellc_keyframe_sim3_align, ellc_sim3_solve, ellc_sim3_apply (include/ellc_abi.h): the host side of the
-// Sim(3) refinement. Included at the end of ellc_hip.hip behind ellc_ring_common.hpp: its refusals, view and pair reduction are used here.
+// ellc_keyframe_sim3_step / _step_lit, ellc_keyframe_sim3_align / _align_lit, ellc_sim3_solve, ellc_sim3_apply (include/ellc_abi.h): the
+// host side of the Sim(3) refinement, without and with the affine brightness - one evaluation and one Gauss-Newton loop behind each
+// pair of entry points. Included at the end of ellc_hip.hip behind ellc_ring_common.hpp: its refusals, view and pair reduction are used here.
 #pragma once
 #include "ellc_ring_common.hpp"
-#include "ellc_kernels_sim3.hpp"
+#include "ellc_kernels_light.hpp"
 #include <vector>
 
 using namespace ellc;
@@ -36,34 +37,74 @@ ellc_status sim3_validate(ellc_ctx* c, const char* who, int B, const int* src, c
   return ring_check_ready(c, who, B, dst);
 }
 
-// One evaluation of B validated requests on `level`, behind ELLC_ENTER; synchronous. launches_ms (the diagnostic hook only): device
-// time of the launches, HIP events around them.
-ellc_status sim3_evaluate(ellc_ctx* c, int B, const int* src, const int* dst, const float* T12, int level, const ellc_map_filter* f,
-                          const ellc_sim3_params* p, ellc_sim3_normal* out, float* launches_ms) {
-  Sim3Args a{};
+// a given light: every value finite (NULL means (1, 0) for every pair)
+ellc_status light_check(ellc_ctx* c, const char* who, int B, const float* light) {
+  if (!light) return ELLC_OK;
+  for (int k = 0; k < 2 * B; k++)
+    if (!std::isfinite(light[k])) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": light not finite");
+  return ELLC_OK;
+}
+
+ellc_status light_check_params(ellc_ctx* c, const char* who, const ellc_light_params* p) {
+  if (!std::isfinite(p->gain_min) || !std::isfinite(p->gain_max) || !(p->gain_min > 0.0f) || !(p->gain_min <= 1.0f) || !(p->gain_max >= 1.0f) ||
+      p->min_pixels < 2 || p->min_pixels > (1 << 30))
+    return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": light parameters out of range");
+  return ELLC_OK;
+}
+
+// What sim3_pass and light_pass are given alike (a: Sim3Args or LightArgs): the view, room for B requests and their partial records,
+// the 16-word staging on its way to the device (light NULL: (1, 0) for every pair) and the photometric weights. Returns the requests
+// of one launch through per_launch.
+template <class Args>
+ellc_status photo_args(ellc_ctx* c, PairScratch& s, int B, const int* src, const int* dst, const float* T12, const float* light, int level,
+                       const ellc_map_filter* f, const ellc_sim3_params* p, Args& a, int& per_launch) {
+  const size_t rec_bytes = sizeof(*a.partials);
   a.v = ring_view(c, level, f);
-  const int per_launch = pair_per_launch(B, SIM3_SCRATCH_BYTES, (size_t)a.v.tiles * sizeof(Sim3Rec));
-  ELLC_TRY(pair_reserve(c, c->sim3, B, 14 * sizeof(int), sizeof(Sim3Rec), (size_t)per_launch * a.v.tiles));
-  ELLC_TRY(pair_stage_slots(c, c->sim3, B, src, dst, T12));
-  a.stage = (const int*)c->sim3.stage_d;
-  a.cap = c->sim3.cap;
+  per_launch = pair_per_launch(B, SIM3_SCRATCH_BYTES, (size_t)a.v.tiles * rec_bytes);
+  ELLC_TRY(pair_reserve(c, s, B, 16 * sizeof(int), rec_bytes, (size_t)per_launch * a.v.tiles));
+  if (!light) {
+    float* unit = (float*)s.stage_h + 14 * (size_t)s.cap;
+    for (int b = 0; b < B; b++) { unit[2 * b] = 1.0f; unit[2 * b + 1] = 0.0f; }
+  }
+  ELLC_TRY(pair_stage_slots(c, s, B, src, dst, T12, light, 2));
+  a.stage = (const int*)s.stage_d;
+  a.cap = s.cap;
   a.w0 = 1.0f / p->sigma_i2;
   a.sp = sqrtf(a.w0);
   a.huber_k = p->huber_k;
+  return ELLC_OK;
+}
+
+// One evaluation of B validated requests on `level`, behind ELLC_ENTER; synchronous. launches_ms (the diagnostic hook only): device
+// time of the launches, HIP events around them.
+ellc_status sim3_evaluate(ellc_ctx* c, int B, const int* src, const int* dst, const float* T12, const float* light /* NULL: (1, 0) for every pair */,
+                          int level, const ellc_map_filter* f, const ellc_sim3_params* p, ellc_sim3_normal* out, float* launches_ms) {
+  Sim3Args a{};
+  int per_launch;
+  ELLC_TRY(photo_args(c, c->sim3, B, src, dst, T12, light, level, f, p, a, per_launch));
   a.gate_k2 = p->gate_k2;
   a.depth_weight = p->depth_weight;
   return pair_run(c, c->sim3, B, per_launch, sim3_pass, sim3_finish, a, out, launches_ms);
 }
 
-ellc_status sim3_step_impl(ellc_ctx* c, int B, const int* src, const int* dst, const float* T12, int level, const ellc_map_filter* f,
-                           const ellc_sim3_params* p, ellc_sim3_normal* out, float* launches_ms) {
+ellc_status light_evaluate(ellc_ctx* c, int B, const int* src, const int* dst, const float* T12, const float* light, int level,
+                           const ellc_map_filter* f, const ellc_sim3_params* p, ellc_light_normal* out, float* launches_ms) {
+  LightArgs a{};
+  int per_launch;
+  ELLC_TRY(photo_args(c, c->light, B, src, dst, T12, light, level, f, p, a, per_launch));
+  return pair_run(c, c->light, B, per_launch, light_pass, light_finish, a, out, launches_ms);
+}
+
+// ellc_keyframe_sim3_step (light is NULL) and ellc_keyframe_sim3_step_lit, each under its own name
+ellc_status sim3_step_impl(ellc_ctx* c, const char* who, int B, const int* src, const int* dst, const float* T12, const float* light, int level,
+                           const ellc_map_filter* f, const ellc_sim3_params* p, ellc_sim3_normal* out, float* launches_ms) {
   if (!c) return ELLC_ERR_BAD_ARG;
   // validated first: a refused call leaves the context as it was and `out` unwritten
-  if (!out) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_sim3_step: null pointer");
-  const ellc_status s = sim3_validate(c, "ellc_keyframe_sim3_step", B, src, dst, T12, level, level, f, p);
-  if (s != ELLC_OK) return s;
+  if (!out) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": null pointer");
+  ELLC_TRY(sim3_validate(c, who, B, src, dst, T12, level, level, f, p));
+  ELLC_TRY(light_check(c, who, B, light));
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
-  return sim3_evaluate(c, B, src, dst, T12, level, f, p, out, launches_ms);
+  return sim3_evaluate(c, B, src, dst, T12, light, level, f, p, out, launches_ms);
 }
 
 // exp of the 4 x 4 generator [[w]x + sigma I, v; 0 0] in double: scaling by a power of two until the largest row sum is <= 1/4, the
@@ -96,6 +137,115 @@ void sim3_exp(const double xi[7], double M[16]) {
       }
     for (int k = 0; k < 16; k++) M[k] = next[k];
   }
+}
+
+// a trace of n entries, every one marked as not written (n_kept = -1)
+template <class Rec>
+void trace_unwritten(std::vector<Rec>& t, size_t n) {
+  Rec unused;
+  std::memset(&unused, 0, sizeof(unused));
+  unused.n_kept = -1;
+  t.assign(n, unused);
+}
+
+// The Gauss-Newton loop of ellc_keyframe_sim3_align and ellc_keyframe_sim3_align_lit, each under its own name. light_params NULL: no
+// light is fitted, every evaluation is sim3_evaluate's alone at (1, 0), and the light's arrays (light_in, light_out, light_rec_out,
+// trace_light, trace_light_rec) are all NULL.
+ellc_status sim3_align_impl(ellc_ctx* c, const char* who, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12_in,
+                            const float* light_in, int level_from, int level_to, const ellc_map_filter* filter, const ellc_sim3_params* params,
+                            const ellc_light_params* light_params, int max_iter, float eps, float* T12_out, float* light_out, ellc_sim3_normal* out,
+                            ellc_light_normal* light_rec_out, int* iters_out, float* trace_T12, ellc_sim3_normal* trace_rec, float* trace_light,
+                            ellc_light_normal* trace_light_rec, int trace_capacity) {
+  const bool lit = light_params != nullptr;
+  if (!T12_out || !out || (lit && !light_out)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": null pointer");
+  if (level_from < level_to) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": level_from below level_to");
+  if (max_iter < 1 || max_iter > 64) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": max_iter out of range");
+  if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": eps negative or not finite");
+  ELLC_TRY(sim3_validate(c, who, B, src_kf_slots, dst_kf_slots, T12_in, level_to, level_from, filter, params));
+  if (lit) {
+    ELLC_TRY(light_check(c, who, B, light_in));
+    ELLC_TRY(light_check_params(c, who, light_params));
+  }
+  const int n_levels = level_from - level_to + 1;
+  const bool traced = trace_T12 || trace_rec || trace_light || trace_light_rec;
+  if (traced && trace_capacity < n_levels * max_iter + 1) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": trace_capacity too small");
+  ELLC_ENTER(c);
+  // everything of the call is kept here until it has succeeded: a failure half-way leaves the caller's arrays as they were
+  std::vector<float> T(T12_in, T12_in + (size_t)B * 12), l, tT, tL;
+  std::vector<int> iters((size_t)B * n_levels, 0), n_trace((size_t)B, 0);
+  std::vector<ellc_sim3_normal> tR, rec((size_t)B);
+  std::vector<ellc_light_normal> tLR, lrec(lit ? (size_t)B : 0);
+  if (lit) {
+    l.resize((size_t)B * 2);
+    for (int b = 0; b < B; b++) { l[2 * (size_t)b] = light_in ? light_in[2 * b] : 1.0f; l[2 * (size_t)b + 1] = light_in ? light_in[2 * b + 1] : 0.0f; }
+  }
+  if (trace_T12) tT.assign((size_t)B * trace_capacity * 12, 0.0f);
+  if (trace_light) tL.assign((size_t)B * trace_capacity * 2, 0.0f);
+  if (trace_rec) trace_unwritten(tR, (size_t)B * trace_capacity);
+  if (trace_light_rec) trace_unwritten(tLR, (size_t)B * trace_capacity);
+  std::vector<int> active, as, ad;
+  std::vector<float> aT, aL;
+  // one evaluation of the pairs in `active`: with a light the light records and the lights solved from them; the Sim(3) records at
+  // those lights into rec[0..active.size()); and the traces
+  auto evaluate = [&](int level) -> ellc_status {
+    const int n = (int)active.size();
+    as.resize(n); ad.resize(n); aT.resize((size_t)n * 12); aL.resize(lit ? (size_t)n * 2 : 0);
+    for (int k = 0; k < n; k++) {
+      as[k] = src_kf_slots[active[k]]; ad[k] = dst_kf_slots[active[k]];
+      std::memcpy(&aT[(size_t)k * 12], &T[(size_t)active[k] * 12], 12 * sizeof(float));
+      if (lit) std::memcpy(&aL[(size_t)k * 2], &l[(size_t)active[k] * 2], 2 * sizeof(float));
+    }
+    if (lit) {
+      ELLC_TRY(light_evaluate(c, n, as.data(), ad.data(), aT.data(), aL.data(), level, filter, params, lrec.data(), nullptr));
+      for (int k = 0; k < n; k++) (void)ellc_light_solve(&lrec[k], light_params, &aL[(size_t)k * 2], &aL[(size_t)k * 2]);
+    }
+    ELLC_TRY(sim3_evaluate(c, n, as.data(), ad.data(), aT.data(), lit ? aL.data() : nullptr, level, filter, params, rec.data(), nullptr));
+    for (int k = 0; k < n; k++) {
+      const int b = active[k];
+      if (lit) std::memcpy(&l[(size_t)b * 2], &aL[(size_t)k * 2], 2 * sizeof(float));
+      const size_t e = (size_t)b * trace_capacity + n_trace[b];
+      if (trace_T12) std::memcpy(&tT[e * 12], &aT[(size_t)k * 12], 12 * sizeof(float));
+      if (trace_light) std::memcpy(&tL[e * 2], &aL[(size_t)k * 2], 2 * sizeof(float));
+      if (trace_rec) tR[e] = rec[k];
+      if (trace_light_rec) tLR[e] = lrec[k];
+      n_trace[b]++;
+    }
+    return ELLC_OK;
+  };
+  for (int li = 0; li < n_levels; li++) {
+    const int level = level_from - li;
+    active.resize(B);
+    for (int b = 0; b < B; b++) active[b] = b;
+    while (!active.empty()) {
+      ELLC_TRY(evaluate(level));
+      std::vector<int> still;
+      for (size_t k = 0; k < active.size(); k++) {
+        const int b = active[k];
+        double xi[7];
+        if (ellc_sim3_solve(&rec[k], xi)) continue;   // singular: no update, the pair leaves the level
+        ellc_sim3_apply(xi, &T[(size_t)b * 12], &T[(size_t)b * 12]);
+        const int made = ++iters[(size_t)b * n_levels + li];
+        double m = 0.0;
+        for (int i = 0; i < 7; i++) m = std::max(m, std::fabs(xi[i]));
+        if (m <= (double)eps || made >= max_iter) continue;
+        still.push_back(b);
+      }
+      active.swap(still);
+    }
+  }
+  active.resize(B);
+  for (int b = 0; b < B; b++) active[b] = b;
+  ELLC_TRY(evaluate(level_to));
+  std::memcpy(out, rec.data(), (size_t)B * sizeof(ellc_sim3_normal));
+  std::memcpy(T12_out, T.data(), (size_t)B * 12 * sizeof(float));
+  if (lit) std::memcpy(light_out, l.data(), (size_t)B * 2 * sizeof(float));
+  if (light_rec_out) std::memcpy(light_rec_out, lrec.data(), (size_t)B * sizeof(ellc_light_normal));
+  if (iters_out) std::memcpy(iters_out, iters.data(), iters.size() * sizeof(int));
+  if (trace_T12) std::memcpy(trace_T12, tT.data(), tT.size() * sizeof(float));
+  if (trace_rec) std::memcpy(trace_rec, tR.data(), tR.size() * sizeof(ellc_sim3_normal));
+  if (trace_light) std::memcpy(trace_light, tL.data(), tL.size() * sizeof(float));
+  if (trace_light_rec) std::memcpy(trace_light_rec, tLR.data(), tLR.size() * sizeof(ellc_light_normal));
+  return ELLC_OK;
 }
 
 }  // namespace
@@ -158,7 +308,12 @@ void ellc_sim3_apply(const double* xi7, const float* T12_in, float* T12_out) {
 
 ellc_status ellc_keyframe_sim3_step(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,
                                     const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out) {
-  return sim3_step_impl(c, B, src_kf_slots, dst_kf_slots, T12, level, filter, params, out, nullptr);
+  return sim3_step_impl(c, "ellc_keyframe_sim3_step", B, src_kf_slots, dst_kf_slots, T12, nullptr, level, filter, params, out, nullptr);
+}
+
+ellc_status ellc_keyframe_sim3_step_lit(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, const float* light,
+                                        int level, const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out) {
+  return sim3_step_impl(c, "ellc_keyframe_sim3_step_lit", B, src_kf_slots, dst_kf_slots, T12, light, level, filter, params, out, nullptr);
 }
 
 ellc_status ellc_keyframe_sim3_align(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12_in, int level_from,
@@ -166,89 +321,37 @@ ellc_status ellc_keyframe_sim3_align(ellc_ctx* c, int B, const int* src_kf_slots
                                      float* T12_out, ellc_sim3_normal* out, int* iters_out, float* trace_T12, ellc_sim3_normal* trace_rec,
                                      int trace_capacity) {
   if (!c) return ELLC_ERR_BAD_ARG;
-  const char* who = "ellc_keyframe_sim3_align";
-  if (!T12_out || !out) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": null pointer");
-  if (level_from < level_to) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": level_from below level_to");
-  if (max_iter < 1 || max_iter > 64) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": max_iter out of range");
-  if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": eps negative or not finite");
-  const ellc_status s = sim3_validate(c, who, B, src_kf_slots, dst_kf_slots, T12_in, level_to, level_from, filter, params);
-  if (s != ELLC_OK) return s;
-  const int n_levels = level_from - level_to + 1;
-  if ((trace_T12 || trace_rec) && trace_capacity < n_levels * max_iter + 1) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": trace_capacity too small");
-  ELLC_ENTER(c);
-  // everything of the call is kept here until it has succeeded: a failure half-way leaves the caller's arrays as they were
-  std::vector<float> T(T12_in, T12_in + (size_t)B * 12), tT;
-  std::vector<int> iters((size_t)B * n_levels, 0), n_trace((size_t)B, 0);
-  std::vector<ellc_sim3_normal> tR, rec((size_t)B);
-  if (trace_T12) tT.assign((size_t)B * trace_capacity * 12, 0.0f);
-  if (trace_rec) {
-    ellc_sim3_normal unused;
-    std::memset(&unused, 0, sizeof(unused));
-    unused.n_kept = -1;
-    tR.assign((size_t)B * trace_capacity, unused);
-  }
-  std::vector<int> active, as, ad;
-  std::vector<float> aT;
-  // one launch sequence over the pairs in `active`, its records into rec[0..active.size()) and the traces
-  auto evaluate = [&](int level) -> ellc_status {
-    const int n = (int)active.size();
-    as.resize(n); ad.resize(n); aT.resize((size_t)n * 12);
-    for (int k = 0; k < n; k++) {
-      as[k] = src_kf_slots[active[k]]; ad[k] = dst_kf_slots[active[k]];
-      std::memcpy(&aT[(size_t)k * 12], &T[(size_t)active[k] * 12], 12 * sizeof(float));
-    }
-    const ellc_status st = sim3_evaluate(c, n, as.data(), ad.data(), aT.data(), level, filter, params, rec.data(), nullptr);
-    if (st != ELLC_OK) return st;
-    for (int k = 0; k < n; k++) {
-      const int b = active[k];
-      const size_t e = (size_t)b * trace_capacity + n_trace[b];
-      if (trace_T12) std::memcpy(&tT[e * 12], &aT[(size_t)k * 12], 12 * sizeof(float));
-      if (trace_rec) tR[e] = rec[k];
-      n_trace[b]++;
-    }
-    return ELLC_OK;
-  };
-  for (int li = 0; li < n_levels; li++) {
-    const int level = level_from - li;
-    active.resize(B);
-    for (int b = 0; b < B; b++) active[b] = b;
-    while (!active.empty()) {
-      const ellc_status st = evaluate(level);
-      if (st != ELLC_OK) return st;
-      std::vector<int> still;
-      for (size_t k = 0; k < active.size(); k++) {
-        const int b = active[k];
-        double xi[7];
-        if (ellc_sim3_solve(&rec[k], xi)) continue;   // singular: no update, the pair leaves the level
-        ellc_sim3_apply(xi, &T[(size_t)b * 12], &T[(size_t)b * 12]);
-        const int made = ++iters[(size_t)b * n_levels + li];
-        double m = 0.0;
-        for (int i = 0; i < 7; i++) m = std::max(m, std::fabs(xi[i]));
-        if (m <= (double)eps || made >= max_iter) continue;
-        still.push_back(b);
-      }
-      active.swap(still);
-    }
-  }
-  active.resize(B);
-  for (int b = 0; b < B; b++) active[b] = b;
-  {
-    const ellc_status st = evaluate(level_to);
-    if (st != ELLC_OK) return st;
-  }
-  std::memcpy(out, rec.data(), (size_t)B * sizeof(ellc_sim3_normal));
-  std::memcpy(T12_out, T.data(), (size_t)B * 12 * sizeof(float));
-  if (iters_out) std::memcpy(iters_out, iters.data(), iters.size() * sizeof(int));
-  if (trace_T12) std::memcpy(trace_T12, tT.data(), tT.size() * sizeof(float));
-  if (trace_rec) std::memcpy(trace_rec, tR.data(), tR.size() * sizeof(ellc_sim3_normal));
-  return ELLC_OK;
+  return sim3_align_impl(c, "ellc_keyframe_sim3_align", B, src_kf_slots, dst_kf_slots, T12_in, nullptr, level_from, level_to, filter, params, nullptr,
+                         max_iter, eps, T12_out, nullptr, out, nullptr, iters_out, trace_T12, trace_rec, nullptr, nullptr, trace_capacity);
+}
+
+ellc_status ellc_keyframe_sim3_align_lit(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12_in, const float* light_in,
+                                         int level_from, int level_to, const ellc_map_filter* filter, const ellc_sim3_params* params,
+                                         const ellc_light_params* light_params, int max_iter, float eps, float* T12_out, float* light_out,
+                                         ellc_sim3_normal* out, ellc_light_normal* light_rec_out, int* iters_out, float* trace_T12,
+                                         ellc_sim3_normal* trace_rec, float* trace_light, ellc_light_normal* trace_light_rec, int trace_capacity) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  if (!light_params) return fail(c, ELLC_ERR_BAD_ARG, "ellc_keyframe_sim3_align_lit: null pointer");   // (to the loop, NULL says "no light")
+  return sim3_align_impl(c, "ellc_keyframe_sim3_align_lit", B, src_kf_slots, dst_kf_slots, T12_in, light_in, level_from, level_to, filter, params,
+                         light_params, max_iter, eps, T12_out, light_out, out, light_rec_out, iters_out, trace_T12, trace_rec, trace_light,
+                         trace_light_rec, trace_capacity);
 }
 
 #ifdef ELLC_DIAG_ABI
 ellc_status ellc_profile_sim3_step(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, int level,
                                    const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out, float* launches_ms) {
-  return ring_profiled(launches_ms, [&](float* ms) { return sim3_step_impl(c, B, src_kf_slots, dst_kf_slots, T12, level, filter, params, out, ms); });
+  return ring_profiled(launches_ms, [&](float* ms) {
+    return sim3_step_impl(c, "ellc_keyframe_sim3_step", B, src_kf_slots, dst_kf_slots, T12, nullptr, level, filter, params, out, ms);
+  });
+}
+
+ellc_status ellc_profile_sim3_step_lit(ellc_ctx* c, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12, const float* light,
+                                       int level, const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out, float* launches_ms) {
+  return ring_profiled(launches_ms, [&](float* ms) {
+    return sim3_step_impl(c, "ellc_keyframe_sim3_step_lit", B, src_kf_slots, dst_kf_slots, T12, light, level, filter, params, out, ms);
+  });
 }
 #endif   // ELLC_DIAG_ABI
 
 }  // extern "C"
+

@@ -71,7 +71,7 @@ ellc_status ellc_profile_sim3_step(ellc_ctx* ctx, int B, const int* src_kf_slots
                                    const ellc_map_filter* filter, const ellc_sim3_params* params, ellc_sim3_normal* out, float* launches_ms);
 
 /* ellc_keyframe_light_step / ellc_keyframe_sim3_step_lit with HIP events around their launches (light_pass, light_finish;
- * sim3l_pass, sim3l_finish): launches_ms receives their device time, without the staging copy in front. Everything else as the
+ * sim3_pass, sim3_finish): launches_ms receives their device time, without the staging copy in front. Everything else as the
  * product calls. */
 ellc_status ellc_profile_light_step(ellc_ctx* ctx, int B, const int* src_kf_slots, const int* dst_kf_slots, const float* T12,
                                     const float* light_in, int level, const ellc_map_filter* filter, const ellc_sim3_params* params,

@@ -99,6 +99,8 @@ def test_steps_against_the_reference(world, flt, light):
 
 
 def test_unit_light_gives_the_bytes_of_sim3_step(world):
+    """(Both calls run sim3_pass since the plain and the lit kernel were merged, so the first two comparisons hold a path to itself;
+    tests/test_gpu_sim3_bytes.py holds both to the bytes of the library that still had two kernels.)"""
     ctx = world["ctx"]
     src, dst, Ts = G.batch_args(world)
     n = len(BATCH)
@@ -365,7 +367,8 @@ def test_the_loop_link_by_link(world, ellc):
 
 def test_a_frozen_light_is_sim3_align(world):
     """min_pixels = 2^30 refuses every fit: with light_in NULL the T's, records, iteration counts and traces are ellc_keyframe_sim3_align's
-    bit for bit, and the light stays (1, 0)."""
+    bit for bit, and the light stays (1, 0). (One loop serves both calls now: this holds that the light's branch of it changes nothing
+    when every fit is refused; tests/test_gpu_sim3_bytes.py holds both calls to the bytes of the library that still had two loops.)"""
     ctx, L = world["ctx"], world["L"]
     batch = BATCH + [(0, G.ZERO_SLOT, 1)]
     src, dst, Ts = G.batch_args(world, batch)
