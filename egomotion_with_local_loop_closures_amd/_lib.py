@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "ellc_depth_absorb_keyframes", "ellc_absorb_default_params", "ellc_keyframe_trial_propagate", "ellc_depth_restart_from_keyframes",
     "ellc_keyframe_depth_consistency", "ellc_keyframe_sim3_step", "ellc_keyframe_sim3_align", "ellc_sim3_default_params", "ellc_sim3_solve", "ellc_sim3_apply",
     "ellc_keyframe_light_step", "ellc_keyframe_sim3_step_lit", "ellc_keyframe_sim3_align_lit", "ellc_light_default_params", "ellc_light_solve",
+    "ellc_keyframe_refine_depth", "ellc_refine_default_params", "ellc_sim3_invert",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
     "ellc_gather_start", "ellc_gather_finish", "ellc_gather_results",
@@ -37,7 +38,7 @@ DIAG_SYMBOLS = [
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
     "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
     "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_fuse_depth", "ellc_profile_depth_absorb", "ellc_profile_trial_propagate", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
-    "ellc_profile_light_step", "ellc_profile_sim3_step_lit",
+    "ellc_profile_light_step", "ellc_profile_sim3_step_lit", "ellc_profile_refine_depth",
 ]
 
 
@@ -102,6 +103,22 @@ class EllcLightNormal(C.Structure):
 class EllcLightParams(C.Structure):
     """ellc_light_params: what ellc_light_solve accepts (12 bytes)."""
     _fields_ = [("gain_min", C.c_float), ("gain_max", C.c_float), ("min_pixels", C.c_int32)]
+
+
+class EllcRefineParams(C.Structure):
+    """ellc_refine_params: the weights, the step bound and the limits of ellc_keyframe_refine_depth (24 bytes)."""
+    _fields_ = [("sigma_i2", C.c_float), ("huber_k", C.c_float), ("prior_weight", C.c_float), ("max_step_rel", C.c_float),
+                ("n_iter", C.c_int), ("min_views", C.c_int)]
+
+
+REFINE_STATUS = ("NOT_TAKING_PART", "REFINED", "TOO_FEW_VIEWS", "NO_INFORMATION", "BAD_STEP", "VIEWS_CHANGED", "COST_ROSE")
+
+
+class EllcRefineStats(C.Structure):
+    """ellc_refine_stats: what ellc_keyframe_refine_depth counts (64 bytes)."""
+    _fields_ = [("n_kept", C.c_int32), ("n_taking_part", C.c_int32), ("n_refined", C.c_int32), ("n_too_few_views", C.c_int32),
+                ("n_no_information", C.c_int32), ("n_bad_step", C.c_int32), ("n_views_changed", C.c_int32), ("n_cost_rose", C.c_int32),
+                ("sum_views", C.c_int64), ("sum_cost_before", C.c_double), ("sum_cost_after", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
 class EllcAbsorbParams(C.Structure):
@@ -189,6 +206,9 @@ def _bind(path, symbols, what):
         h.ellc_sim3_default_params.restype = None
     if hasattr(h, "ellc_light_default_params"):
         h.ellc_light_default_params.restype = None
+    if hasattr(h, "ellc_refine_default_params"):
+        h.ellc_refine_default_params.restype = None
+        h.ellc_sim3_invert.restype = None
     if hasattr(h, "ellc_absorb_default_params"):
         h.ellc_absorb_default_params.restype = None
     for name in symbols:

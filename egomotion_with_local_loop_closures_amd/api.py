@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -572,6 +572,35 @@ class Context:
         return self._align("ellc_keyframe_sim3_align_lit", True, src_slots, dst_slots, Ts, lights, level_from, level_to, max_iter, eps, max_var,
                            min_support, support_k2, stride, params, light_params, trace)
 
+    # ---- a keyframe's map refined against other views
+    def _refine(self, name, tail, kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support, support_k2, stride, params):
+        vs = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
+        B = vs.size
+        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
+        li = self._lights(lights, B)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        prm = params if isinstance(params, EllcRefineParams) else refine_default_params(**(params or {}))
+        rows, cols = self.level_shape(level)
+        res = dict(depth=np.zeros((rows, cols), np.float32), var=np.zeros((rows, cols), np.float32), views=np.zeros((rows, cols), np.uint8),
+                   status=np.zeros((rows, cols), np.uint8))
+        st = EllcRefineStats()
+        self._ck(getattr(self._l, name)(self.h, int(kf_slot), int(level), B, int(views_are_keyframes), _p(vs), _p(T), _p(li), C.byref(flt), C.byref(prm),
+                                        int(dst_slot), _p(res["depth"]), _p(res["var"]), _p(res["views"]), _p(res["status"]), C.byref(st), *tail), name)
+        res["stats"] = {f[0]: (list(getattr(st, f[0])) if f[0] == "reserved" else getattr(st, f[0])) for f in EllcRefineStats._fields_}
+        return res
+
+    def refine_depth(self, kf_slot, view_slots, Ts, lights=None, level=0, views_are_keyframes=True, dst_slot=-1, max_var=0.0, min_support=0,
+                     support_k2=1.0, stride=1, params=None):
+        """The per-pixel photometric Gauss-Newton on the inverse depths of keyframe slot kf_slot against the images of the views
+        (ellc_keyframe_refine_depth): view b is slot view_slots[b] (keyframe slots, or frame slots with views_are_keyframes=False), Ts[b]
+        the row-major 3x4 transform from the keyframe's camera into the view's, lights[b] its (gain, offset) with the keyframe as the
+        source (None: (1, 0)). params: an ellc_refine_params (refine_default_params()) or a dict of sigma_i2, huber_k, prior_weight,
+        max_step_rel, n_iter, min_views (defaults 16, 1.345, 1, 0.5, 3, 2). dst_slot >= 0 (level 0 only) stores the planes into that
+        keyframe slot as keyframe_set_depth would. Returns dict(depth, var (f32), views, status (u8; REFINE_STATUS names the values),
+        stats = the fields of ellc_refine_stats). The order of the views enters the result."""
+        return self._refine("ellc_keyframe_refine_depth", (), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support,
+                            support_k2, stride, params)
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -761,6 +790,15 @@ class Context:
         out = self._pair_step("ellc_profile_sim3_step_lit", SIM3_NORMAL_DTYPE, (lights,), src_slots, dst_slots, Ts, tail=(C.byref(ms),), **kw)
         return out, ms.value
 
+    def profile_refine_depth(self, kf_slot, view_slots, Ts, lights=None, level=0, views_are_keyframes=True, dst_slot=-1, max_var=0.0, min_support=0,
+                             support_k2=1.0, stride=1, params=None):
+        """refine_depth through ellc_profile_refine_depth: (result, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_refine_depth")
+        ms = C.c_float(0)
+        out = self._refine("ellc_profile_refine_depth", (C.byref(ms),), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var,
+                           min_support, support_k2, stride, params)
+        return out, ms.value
+
     def profile_calibrate_read(self, nbytes, reps=10):
         self._need_diag("ellc_profile_calibrate_read")
         ms = C.c_float(0)
@@ -846,6 +884,27 @@ def light_params(gain_min=None, gain_max=None, min_pixels=None):
         if v is not None:
             setattr(p, k, v)
     return p
+
+
+def refine_default_params(sigma_i2=None, huber_k=None, prior_weight=None, max_step_rel=None, n_iter=None, min_views=None):
+    """ellc_refine_params: the library's defaults (ellc_refine_default_params) with the given fields replaced."""
+    p = EllcRefineParams()
+    _lib.lib().ellc_refine_default_params(C.byref(p))
+    for k, v in (("sigma_i2", sigma_i2), ("huber_k", huber_k), ("prior_weight", prior_weight), ("max_step_rel", max_step_rel), ("n_iter", n_iter),
+                 ("min_views", min_views)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def sim3_invert(T12, light=None):
+    """ellc_sim3_invert: (the inverse of a row-major 3x4 similarity as 12 f32, the inverse light (1 / gain, -offset / gain) as 2 f32);
+    light None means (1, 0)."""
+    T = np.ascontiguousarray(T12, np.float32).reshape(12)
+    li = None if light is None else np.ascontiguousarray(light, np.float32).reshape(2)
+    To, lo = np.zeros(12, np.float32), np.zeros(2, np.float32)
+    _lib.lib().ellc_sim3_invert(_p(T), _p(li), _p(To), _p(lo))
+    return To, lo
 
 
 def _as_light_params(p):

@@ -271,6 +271,10 @@ struct ellc_ctx {
   ellc::PairScratch consist, sim3, trial, light;
   unsigned* trial_bits_d = nullptr;         // [requests of one launch][ceil(W*H / 32)] one bit per target pixel
   size_t trial_bits_cap = 0;                //   words it holds
+  // ellc_keyframe_refine_depth: a PairScratch (the views' staging, one record, the blocks' partial records) and the four planes it returns
+  ellc::PairScratch refine;
+  void* refine_planes_d = nullptr;          // [n] f32 depth, [n] f32 variance, [n] u8 views, [n] u8 status of the largest level asked for
+  size_t refine_planes_cap = 0;             //   pixels it holds
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

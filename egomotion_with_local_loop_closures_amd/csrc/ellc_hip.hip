@@ -1244,6 +1244,8 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   ellc::pair_free(c->sim3);
   ellc::pair_free(c->trial);
   ellc::pair_free(c->light);
+  ellc::pair_free(c->refine);
+  if (c->refine_planes_d) (void)hipFree(c->refine_planes_d);
   if (c->trial_bits_d) (void)hipFree(c->trial_bits_d);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
   if (c->ingest_bgr) (void)hipFree(c->ingest_bgr);
@@ -2739,3 +2741,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 #include "ellc_absorb_impl.hpp"
 #include "ellc_trial_impl.hpp"
 #include "ellc_light_impl.hpp"
+#include "ellc_refine_impl.hpp"

@@ -35,6 +35,12 @@
 // --match-light      (LC mode, with --match-sim3 only: a usage error otherwise) the refinement fits an affine brightness between the
 //                    pair before every step (ellc_keyframe_sim3_align_lit; globalOptimize::matchAffineLight) and every line of the
 //                    --match-sim3 file ends in " gain offset"; without the flag every output file is as before
+// --refine-matches PATH  (LC mode, with --match-sim3 only: a usage error otherwise) behind the Sim(3) refinement the pushed keyframe's
+//                    ring map is refined against the images of its candidates at the inverted refined transforms and lights
+//                    (ellc_keyframe_refine_depth, level 0, into the keyframe's own ring slot; globalOptimize::refineMatchDepth); PATH gets
+//                    one line per push that had candidates: "frameId views n_kept n_taking_part n_refined n_too_few_views
+//                    n_no_information n_bad_step n_views_changed n_cost_rose sum_views sum_cost_before sum_cost_after". Without the
+//                    flag every output file is as before
 // --map FILE         (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
 //                    level 0, no variance test, at least 3 supporting neighbours, support_k2 1, every pixel), written as binary PLY
 //                    (x y z float, intensity uchar, var float); every other file is unchanged
@@ -75,7 +81,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--refine-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -85,7 +91,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false, match_light = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, match_geometry, match_sim3, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
+  std::string comm_id_file, match_quality, match_geometry, match_sim3, refine_matches, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -105,6 +111,7 @@ int main(int argc, char** argv) {
     else if (a == "--match-geometry" && i + 1 < argc) match_geometry = argv[++i];
     else if (a == "--match-sim3" && i + 1 < argc) match_sim3 = argv[++i];
     else if (a == "--match-light") match_light = true;
+    else if (a == "--refine-matches" && i + 1 < argc) refine_matches = argv[++i];
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (a == "--fuse" && i + 1 < argc) fuse_file = argv[++i];
@@ -116,6 +123,10 @@ int main(int argc, char** argv) {
   }
   if (match_light && match_sim3.empty()) {
     std::fprintf(stderr, "--match-light needs --match-sim3 PATH: the light is fitted inside the Sim(3) refinement and reported in its file\n");
+    return -1;
+  }
+  if (!refine_matches.empty() && match_sim3.empty()) {
+    std::fprintf(stderr, "--refine-matches needs --match-sim3 PATH: the map is refined at the transforms the Sim(3) refinement returns\n");
     return -1;
   }
   if (!match_quality.empty() && world > 1) {
@@ -194,6 +205,11 @@ int main(int argc, char** argv) {
       if (!globalOptimizeLoop->match_sim3_file) { std::fprintf(stderr, "cannot open %s\n", match_sim3.c_str()); return -1; }
       globalOptimizeLoop->refineMatchSim3 = true;
       globalOptimizeLoop->matchAffineLight = match_light;
+    }
+    if (lc && !refine_matches.empty()) {
+      globalOptimizeLoop->refine_matches_file.open(refine_matches.c_str());
+      if (!globalOptimizeLoop->refine_matches_file) { std::fprintf(stderr, "cannot open %s\n", refine_matches.c_str()); return -1; }
+      globalOptimizeLoop->refineMatchDepth = true;
     }
     if (lc && !absorb_matches.empty()) {
       globalOptimizeLoop->absorb_file.open(absorb_matches.c_str());

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 19   /* ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 20   /* ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -763,6 +763,91 @@ ellc_status ellc_keyframe_sim3_align_lit(ellc_ctx* ctx, int B, const int* src_kf
                                          float* T12_out, float* light_out, ellc_sim3_normal* out, ellc_light_normal* light_rec_out,
                                          int* iters_out, float* trace_T12, ellc_sim3_normal* trace_rec, float* trace_light,
                                          ellc_light_normal* trace_light_rec, int trace_capacity);
+
+/* ---- a keyframe's map refined against other views (v20) -------------------------------------------------------------
+ * The structure step beside the motion step above: a per-pixel photometric Gauss-Newton on the INVERSE DEPTH of keyframe slot
+ * kf_slot (K) against the images of B other views at known transforms and lights. K's depth Z0, variance V0 and image are read on
+ * `level`. View b is slot view_slots[b], a keyframe slot if views_are_keyframes == 1 and a frame slot if 0 (as in
+ * ellc_keyframe_trial_propagate); only its image on `level` is read, so a view needs no depth. Slots may repeat and K may be among
+ * the views. T = T12 + 12 * b is a row-major 3x4 f32 that takes K's camera coordinates into view b's, the scale folded into the 3x3
+ * block; light + 2 * b is (gain, offset) in v19's sense with K as the source, Ip = gain * Is + offset (two roundings), NULL meaning
+ * (1, 0): exactly what ellc_keyframe_sim3_align_lit(src = K, dst = view) returned. Per pixel of K, all arithmetic IEEE f32 in this
+ * order, no contraction, correctly rounded divisions:
+ *   1. TAKING PART. Iff ellc_keyframe_map_points would KEEP the pixel under `filter` (n_kept) and prior_weight == 0 || V0 > 0
+ *      (n_taking_part). d0 = 1 / Z0;  hp = prior_weight / V0, hp = 0 when prior_weight == 0.
+ *   2. EVALUATION at an inverse depth d, Z = 1 / d: H = g = E = 0, n = 0, then the views in ascending b. The candidate (P' = (x', y',
+ *      z'), nid, u, v) is ellc_keyframe_render_depth's for (px, py, Z, V0) at view b's T, with the same drops. The photometric pixel
+ *      is rule 3 of ellc_keyframe_sim3_step word for word (the four-tap condition, Iw, gx, gy, A, Bv, Cq, rp = Iw - Ip, e and wp with
+ *      the host-rounded w0 and sp). A view without a candidate or without four taps contributes nothing. Otherwise
+ *        qx = x' - T[3];  qy = y' - T[7];  qz = z' - T[11];  J = -(Z * (((A * qx) + (Bv * qy)) + (Cq * qz)));
+ *      (the exact derivative of Iw by d, since dP'/dd = -Z (P' - t));
+ *        wJ = wp * J;  H = H + wJ * J;  g = g + wJ * rp;  E = E + (rp * rp) * wp;  n += 1.
+ *   3. LOOP. d = d0; for it = 0 .. n_iter - 1: evaluate at d (the first evaluation's E and n are E0 and n0); stop with TOO_FEW_VIEWS
+ *      if n < min_views;  Ht = H + hp;  gt = g + hp * (d - d0);  stop with NO_INFORMATION unless Ht > 0 && Ht <= FLT_MAX;
+ *      step = gt / Ht;  dn = d - step;  stop with BAD_STEP unless dn > 0 && dn <= FLT_MAX && fabsf(step) <= max_step_rel * d (NaN
+ *      fails);  d = dn.
+ *   4. ACCEPTANCE. One more evaluation at the final d gives (H1, E1, n1): VIEWS_CHANGED unless n1 == n0; NO_INFORMATION unless
+ *      Ht1 = H1 + hp is in (0, FLT_MAX];  c1 = E1 + (hp * (d - d0)) * (d - d0), COST_ROSE unless c1 <= E0; otherwise REFINED.
+ *   5. OUTPUTS (host pointers, dense cols x rows of the level, each may be NULL). REFINED pixels get depth = 1 / d, var = 1 / Ht1,
+ *      views = n1. Every other pixel keeps K's own depth and variance BITS (pixels not taking part and K's inf / NaN / negative
+ *      pixels included); its `views` is n of the last evaluation made, 0 where none was made. `status` is an ellc_refine_status.
+ *   6. STATS. The integers are exact. sum_cost_before / sum_cost_after add (double)E0 / (double)c1 over the refined pixels: the
+ *      pixels are partitioned by the level's size (256-pixel blocks), partial sums are combined in a fixed order in double.
+ *   7. dst_kf_slot is -1 or a keyframe slot, at level 0 only, exactly as in ellc_keyframe_fuse_depth: afterwards the slot is what
+ *      ellc_keyframe_set_depth(dst_kf_slot, depth, var) with the returned planes would leave. It may be K itself (the main use) or
+ *      a view: every kernel has read its inputs before the copy, in stream order.
+ *   The result is a function of the intrinsics, the level, K's three planes, the views' images, the T's, the lights, the filter and
+ *   the params ALONE; cfg.arith, cfg.grid_batch and whatever else is in flight do not enter it. THE ORDER OF THE VIEWS DOES: H, g and
+ *   E are f32 sums in ascending b. A view from which no pixel gets four taps changes no byte.
+ *   Synchronous, ordered like every other non-batch entry point. A refused call changes nothing and writes nothing.
+ * ELLC_ERR_BAD_ARG: B outside 1..ELLC_REFINE_MAX_VIEWS, a slot or the level out of range, more than 2^24 pixels on the level; a NULL
+ * view_slots, T12, filter or params; the filter errors of ellc_keyframe_map_points; a value of T, light or params that is not
+ * finite; sigma_i2 <= 0, huber_k <= 0, prior_weight < 0, max_step_rel <= 0; n_iter outside 1..8, min_views outside 1..B,
+ * views_are_keyframes outside 0..1; the destination errors of the fusion.
+ * ELLC_ERR_NOT_READY: K without image or depth, a view without image. */
+#define ELLC_REFINE_MAX_VIEWS 64
+
+typedef enum {
+  ELLC_REFINE_NOT_TAKING_PART = 0,
+  ELLC_REFINE_REFINED = 1,
+  ELLC_REFINE_TOO_FEW_VIEWS = 2,
+  ELLC_REFINE_NO_INFORMATION = 3,
+  ELLC_REFINE_BAD_STEP = 4,
+  ELLC_REFINE_VIEWS_CHANGED = 5,
+  ELLC_REFINE_COST_ROSE = 6
+} ellc_refine_status;
+
+typedef struct {
+  float sigma_i2;      /* > 0: variance of a grey value, as in ellc_sim3_params */
+  float huber_k;       /* > 0: Huber threshold on |rp| / sigma_i */
+  float prior_weight;  /* >= 0: factor on the prior's information 1 / V0; 0 switches the prior off */
+  float max_step_rel;  /* > 0: a step beyond max_step_rel * d ends the pixel with BAD_STEP */
+  int   n_iter;        /* 1..8 Gauss-Newton steps */
+  int   min_views;     /* 1..B views with four taps an evaluation needs */
+} ellc_refine_params;  /* 24 bytes */
+void ellc_refine_default_params(ellc_refine_params* params);   /* {16, 1.345, 1, 0.5, 3, 2} */
+
+typedef struct {
+  int32_t n_kept;            /* pixels ellc_keyframe_map_points would keep under `filter` */
+  int32_t n_taking_part;     /* of those, prior_weight == 0 || V0 > 0: the sum of the six counts below */
+  int32_t n_refined, n_too_few_views, n_no_information, n_bad_step, n_views_changed, n_cost_rose;
+  int64_t sum_views;         /* sum of n1 over the refined pixels */
+  double  sum_cost_before;   /* sum of (double)E0 over the refined pixels */
+  double  sum_cost_after;    /* sum of (double)c1 over the refined pixels */
+  int32_t reserved[2];       /* 0 */
+} ellc_refine_stats;         /* 64 bytes, every field naturally aligned */
+
+ellc_status ellc_keyframe_refine_depth(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                       const float* T12, const float* light /* may be NULL */, const ellc_map_filter* filter,
+                                       const ellc_refine_params* params, int dst_kf_slot, float* depth, float* var, uint8_t* views,
+                                       uint8_t* status, ellc_refine_stats* out /* each may be NULL */);
+
+/* Host only, no device work. The inverse of a similarity and of its light, for a caller that holds view -> keyframe transforms
+ * (ellc_keyframe_sim3_align_lit(src = view, dst = K)) and needs keyframe -> view: the 3x3 block M is inverted in double as a general
+ * matrix (adjugate over determinant), t' = -(M^-1 t), each of the twelve entries rounded to f32 once; the light becomes
+ * (1 / gain, -offset / gain), computed in double and rounded once. light_in NULL means (1, 0); light_out may be NULL; the outputs
+ * may be the inputs. Nothing is checked: a singular block or a zero gain gives inf / NaN. */
+void ellc_sim3_invert(const float* T12_in, const float* light_in /* may be NULL */, float* T12_out, float* light_out /* may be NULL */);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

@@ -80,6 +80,13 @@ ellc_status ellc_profile_sim3_step_lit(ellc_ctx* ctx, int B, const int* src_kf_s
                                        const float* light, int level, const ellc_map_filter* filter, const ellc_sim3_params* params,
                                        ellc_sim3_normal* out, float* launches_ms);
 
+/* ellc_keyframe_refine_depth with HIP events around its launches (refine_pixels, refine_finish): launches_ms receives their device
+ * time, without the staging copy in front and the downloads behind. Everything else as the product call. */
+ellc_status ellc_profile_refine_depth(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                      const float* T12, const float* light, const ellc_map_filter* filter, const ellc_refine_params* params,
+                                      int dst_kf_slot, float* depth, float* var, uint8_t* views, uint8_t* status, ellc_refine_stats* out,
+                                      float* launches_ms);
+
 /* Counter calibration: stream `bytes` of device memory once per launch with 4-byte-per-lane loads (the access
  * width of the compacted pixel arrays), `reps` launches, so FETCH_SIZE can be scaled against a known byte count
  * (MI355X_MICROARCH.md, HBM section). Returns average milliseconds per launch. */

@@ -462,6 +462,19 @@ class globalOptimize {
   bool matchAffineLight = false;
   std::vector<MatchSim3> lastMatchSim3;
   std::ofstream match_sim3_file;
+  // The structure step behind the motion step (ellc_keyframe_refine_depth; off by default: nothing changes; it needs refineMatchSim3,
+  // with or without matchAffineLight): the pushed keyframe's ring map is refined against the images of its candidates - level 0, K the
+  // pushed keyframe's ring slot, the views the candidates' ring slots (the first ELLC_REFINE_MAX_VIEWS of them), each at the INVERSE of
+  // its refined transform and light (ellc_sim3_invert: lastMatchSim3 holds candidate -> keyframe), the filter of ellc_main --map, the
+  // default ellc_refine_params with min_views = min(2, views), and the keyframe's own ring slot as the destination. lastRefineStats
+  // keeps the record and lastRefineViews the number of views of the push that ran last (0 and zeros: no candidates), and
+  // refine_matches_file (when open) gets "frameId views n_kept n_taking_part n_refined n_too_few_views n_no_information n_bad_step
+  // n_views_changed n_cost_rose sum_views sum_cost_before sum_cost_after" per push that had candidates. Every rank of a sharded run
+  // computes the whole call, as for the Sim(3) refinement. The ring copy alone is refined: the tracking context's map is not touched.
+  bool refineMatchDepth = false;
+  ellc_refine_stats lastRefineStats = ellc_refine_stats();
+  int lastRefineViews = 0;
+  std::ofstream refine_matches_file;
   // What a closed loop teaches, kept in the TRACKING context (ellc_depth_absorb_keyframes): every candidate of the push's batch is folded
   // into the live depth map of the pushed keyframe at its refined Sim(3). Off by default: nothing changes. On: pushToArray runs
   // findMatchParallel synchronously with the Sim(3) refinement, copies the ring slot of every entry of lastMatchSim3 into the tracking
@@ -933,6 +946,8 @@ class globalOptimize {
     struct Match { int arrayId; float matchValue, rms, angle; };
     std::vector<Match> matches;
     lastMatchSlots.clear();
+    lastRefineStats = ellc_refine_stats();
+    lastRefineViews = 0;
     loopFrameArray[nextArrayId].frameId = testFrame.frameId;
     lastTestedLoopClosureArrayId = -1;
     firstTestedLoopClosureArrayId = -1;
@@ -1061,6 +1076,32 @@ class globalOptimize {
           for (int l = 0; l < n_levels; l++) q.iters += iters[(size_t)b * n_levels + l];
           q.gain = light[(size_t)b * 2];
           q.offset = light[(size_t)b * 2 + 1];
+        }
+      }
+      if (refineMatchSim3 && refineMatchDepth) {
+        const int V = std::min(B, (int)ELLC_REFINE_MAX_VIEWS);
+        std::vector<float> T((size_t)V * 12), light((size_t)V * 2);
+        for (int b = 0; b < V; b++) {
+          const MatchSim3& q = lastMatchSim3[(size_t)b];
+          const float l[2] = {q.gain, q.offset};
+          ellc_sim3_invert(q.T, l, &T[(size_t)b * 12], &light[(size_t)b * 2]);
+        }
+        ellc_map_filter filter;   // the filter of ellc_main --map
+        filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+        ellc_refine_params params;
+        ellc_refine_default_params(&params);
+        params.min_views = std::min(params.min_views, V);
+        lastRefineStats = ellc_refine_stats();
+        lastRefineViews = V;
+        ring.check(ellc_keyframe_refine_depth(ring.ctx, testFrame.ring_slot, 0, V, 1, kf.data(), T.data(), light.data(), &filter, &params,
+                                              testFrame.ring_slot, nullptr, nullptr, nullptr, nullptr, &lastRefineStats),
+                   "ellc_keyframe_refine_depth");
+        if (refine_matches_file.is_open()) {
+          const ellc_refine_stats& r = lastRefineStats;
+          refine_matches_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << V << " " << r.n_kept << " " << r.n_taking_part << " " << r.n_refined
+                              << " " << r.n_too_few_views << " " << r.n_no_information << " " << r.n_bad_step << " " << r.n_views_changed << " "
+                              << r.n_cost_rose << " " << r.sum_views << " " << r.sum_cost_before << " " << r.sum_cost_after << "\n";
+          refine_matches_file.flush();
         }
       }
       for (int b = 0; b < B; b++) {
