@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "ellc_keyframe_depth_consistency", "ellc_keyframe_sim3_step", "ellc_keyframe_sim3_align", "ellc_sim3_default_params", "ellc_sim3_solve", "ellc_sim3_apply",
     "ellc_keyframe_light_step", "ellc_keyframe_sim3_step_lit", "ellc_keyframe_sim3_align_lit", "ellc_light_default_params", "ellc_light_solve",
     "ellc_keyframe_refine_depth", "ellc_refine_default_params", "ellc_sim3_invert",
+    "ellc_keyframe_sweep_depth", "ellc_sweep_default_params",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
     "ellc_gather_start", "ellc_gather_finish", "ellc_gather_results",
@@ -38,7 +39,7 @@ DIAG_SYMBOLS = [
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
     "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
     "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_fuse_depth", "ellc_profile_depth_absorb", "ellc_profile_trial_propagate", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
-    "ellc_profile_light_step", "ellc_profile_sim3_step_lit", "ellc_profile_refine_depth",
+    "ellc_profile_light_step", "ellc_profile_sim3_step_lit", "ellc_profile_refine_depth", "ellc_profile_sweep_depth",
 ]
 
 
@@ -119,6 +120,25 @@ class EllcRefineStats(C.Structure):
     _fields_ = [("n_kept", C.c_int32), ("n_taking_part", C.c_int32), ("n_refined", C.c_int32), ("n_too_few_views", C.c_int32),
                 ("n_no_information", C.c_int32), ("n_bad_step", C.c_int32), ("n_views_changed", C.c_int32), ("n_cost_rose", C.c_int32),
                 ("sum_views", C.c_int64), ("sum_cost_before", C.c_double), ("sum_cost_after", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class EllcSweepParams(C.Structure):
+    """ellc_sweep_params: the weights, the inverse-depth range and the tests of ellc_keyframe_sweep_depth (40 bytes)."""
+    _fields_ = [("sigma_i2", C.c_float), ("huber_k", C.c_float), ("d_min", C.c_float), ("d_max", C.c_float), ("min_grad2", C.c_float),
+                ("max_cost", C.c_float), ("distinct_ratio", C.c_float), ("var_scale", C.c_float), ("n_samples", C.c_int), ("min_views", C.c_int)]
+
+
+SWEEP_STATUS = ("NOT_SWEPT", "CREATED", "NO_VALID_SAMPLE", "AT_RANGE_END", "COST_TOO_HIGH", "NOT_DISTINCT", "FLAT")
+
+
+class EllcSweepStats(C.Structure):
+    """ellc_sweep_stats: what ellc_keyframe_sweep_depth counts (64 bytes)."""
+    _fields_ = [("n_ok", C.c_int32), ("n_swept", C.c_int32), ("n_created", C.c_int32), ("n_no_valid_sample", C.c_int32),
+                ("n_at_range_end", C.c_int32), ("n_cost_too_high", C.c_int32), ("n_not_distinct", C.c_int32), ("n_flat", C.c_int32),
+                ("sum_views", C.c_int64), ("sum_cost", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+SWEEP_STATS_FIELDS = tuple(f[0] for f in EllcSweepStats._fields_ if f[0] != "reserved")
 
 
 class EllcAbsorbParams(C.Structure):
@@ -209,6 +229,8 @@ def _bind(path, symbols, what):
     if hasattr(h, "ellc_refine_default_params"):
         h.ellc_refine_default_params.restype = None
         h.ellc_sim3_invert.restype = None
+    if hasattr(h, "ellc_sweep_default_params"):
+        h.ellc_sweep_default_params.restype = None
     if hasattr(h, "ellc_absorb_default_params"):
         h.ellc_absorb_default_params.restype = None
     for name in symbols:

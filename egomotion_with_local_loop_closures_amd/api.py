@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcSweepParams, EllcSweepStats, SWEEP_STATUS, SWEEP_STATS_FIELDS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -601,6 +601,29 @@ class Context:
         return self._refine("ellc_keyframe_refine_depth", (), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support,
                             support_k2, stride, params)
 
+    # ---- hypotheses created in a keyframe's map by a depth sweep against other views
+    def _sweep(self, name, tail, kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, params):
+        vs = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
+        B = vs.size
+        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
+        li = self._lights(lights, B)
+        prm = params if isinstance(params, EllcSweepParams) else sweep_params(**(params or {}))
+        rows, cols = self.level_shape(level)
+        depth, var = np.zeros((rows, cols), np.float32), np.zeros((rows, cols), np.float32)
+        views, status = np.zeros((rows, cols), np.uint8), np.zeros((rows, cols), np.uint8)
+        st = EllcSweepStats()
+        self._ck(getattr(self._l, name)(self.h, int(kf_slot), int(level), B, int(views_are_keyframes), _p(vs), _p(T), _p(li), C.byref(prm), int(dst_slot),
+                                        _p(depth), _p(var), _p(views), _p(status), C.byref(st), *tail), name)
+        return depth, var, views, status, {k: getattr(st, k) for k in SWEEP_STATS_FIELDS}
+
+    def sweep_depth(self, kf_slot, view_slots, Ts, lights=None, level=0, views_are_keyframes=True, dst_slot=-1, params=None):
+        """Hypotheses for the pixels of keyframe slot kf_slot that hold none, from a sweep over inverse depths against the images of the
+        views (ellc_keyframe_sweep_depth): view_slots, Ts, lights, level, views_are_keyframes and dst_slot as in refine_depth. params: an
+        ellc_sweep_params (sweep_params()) or a dict of sigma_i2, huber_k, d_min, d_max, min_grad2, max_cost, distinct_ratio, var_scale,
+        n_samples, min_views (defaults 16, 1.345, 0.125, 4, 100, 0, 0.7, 1, 64, 2). Returns (depth, var (f32), views, status (u8;
+        SWEEP_STATUS names the values), stats = the fields of ellc_sweep_stats as a dict)."""
+        return self._sweep("ellc_keyframe_sweep_depth", (), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, params)
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -799,6 +822,13 @@ class Context:
                            min_support, support_k2, stride, params)
         return out, ms.value
 
+    def profile_sweep_depth(self, kf_slot, view_slots, Ts, lights=None, level=0, views_are_keyframes=True, dst_slot=-1, params=None):
+        """sweep_depth through ellc_profile_sweep_depth: (result, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_sweep_depth")
+        ms = C.c_float(0)
+        out = self._sweep("ellc_profile_sweep_depth", (C.byref(ms),), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, params)
+        return out, ms.value
+
     def profile_calibrate_read(self, nbytes, reps=10):
         self._need_diag("ellc_profile_calibrate_read")
         ms = C.c_float(0)
@@ -892,6 +922,18 @@ def refine_default_params(sigma_i2=None, huber_k=None, prior_weight=None, max_st
     _lib.lib().ellc_refine_default_params(C.byref(p))
     for k, v in (("sigma_i2", sigma_i2), ("huber_k", huber_k), ("prior_weight", prior_weight), ("max_step_rel", max_step_rel), ("n_iter", n_iter),
                  ("min_views", min_views)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def sweep_params(sigma_i2=None, huber_k=None, d_min=None, d_max=None, min_grad2=None, max_cost=None, distinct_ratio=None, var_scale=None,
+                 n_samples=None, min_views=None):
+    """ellc_sweep_params: the library's defaults (ellc_sweep_default_params) with the given fields replaced."""
+    p = EllcSweepParams()
+    _lib.lib().ellc_sweep_default_params(C.byref(p))
+    for k, v in (("sigma_i2", sigma_i2), ("huber_k", huber_k), ("d_min", d_min), ("d_max", d_max), ("min_grad2", min_grad2), ("max_cost", max_cost),
+                 ("distinct_ratio", distinct_ratio), ("var_scale", var_scale), ("n_samples", n_samples), ("min_views", min_views)):
         if v is not None:
             setattr(p, k, v)
     return p

@@ -275,6 +275,8 @@ struct ellc_ctx {
   ellc::PairScratch refine;
   void* refine_planes_d = nullptr;          // [n] f32 depth, [n] f32 variance, [n] u8 views, [n] u8 status of the largest level asked for
   size_t refine_planes_cap = 0;             //   pixels it holds
+  // ellc_keyframe_sweep_depth: a PairScratch of its own; the four planes it returns are the refinement's (both calls are synchronous)
+  ellc::PairScratch sweep;
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

@@ -41,6 +41,13 @@
 //                    one line per push that had candidates: "frameId views n_kept n_taking_part n_refined n_too_few_views
 //                    n_no_information n_bad_step n_views_changed n_cost_rose sum_views sum_cost_before sum_cost_after". Without the
 //                    flag every output file is as before
+// --sweep-matches PATH  (LC mode, with --match-sim3 only: a usage error otherwise) behind the Sim(3) refinement, and in front of
+//                    --refine-matches' step where both are given, the pixels of the pushed keyframe's ring map that hold no hypothesis
+//                    get one from a depth sweep against the images of its candidates at the inverted refined transforms and lights
+//                    (ellc_keyframe_sweep_depth, level 0, default parameters, into the keyframe's own ring slot;
+//                    globalOptimize::sweepMatchDepth); PATH gets one line per push that had candidates: "frameId views n_ok n_swept
+//                    n_created n_no_valid_sample n_at_range_end n_cost_too_high n_not_distinct n_flat sum_views sum_cost". Without the
+//                    flag every output file is as before
 // --map FILE         (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
 //                    level 0, no variance test, at least 3 supporting neighbours, support_k2 1, every pixel), written as binary PLY
 //                    (x y z float, intensity uchar, var float); every other file is unchanged
@@ -81,7 +88,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--refine-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--sweep-matches PATH] [--refine-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -91,7 +98,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false, match_light = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, match_geometry, match_sim3, refine_matches, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
+  std::string comm_id_file, match_quality, match_geometry, match_sim3, refine_matches, sweep_matches, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -112,6 +119,7 @@ int main(int argc, char** argv) {
     else if (a == "--match-sim3" && i + 1 < argc) match_sim3 = argv[++i];
     else if (a == "--match-light") match_light = true;
     else if (a == "--refine-matches" && i + 1 < argc) refine_matches = argv[++i];
+    else if (a == "--sweep-matches" && i + 1 < argc) sweep_matches = argv[++i];
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (a == "--fuse" && i + 1 < argc) fuse_file = argv[++i];
@@ -127,6 +135,10 @@ int main(int argc, char** argv) {
   }
   if (!refine_matches.empty() && match_sim3.empty()) {
     std::fprintf(stderr, "--refine-matches needs --match-sim3 PATH: the map is refined at the transforms the Sim(3) refinement returns\n");
+    return -1;
+  }
+  if (!sweep_matches.empty() && match_sim3.empty()) {
+    std::fprintf(stderr, "--sweep-matches needs --match-sim3 PATH: the sweep runs at the transforms the Sim(3) refinement returns\n");
     return -1;
   }
   if (!match_quality.empty() && world > 1) {
@@ -210,6 +222,11 @@ int main(int argc, char** argv) {
       globalOptimizeLoop->refine_matches_file.open(refine_matches.c_str());
       if (!globalOptimizeLoop->refine_matches_file) { std::fprintf(stderr, "cannot open %s\n", refine_matches.c_str()); return -1; }
       globalOptimizeLoop->refineMatchDepth = true;
+    }
+    if (lc && !sweep_matches.empty()) {
+      globalOptimizeLoop->sweep_matches_file.open(sweep_matches.c_str());
+      if (!globalOptimizeLoop->sweep_matches_file) { std::fprintf(stderr, "cannot open %s\n", sweep_matches.c_str()); return -1; }
+      globalOptimizeLoop->sweepMatchDepth = true;
     }
     if (lc && !absorb_matches.empty()) {
       globalOptimizeLoop->absorb_file.open(absorb_matches.c_str());

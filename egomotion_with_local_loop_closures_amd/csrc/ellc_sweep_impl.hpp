@@ -1,0 +1,158 @@
+// ellc_keyframe_sweep_depth, ellc_sweep_default_params (include/ellc_abi.h): the host side of the depth sweep that creates hypotheses in
+// a keyframe slot from other views. Included at the end of ellc_hip.hip behind ellc_refine_impl.hpp: ellc_keyframe_refine_depth's
+// refusals, staging of the views (RefineView) and four planes are used here as they stand; the record and the scratch are this call's own.
+#pragma once
+#include "ellc_refine_impl.hpp"
+#include "ellc_kernels_sweep.hpp"
+
+using namespace ellc;
+
+static_assert(sizeof(ellc_sweep_params) == 40 && sizeof(ellc_sweep_stats) == 64 && offsetof(ellc_sweep_stats, sum_views) == 32 &&
+                  offsetof(ellc_sweep_stats, sum_cost) == 40 && offsetof(ellc_sweep_stats, reserved) == 48,
+              "ellc_sweep_params is 40 bytes, ellc_sweep_stats 64");
+
+namespace {
+
+// launches_ms (the diagnostic hook only): device time of sweep_pixels and sweep_finish, HIP events around them
+ellc_status sweep_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int views_are_kf, const int* view_slots, const float* T12, const float* light,
+                             const ellc_sweep_params* p, int dst, float* depth, float* var, uint8_t* views, uint8_t* status, ellc_sweep_stats* out,
+                             float* launches_ms) {
+  const char* who = "ellc_keyframe_sweep_depth";
+  if (!c) return ELLC_ERR_BAD_ARG;
+  const std::string w(who);
+  // validated first: a refused call leaves the context and every slot as they were and writes nothing
+  if (!view_slots || !T12 || !p) return fail(c, ELLC_ERR_BAD_ARG, w + ": null pointer");
+  if (B < 1 || B > ELLC_REFINE_MAX_VIEWS) return fail(c, ELLC_ERR_BAD_ARG, w + ": B out of range");
+  if (views_are_kf < 0 || views_are_kf > 1) return fail(c, ELLC_ERR_BAD_ARG, w + ": views_are_keyframes not 0 or 1");
+  if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, w + ": level out of range");
+  const LevelGeom& g = c->geom_h[level];
+  if (g.n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, w + ": more than 2^24 pixels on the level");
+  for (int k = 0; k < 12 * B; k++)
+    if (!std::isfinite(T12[k])) return fail(c, ELLC_ERR_BAD_ARG, w + ": transform not finite");
+  ELLC_TRY(light_check(c, who, B, light));
+  if (!std::isfinite(p->sigma_i2) || !std::isfinite(p->huber_k) || !std::isfinite(p->d_min) || !std::isfinite(p->d_max) || !std::isfinite(p->min_grad2) ||
+      !std::isfinite(p->max_cost) || !std::isfinite(p->distinct_ratio) || !std::isfinite(p->var_scale))
+    return fail(c, ELLC_ERR_BAD_ARG, w + ": parameter not finite");
+  if (!(p->sigma_i2 > 0.0f) || !(p->huber_k > 0.0f) || !(p->d_min > 0.0f) || !(p->d_min < p->d_max) || !std::isfinite(1.0f / p->d_min) ||
+      !(p->min_grad2 >= 0.0f) || !(p->distinct_ratio > 0.0f) || !(p->distinct_ratio <= 1.0f) || !(p->var_scale > 0.0f) || p->n_samples < 3 ||
+      p->n_samples > ELLC_SWEEP_MAX_SAMPLES || p->min_views < 1 || p->min_views > B)
+    return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
+  if (dst < -1 || dst >= c->cfg.max_keyframes) return fail(c, ELLC_ERR_BAD_ARG, w + ": destination slot out of range");
+  if (dst >= 0 && level != 0) return fail(c, ELLC_ERR_BAD_ARG, w + ": a destination slot takes level 0 only");
+  ELLC_TRY(ring_check_slots(c, who, 1, &kf_slot, c->cfg.max_keyframes));
+  ELLC_TRY(ring_check_slots(c, who, B, view_slots, views_are_kf ? c->cfg.max_keyframes : c->cfg.max_frames));
+  ELLC_TRY(ring_check_ready(c, who, 1, &kf_slot));
+  for (int b = 0; b < B; b++)
+    if (!(views_are_kf ? c->kf_has_image[view_slots[b]] : c->fr_has_image[view_slots[b]]))
+      return fail(c, ELLC_ERR_NOT_READY, w + ": view slot lacks an image");
+  ELLC_ENTER(c);   // behind the batches in flight, on the main stream
+  const size_t n = (size_t)g.n;
+  const int blocks = (int)((n + 255) / 256);
+  ELLC_TRY(pair_reserve(c, c->sweep, ELLC_REFINE_MAX_VIEWS, sizeof(RefineView), sizeof(SweepRec), (size_t)blocks));
+  ELLC_TRY(dev_grow(c, &c->refine_planes_d, &c->refine_planes_cap, n, 10));   // two f32 planes and two u8 planes, shared with the refinement
+  RefineView* vw = (RefineView*)c->sweep.stage_h;
+  for (int b = 0; b < B; b++) {
+    const size_t e = (size_t)level * (views_are_kf ? c->cfg.max_keyframes : c->cfg.max_frames) + view_slots[b];
+    vw[b].img = views_are_kf ? c->kf_tab_h[e].img : c->fr_tab_h[e].img;
+    std::memcpy(vw[b].T, T12 + (size_t)12 * b, 12 * sizeof(float));
+    vw[b].gain = light ? light[2 * b] : 1.0f;
+    vw[b].offset = light ? light[2 * b + 1] : 0.0f;
+  }
+  ELLC_HIP(c, hipMemcpyAsync(c->sweep.stage_d, c->sweep.stage_h, (size_t)B * sizeof(RefineView), hipMemcpyHostToDevice, c->stream));
+  const ellc_map_filter every = {0.0f, 0, 1.0f, 1};   // (ring_view wants one; no kernel of this call reads it)
+  SweepArgs a{};
+  a.v = ring_view(c, level, &every);
+  a.views = (const RefineView*)c->sweep.stage_d;
+  a.partials = (SweepRec*)c->sweep.partials_d;
+  a.out = (SweepRec*)c->sweep.out_dev_alias;
+  char* planes = (char*)c->refine_planes_d;
+  const size_t cap = c->refine_planes_cap;
+  a.depth = (float*)planes;
+  a.var = (float*)(planes + 4 * cap);
+  a.nviews = (uint8_t*)(planes + 8 * cap);
+  a.status = (uint8_t*)(planes + 9 * cap);
+  a.kf_slot = kf_slot;
+  a.B = B;
+  a.blocks = blocks;
+  a.first = 0;
+  a.w0 = 1.0f / p->sigma_i2;
+  a.sp = sqrtf(a.w0);
+  a.huber_k = p->huber_k;
+  a.d_min = p->d_min;
+  a.dstep = (p->d_max - p->d_min) / (float)(p->n_samples - 1);
+  a.min_grad2 = p->min_grad2;
+  a.max_cost = p->max_cost;
+  a.distinct_ratio = p->distinct_ratio;
+  a.var_scale = p->var_scale;
+  a.n_samples = p->n_samples;
+  a.min_views = p->min_views;
+  LaunchTimer t(c, launches_ms);
+  ELLC_TRY(t.begin());
+  hipLaunchKernelGGL(sweep_pixels, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(sweep_finish, dim3(1), dim3(64), 0, c->stream, a);
+  ELLC_HIP(c, hipGetLastError());
+  ELLC_TRY(t.end());
+  if (!views_are_kf) {   // a later upload into a frame slot waits for this reader
+    std::vector<char> seen((size_t)c->cfg.max_frames, 0);
+    for (int b = 0; b < B; b++)
+      if (!seen[view_slots[b]]) {
+        seen[view_slots[b]] = 1;
+        ELLC_TRY(mark_frame_use(c, view_slots[b]));
+      }
+  }
+  if (depth) ELLC_HIP(c, hipMemcpyAsync(depth, a.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (var) ELLC_HIP(c, hipMemcpyAsync(var, a.var, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (views) ELLC_HIP(c, hipMemcpyAsync(views, a.nviews, n, hipMemcpyDeviceToHost, c->stream));
+  if (status) ELLC_HIP(c, hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToHost, c->stream));
+  const SweepRec* rec = (const SweepRec*)c->sweep.out_h;
+  if (dst >= 0) {
+    // the level-0 planes into keyframe slot dst, behind the kernel that read K and the views: ellc_keyframe_refine_depth's store
+    const KfLevelDev& k = c->kf_tab_h[dst];
+    invalidate_records(c, dst);
+    ELLC_HIP(c, hipMemcpyAsync(k.depth, a.depth, n * 4, hipMemcpyDeviceToDevice, c->stream));
+    ELLC_HIP(c, hipMemcpyAsync(k.var, a.var, n * 4, hipMemcpyDeviceToDevice, c->stream));
+    ELLC_TRY(finish_depth_planes(c, dst, [&]() {
+      (void)hipStreamSynchronize(c->stream);
+      return (size_t)rec->n[8];
+    }));
+  }
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  if (out) {
+    std::memset(out, 0, sizeof(*out));
+    out->n_ok = rec->n[0]; out->n_swept = rec->n[1];
+    out->n_created = rec->n[2]; out->n_no_valid_sample = rec->n[3]; out->n_at_range_end = rec->n[4];
+    out->n_cost_too_high = rec->n[5]; out->n_not_distinct = rec->n[6]; out->n_flat = rec->n[7];
+    out->sum_views = rec->sum_views;
+    out->sum_cost = rec->s[0];
+  }
+  return t.read();
+}
+
+}  // namespace
+
+extern "C" {
+
+void ellc_sweep_default_params(ellc_sweep_params* p) {
+  if (!p) return;
+  p->sigma_i2 = 16.0f; p->huber_k = 1.345f; p->d_min = 0.125f; p->d_max = 4.0f; p->min_grad2 = 100.0f; p->max_cost = 0.0f;
+  p->distinct_ratio = 0.7f; p->var_scale = 1.0f; p->n_samples = 64; p->min_views = 2;
+}
+
+ellc_status ellc_keyframe_sweep_depth(ellc_ctx* c, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots, const float* T12,
+                                      const float* light, const ellc_sweep_params* params, int dst_kf_slot, float* depth, float* var, uint8_t* views,
+                                      uint8_t* status, ellc_sweep_stats* out) {
+  return sweep_depth_impl(c, kf_slot, level, B, views_are_keyframes, view_slots, T12, light, params, dst_kf_slot, depth, var, views, status, out,
+                          nullptr);
+}
+
+#ifdef ELLC_DIAG_ABI
+ellc_status ellc_profile_sweep_depth(ellc_ctx* c, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots, const float* T12,
+                                     const float* light, const ellc_sweep_params* params, int dst_kf_slot, float* depth, float* var, uint8_t* views,
+                                     uint8_t* status, ellc_sweep_stats* out, float* launches_ms) {
+  return ring_profiled(launches_ms, [&](float* ms) {
+    return sweep_depth_impl(c, kf_slot, level, B, views_are_keyframes, view_slots, T12, light, params, dst_kf_slot, depth, var, views, status, out, ms);
+  });
+}
+#endif   // ELLC_DIAG_ABI
+
+}  // extern "C"

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 20   /* ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 21   /* ellc_keyframe_sweep_depth, ellc_sweep_default_params; 20: ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -848,6 +848,94 @@ ellc_status ellc_keyframe_refine_depth(ellc_ctx* ctx, int kf_slot, int level, in
  * (1 / gain, -offset / gain), computed in double and rounded once. light_in NULL means (1, 0); light_out may be NULL; the outputs
  * may be the inputs. Nothing is checked: a singular block or a zero gain gives inf / NaN. */
 void ellc_sim3_invert(const float* T12_in, const float* light_in /* may be NULL */, float* T12_out, float* light_out /* may be NULL */);
+
+/* ---- hypotheses created by a depth sweep (v21) ----------------------------------------------------------------------
+ * The structure-CREATION step beside the refinement above: the pixels of keyframe slot kf_slot (K) that hold no hypothesis and have
+ * texture get one from a sweep over n_samples inverse depths against the images of B other views. K, `level`, the views,
+ * views_are_keyframes, T12, light and dst_kf_slot mean what they mean in ellc_keyframe_refine_depth: K's camera goes into view b's
+ * through T12 + 12 * b, light + 2 * b is (gain, offset) with K as the source (NULL: (1, 0)), only a view's image on `level` is read.
+ * K's depth Z0, variance V0 and image I (grey values as f32) are read on `level`. Per pixel (px, py) of K, all arithmetic IEEE f32
+ * in this order, no contraction, correctly rounded divisions:
+ *   1. SWEPT PIXELS. A pixel is OK iff Z0 > 0 && Z0 <= FLT_MAX && V0 >= 0 (ellc_keyframe_map_points' rule; n_ok). It is SWEPT iff it
+ *      is not OK, 1 <= px <= cols - 2 and 1 <= py <= rows - 2, and with gxc = I(px+1,py) - I(px-1,py), gyc = I(px,py+1) - I(px,py-1):
+ *      (gxc*gxc) + (gyc*gyc) >= min_grad2 (n_swept). No ellc_map_filter takes part.
+ *   2. SAMPLES. dstep = (d_max - d_min) / (float)(n_samples - 1), computed once on the host in f32;
+ *      d_k = d_min + (float)k * dstep;  Z = 1 / d_k,  k = 0 .. n_samples - 1.
+ *   3. COST OF SAMPLE k. E = 0, n = 0, then the views in ascending b. For the five pattern pixels j = 0..4 at the offsets (0,0),
+ *      (1,0), (-1,0), (0,1), (0,-1) in this order: the candidate is ellc_keyframe_render_depth's for (px+dx, py+dy, Z, V = 0.0f) at
+ *      view b's T, with its drops; then rule 3 of ellc_keyframe_sim3_step word for word (the four-tap condition, Iw, e and wp with the
+ *      host-rounded w0 and sp);  rp = Iw - (gain * Is_j + offset), Is_j K's grey value at the pattern pixel;  c_j = (rp * rp) * wp.
+ *      A view counts iff all five pattern pixels have a candidate and four taps: then E = E + ((((c_0 + c_1) + c_2) + c_3) + c_4),
+ *      n += 1; otherwise it contributes nothing.  cost = E / (float)n.  The sample is VALID iff n >= min_views && cost <= FLT_MAX
+ *      (NaN fails).
+ *   4. DECISION, in this order. No valid sample: NO_VALID_SAMPLE. k1 is the lowest k among the valid samples of smallest cost, c1
+ *      and n1 its cost and n. k1 == 0, k1 == n_samples - 1 or a neighbour k1 - 1 / k1 + 1 not valid: AT_RANGE_END; cm and cp are the
+ *      neighbours' costs. max_cost > 0 && !(c1 <= max_cost): COST_TOO_HIGH. c2 is the smallest valid cost among the samples with
+ *      |k - k1| >= 2: !(c1 <= distinct_ratio * c2): NOT_DISTINCT; with no such sample the test passes.
+ *        curv = (cm - (2.0f * c1)) + cp;                                  !(curv > 0 && curv <= FLT_MAX): FLAT
+ *        off = (0.5f * (cm - cp)) / curv;  d = d_k1 + off * dstep;
+ *        v = var_scale * ((2.0f * (dstep * dstep)) / ((float)n1 * curv));
+ *        !(d > 0 && d <= FLT_MAX && v >= 0 && v <= FLT_MAX): FLAT;  otherwise CREATED.
+ *      v is the inverse of half the second difference of the summed chi-square of the n1 views at the parabola's vertex: a MODEL
+ *      figure, conservative where the images are cleaner than sigma_i2 says.
+ *   5. OUTPUTS (host pointers, dense cols x rows of the level, each may be NULL). CREATED pixels get depth = 1 / d, var = v,
+ *      views = n1. Every other pixel keeps K's own depth and variance BITS (OK pixels, NaN, inf and negative ones included); its
+ *      `views` is n1 where a k1 exists and 0 otherwise. `status` is an ellc_sweep_status. The integer stats are exact; sum_views adds
+ *      n1 and sum_cost (double)c1 over the created pixels, sum_cost in the fixed order of the refinement's sums (256-pixel blocks by
+ *      the level's size, then the blocks): its bytes are a function of the inputs alone.
+ *   6. dst_kf_slot is -1 or a keyframe slot, at level 0 only: afterwards the slot is what ellc_keyframe_set_depth(dst_kf_slot,
+ *      depth, var) with the returned planes would leave. It may be K itself (the main use) or a view.
+ *   The result is a function of the intrinsics, the level, K's three planes, the views' images, the T's, the lights and the params
+ *   ALONE; cfg.arith, cfg.grid_batch and whatever else is in flight do not enter it. The order of the views enters through the f32
+ *   sum E only. A view in which no pattern gets its taps changes no byte. A second call gives the same bytes.
+ *   Synchronous, ordered like every other non-batch entry point. A refused call changes nothing and writes nothing.
+ * The defaults {16, 1.345, 0.125, 4, 100, 0, 0.7, 1, 64, 2} are DESIGN CHOICES, not measured optima: a depth range of 0.25 .. 8 in the
+ * keyframe's own units (the reference scales a new keyframe's mean inverse depth to 1), a central difference of 10 grey values, a
+ * best cost at most 0.7 of the best one two steps away.
+ * ELLC_ERR_BAD_ARG, in this order: a NULL view_slots, T12 or params; B outside 1..ELLC_REFINE_MAX_VIEWS; views_are_keyframes outside
+ * 0..1; the level out of range or more than 2^24 pixels on it; a value of T12 or light that is not finite; a value of params that is
+ * not finite; sigma_i2 <= 0, huber_k <= 0, !(0 < d_min < d_max) or 1 / d_min not finite, min_grad2 < 0, distinct_ratio outside
+ * (0, 1], var_scale <= 0, n_samples outside 3..ELLC_SWEEP_MAX_SAMPLES, min_views outside 1..B; the destination errors of the fusion;
+ * a slot out of range.
+ * ELLC_ERR_NOT_READY: K without image or depth, a view without image. */
+#define ELLC_SWEEP_MAX_SAMPLES 64
+
+typedef enum {
+  ELLC_SWEEP_NOT_SWEPT = 0,
+  ELLC_SWEEP_CREATED = 1,
+  ELLC_SWEEP_NO_VALID_SAMPLE = 2,
+  ELLC_SWEEP_AT_RANGE_END = 3,
+  ELLC_SWEEP_COST_TOO_HIGH = 4,
+  ELLC_SWEEP_NOT_DISTINCT = 5,
+  ELLC_SWEEP_FLAT = 6
+} ellc_sweep_status;
+
+typedef struct {
+  float sigma_i2;        /* > 0: variance of a grey value, as in ellc_refine_params */
+  float huber_k;         /* > 0: Huber threshold on |rp| / sigma_i */
+  float d_min, d_max;    /* the inverse-depth range: 0 < d_min < d_max, finite, 1 / d_min finite */
+  float min_grad2;       /* >= 0: squared central-difference gradient a swept pixel needs */
+  float max_cost;        /* <= 0: no test; otherwise the best sample's cost may not exceed it */
+  float distinct_ratio;  /* in (0, 1]: c1 <= distinct_ratio * c2 */
+  float var_scale;       /* > 0: factor on the model variance */
+  int   n_samples;       /* 3 .. ELLC_SWEEP_MAX_SAMPLES */
+  int   min_views;       /* 1..B views with all five pattern pixels a sample needs */
+} ellc_sweep_params;     /* 40 bytes */
+void ellc_sweep_default_params(ellc_sweep_params* params);   /* {16, 1.345, 0.125, 4, 100, 0, 0.7, 1, 64, 2}: design choices */
+
+typedef struct {
+  int32_t n_ok;              /* pixels that hold a hypothesis already */
+  int32_t n_swept;           /* pixels swept: the sum of the six counts below */
+  int32_t n_created, n_no_valid_sample, n_at_range_end, n_cost_too_high, n_not_distinct, n_flat;
+  int64_t sum_views;         /* sum of n1 over the created pixels */
+  double  sum_cost;          /* sum of (double)c1 over the created pixels */
+  int32_t reserved[4];       /* 0 */
+} ellc_sweep_stats;          /* 64 bytes, every field naturally aligned */
+
+ellc_status ellc_keyframe_sweep_depth(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                      const float* T12, const float* light /* may be NULL */, const ellc_sweep_params* params,
+                                      int dst_kf_slot, float* depth, float* var, uint8_t* views, uint8_t* status,
+                                      ellc_sweep_stats* out /* each may be NULL */);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

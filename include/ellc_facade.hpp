@@ -475,6 +475,17 @@ class globalOptimize {
   ellc_refine_stats lastRefineStats = ellc_refine_stats();
   int lastRefineViews = 0;
   std::ofstream refine_matches_file;
+  // The structure-CREATION step in front of that refinement (ellc_keyframe_sweep_depth; off by default: nothing changes; it needs
+  // refineMatchSim3, with or without matchAffineLight and refineMatchDepth): the pixels of the pushed keyframe's ring map that hold no
+  // hypothesis get one from a depth sweep against the same views at the same inverted transforms and lights - level 0, the default
+  // ellc_sweep_params with min_views = min(2, views), the keyframe's own ring slot as the destination - BEFORE refineMatchDepth runs, so
+  // that the refinement polishes what the sweep created. lastSweepStats / lastSweepViews keep the record (zeros: no candidates) and
+  // sweep_matches_file (when open) gets "frameId views n_ok n_swept n_created n_no_valid_sample n_at_range_end n_cost_too_high
+  // n_not_distinct n_flat sum_views sum_cost" per push that had candidates. The ring copy alone is touched.
+  bool sweepMatchDepth = false;
+  ellc_sweep_stats lastSweepStats = ellc_sweep_stats();
+  int lastSweepViews = 0;
+  std::ofstream sweep_matches_file;
   // What a closed loop teaches, kept in the TRACKING context (ellc_depth_absorb_keyframes): every candidate of the push's batch is folded
   // into the live depth map of the pushed keyframe at its refined Sim(3). Off by default: nothing changes. On: pushToArray runs
   // findMatchParallel synchronously with the Sim(3) refinement, copies the ring slot of every entry of lastMatchSim3 into the tracking
@@ -948,6 +959,8 @@ class globalOptimize {
     lastMatchSlots.clear();
     lastRefineStats = ellc_refine_stats();
     lastRefineViews = 0;
+    lastSweepStats = ellc_sweep_stats();
+    lastSweepViews = 0;
     loopFrameArray[nextArrayId].frameId = testFrame.frameId;
     lastTestedLoopClosureArrayId = -1;
     firstTestedLoopClosureArrayId = -1;
@@ -1078,14 +1091,35 @@ class globalOptimize {
           q.offset = light[(size_t)b * 2 + 1];
         }
       }
-      if (refineMatchSim3 && refineMatchDepth) {
-        const int V = std::min(B, (int)ELLC_REFINE_MAX_VIEWS);
-        std::vector<float> T((size_t)V * 12), light((size_t)V * 2);
+      // the views of the two structure steps: the candidates' ring slots, each at the INVERSE of its refined transform and light
+      const int V = std::min(B, (int)ELLC_REFINE_MAX_VIEWS);
+      std::vector<float> T, light;
+      if (refineMatchSim3 && (sweepMatchDepth || refineMatchDepth)) {
+        T.resize((size_t)V * 12); light.resize((size_t)V * 2);
         for (int b = 0; b < V; b++) {
           const MatchSim3& q = lastMatchSim3[(size_t)b];
           const float l[2] = {q.gain, q.offset};
           ellc_sim3_invert(q.T, l, &T[(size_t)b * 12], &light[(size_t)b * 2]);
         }
+      }
+      if (refineMatchSim3 && sweepMatchDepth) {
+        ellc_sweep_params params;
+        ellc_sweep_default_params(&params);
+        params.min_views = std::min(params.min_views, V);
+        lastSweepStats = ellc_sweep_stats();
+        lastSweepViews = V;
+        ring.check(ellc_keyframe_sweep_depth(ring.ctx, testFrame.ring_slot, 0, V, 1, kf.data(), T.data(), light.data(), &params, testFrame.ring_slot,
+                                             nullptr, nullptr, nullptr, nullptr, &lastSweepStats),
+                   "ellc_keyframe_sweep_depth");
+        if (sweep_matches_file.is_open()) {
+          const ellc_sweep_stats& r = lastSweepStats;
+          sweep_matches_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << V << " " << r.n_ok << " " << r.n_swept << " " << r.n_created << " "
+                             << r.n_no_valid_sample << " " << r.n_at_range_end << " " << r.n_cost_too_high << " " << r.n_not_distinct << " " << r.n_flat
+                             << " " << r.sum_views << " " << r.sum_cost << "\n";
+          sweep_matches_file.flush();
+        }
+      }
+      if (refineMatchSim3 && refineMatchDepth) {
         ellc_map_filter filter;   // the filter of ellc_main --map
         filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
         ellc_refine_params params;
