@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "ellc_keyframe_light_step", "ellc_keyframe_sim3_step_lit", "ellc_keyframe_sim3_align_lit", "ellc_light_default_params", "ellc_light_solve",
     "ellc_keyframe_refine_depth", "ellc_refine_default_params", "ellc_sim3_invert",
     "ellc_keyframe_sweep_depth", "ellc_sweep_default_params",
+    "ellc_keyframe_cull_depth", "ellc_cull_default_params",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
     "ellc_gather_start", "ellc_gather_finish", "ellc_gather_results",
@@ -39,7 +40,7 @@ DIAG_SYMBOLS = [
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
     "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
     "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_fuse_depth", "ellc_profile_depth_absorb", "ellc_profile_trial_propagate", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
-    "ellc_profile_light_step", "ellc_profile_sim3_step_lit", "ellc_profile_refine_depth", "ellc_profile_sweep_depth",
+    "ellc_profile_light_step", "ellc_profile_sim3_step_lit", "ellc_profile_refine_depth", "ellc_profile_sweep_depth", "ellc_profile_cull_depth",
 ]
 
 
@@ -141,6 +142,25 @@ class EllcSweepStats(C.Structure):
 SWEEP_STATS_FIELDS = tuple(f[0] for f in EllcSweepStats._fields_ if f[0] != "reserved")
 
 
+class EllcCullParams(C.Structure):
+    """ellc_cull_params: the agreement rule, the photometric bound and the four counts of ellc_keyframe_cull_depth (28 bytes)."""
+    _fields_ = [("agree_k2", C.c_float), ("sigma_i2", C.c_float), ("photo_k", C.c_float), ("min_support", C.c_int), ("min_judged", C.c_int),
+                ("min_in_front", C.c_int), ("min_photo", C.c_int)]
+
+
+CULL_STATUS = ("NOT_TAKING_PART", "KEPT", "CULLED_FREE_SPACE", "CULLED_UNSUPPORTED", "CULLED_PHOTO", "UNSEEN")
+
+
+class EllcCullStats(C.Structure):
+    """ellc_cull_stats: what ellc_keyframe_cull_depth counts (64 bytes)."""
+    _fields_ = [("n_kept", C.c_int32), ("n_retained", C.c_int32), ("n_unseen", C.c_int32), ("n_culled_free_space", C.c_int32),
+                ("n_culled_unsupported", C.c_int32), ("n_culled_photo", C.c_int32),
+                ("sum_agree", C.c_int64), ("sum_in_front", C.c_int64), ("sum_behind", C.c_int64), ("sum_photo", C.c_int64), ("sum_photo_bad", C.c_int64)]
+
+
+CULL_STATS_FIELDS = tuple(f[0] for f in EllcCullStats._fields_)
+
+
 class EllcAbsorbParams(C.Structure):
     """ellc_absorb_params: the gates and limits of ellc_depth_absorb_keyframes."""
     _fields_ = [("agree_k2", C.c_float), ("max_fold", C.c_int), ("photo_gate", C.c_int), ("src_validity", C.c_int), ("finalise", C.c_int)]
@@ -231,6 +251,8 @@ def _bind(path, symbols, what):
         h.ellc_sim3_invert.restype = None
     if hasattr(h, "ellc_sweep_default_params"):
         h.ellc_sweep_default_params.restype = None
+    if hasattr(h, "ellc_cull_default_params"):
+        h.ellc_cull_default_params.restype = None
     if hasattr(h, "ellc_absorb_default_params"):
         h.ellc_absorb_default_params.restype = None
     for name in symbols:

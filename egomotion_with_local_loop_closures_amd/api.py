@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcSweepParams, EllcSweepStats, SWEEP_STATUS, SWEEP_STATS_FIELDS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcSweepParams, EllcSweepStats, SWEEP_STATUS, SWEEP_STATS_FIELDS, EllcCullParams, EllcCullStats, CULL_STATUS, CULL_STATS_FIELDS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -624,6 +624,36 @@ class Context:
         SWEEP_STATUS names the values), stats = the fields of ellc_sweep_stats as a dict)."""
         return self._sweep("ellc_keyframe_sweep_depth", (), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, params)
 
+    # ---- the hypotheses of a keyframe's map that other views contradict, removed
+    def _cull(self, name, tail, kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support, support_k2, stride, params):
+        vs = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
+        B = vs.size
+        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
+        li = self._lights(lights, B)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        prm = params if isinstance(params, EllcCullParams) else cull_default_params(**(params or {}))
+        rows, cols = self.level_shape(level)
+        res = dict(depth=np.zeros((rows, cols), np.float32), var=np.zeros((rows, cols), np.float32), votes=np.zeros((rows, cols), np.uint32),
+                   photo=np.zeros((rows, cols), np.uint8), status=np.zeros((rows, cols), np.uint8))
+        st = EllcCullStats()
+        self._ck(getattr(self._l, name)(self.h, int(kf_slot), int(level), B, int(views_are_keyframes), _p(vs), _p(T), _p(li), C.byref(flt), C.byref(prm),
+                                        int(dst_slot), _p(res["depth"]), _p(res["var"]), _p(res["votes"]), _p(res["photo"]), _p(res["status"]),
+                                        C.byref(st), *tail), name)
+        res["stats"] = {k: getattr(st, k) for k in CULL_STATS_FIELDS}
+        return res
+
+    def cull_depth(self, kf_slot, view_slots, Ts, lights=None, level=0, views_are_keyframes=True, dst_slot=-1, max_var=0.0, min_support=0,
+                   support_k2=1.0, stride=1, params=None):
+        """The hypotheses of keyframe slot kf_slot that the views contradict, removed (ellc_keyframe_cull_depth): view_slots, Ts, lights,
+        level, views_are_keyframes, dst_slot and the filter as in refine_depth. A keyframe view that holds a depth votes geometrically
+        (agree / in front / behind, depth_consistency's rule) and photometrically, every other view photometrically only. params: an
+        ellc_cull_params (cull_default_params()) or a dict of agree_k2, sigma_i2, photo_k, min_support, min_judged, min_in_front,
+        min_photo (defaults 1, 16, 3, 1, 2, 1, 2; photo_k <= 0: no photometric vote). Returns dict(depth, var (f32; a culled pixel is
+        0 / -1, every other keeps the slot's bits), votes (u32: agree | in_front << 8 | behind << 16 | photo_bad << 24), photo, status
+        (u8; CULL_STATUS names the values), stats = the fields of ellc_cull_stats). The order of the views does not enter the result."""
+        return self._cull("ellc_keyframe_cull_depth", (), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support,
+                          support_k2, stride, params)
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -829,6 +859,15 @@ class Context:
         out = self._sweep("ellc_profile_sweep_depth", (C.byref(ms),), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, params)
         return out, ms.value
 
+    def profile_cull_depth(self, kf_slot, view_slots, Ts, lights=None, level=0, views_are_keyframes=True, dst_slot=-1, max_var=0.0, min_support=0,
+                           support_k2=1.0, stride=1, params=None):
+        """cull_depth through ellc_profile_cull_depth: (result, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_cull_depth")
+        ms = C.c_float(0)
+        out = self._cull("ellc_profile_cull_depth", (C.byref(ms),), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var,
+                         min_support, support_k2, stride, params)
+        return out, ms.value
+
     def profile_calibrate_read(self, nbytes, reps=10):
         self._need_diag("ellc_profile_calibrate_read")
         ms = C.c_float(0)
@@ -934,6 +973,17 @@ def sweep_params(sigma_i2=None, huber_k=None, d_min=None, d_max=None, min_grad2=
     _lib.lib().ellc_sweep_default_params(C.byref(p))
     for k, v in (("sigma_i2", sigma_i2), ("huber_k", huber_k), ("d_min", d_min), ("d_max", d_max), ("min_grad2", min_grad2), ("max_cost", max_cost),
                  ("distinct_ratio", distinct_ratio), ("var_scale", var_scale), ("n_samples", n_samples), ("min_views", min_views)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def cull_default_params(agree_k2=None, sigma_i2=None, photo_k=None, min_support=None, min_judged=None, min_in_front=None, min_photo=None):
+    """ellc_cull_params: the library's defaults (ellc_cull_default_params) with the given fields replaced."""
+    p = EllcCullParams()
+    _lib.lib().ellc_cull_default_params(C.byref(p))
+    for k, v in (("agree_k2", agree_k2), ("sigma_i2", sigma_i2), ("photo_k", photo_k), ("min_support", min_support), ("min_judged", min_judged),
+                 ("min_in_front", min_in_front), ("min_photo", min_photo)):
         if v is not None:
             setattr(p, k, v)
     return p

@@ -277,6 +277,10 @@ struct ellc_ctx {
   size_t refine_planes_cap = 0;             //   pixels it holds
   // ellc_keyframe_sweep_depth: a PairScratch of its own; the four planes it returns are the refinement's (both calls are synchronous)
   ellc::PairScratch sweep;
+  // ellc_keyframe_cull_depth: a PairScratch of its own (a staged view carries two more pointers) and its five planes
+  ellc::PairScratch cull;
+  void* cull_planes_d = nullptr;            // [n] f32 depth, [n] f32 variance, [n] u32 votes, [n] u8 photo, [n] u8 status of the largest level asked for
+  size_t cull_planes_cap = 0;               //   pixels it holds
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

@@ -1246,7 +1246,9 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   ellc::pair_free(c->light);
   ellc::pair_free(c->refine);
   ellc::pair_free(c->sweep);
+  ellc::pair_free(c->cull);
   if (c->refine_planes_d) (void)hipFree(c->refine_planes_d);
+  if (c->cull_planes_d) (void)hipFree(c->cull_planes_d);
   if (c->trial_bits_d) (void)hipFree(c->trial_bits_d);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
   if (c->ingest_bgr) (void)hipFree(c->ingest_bgr);
@@ -2744,3 +2746,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 #include "ellc_light_impl.hpp"
 #include "ellc_refine_impl.hpp"
 #include "ellc_sweep_impl.hpp"
+#include "ellc_cull_impl.hpp"

@@ -48,7 +48,14 @@
 //                    globalOptimize::sweepMatchDepth); PATH gets one line per push that had candidates: "frameId views n_ok n_swept
 //                    n_created n_no_valid_sample n_at_range_end n_cost_too_high n_not_distinct n_flat sum_views sum_cost". Without the
 //                    flag every output file is as before
-// --map FILE         (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
+// --cull-matches PATH  (LC mode, with --match-sim3 only: a usage error otherwise) behind the Sim(3) refinement, and behind
+//                    --refine-matches' step where both are given, the hypotheses of the pushed keyframe's ring map that its
+//                    candidates contradict at the inverted refined transforms and lights are removed (ellc_keyframe_cull_depth,
+//                    level 0, every hypothesis taking part, default parameters, into the keyframe's own ring slot;
+//                    globalOptimize::cullMatchDepth); PATH gets one line per push that had candidates: "frameId views n_kept
+//                    n_retained n_unseen n_culled_free_space n_culled_unsupported n_culled_photo sum_agree sum_in_front sum_behind
+//                    sum_photo sum_photo_bad". Without the flag every output file is as before
+// --map FILE        (LC mode) at the end of the run the ring's keyframes as one world-frame point cloud (globalOptimize::exportLocalMap:
 //                    level 0, no variance test, at least 3 supporting neighbours, support_k2 1, every pixel), written as binary PLY
 //                    (x y z float, intensity uchar, var float); every other file is unchanged
 // --render FILE      (LC mode) at the end of the run the ring's keyframes rendered into the view of the last pushed keyframe
@@ -88,7 +95,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--sweep-matches PATH] [--refine-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--sweep-matches PATH] [--refine-matches PATH] [--cull-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -98,7 +105,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false, match_light = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, match_geometry, match_sim3, refine_matches, sweep_matches, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
+  std::string comm_id_file, match_quality, match_geometry, match_sim3, refine_matches, sweep_matches, cull_matches, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -120,6 +127,7 @@ int main(int argc, char** argv) {
     else if (a == "--match-light") match_light = true;
     else if (a == "--refine-matches" && i + 1 < argc) refine_matches = argv[++i];
     else if (a == "--sweep-matches" && i + 1 < argc) sweep_matches = argv[++i];
+    else if (a == "--cull-matches" && i + 1 < argc) cull_matches = argv[++i];
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (a == "--fuse" && i + 1 < argc) fuse_file = argv[++i];
@@ -139,6 +147,10 @@ int main(int argc, char** argv) {
   }
   if (!sweep_matches.empty() && match_sim3.empty()) {
     std::fprintf(stderr, "--sweep-matches needs --match-sim3 PATH: the sweep runs at the transforms the Sim(3) refinement returns\n");
+    return -1;
+  }
+  if (!cull_matches.empty() && match_sim3.empty()) {
+    std::fprintf(stderr, "--cull-matches needs --match-sim3 PATH: the vote runs at the transforms the Sim(3) refinement returns\n");
     return -1;
   }
   if (!match_quality.empty() && world > 1) {
@@ -227,6 +239,11 @@ int main(int argc, char** argv) {
       globalOptimizeLoop->sweep_matches_file.open(sweep_matches.c_str());
       if (!globalOptimizeLoop->sweep_matches_file) { std::fprintf(stderr, "cannot open %s\n", sweep_matches.c_str()); return -1; }
       globalOptimizeLoop->sweepMatchDepth = true;
+    }
+    if (lc && !cull_matches.empty()) {
+      globalOptimizeLoop->cull_matches_file.open(cull_matches.c_str());
+      if (!globalOptimizeLoop->cull_matches_file) { std::fprintf(stderr, "cannot open %s\n", cull_matches.c_str()); return -1; }
+      globalOptimizeLoop->cullMatchDepth = true;
     }
     if (lc && !absorb_matches.empty()) {
       globalOptimizeLoop->absorb_file.open(absorb_matches.c_str());

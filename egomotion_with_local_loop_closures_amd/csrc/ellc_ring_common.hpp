@@ -1,5 +1,5 @@
 // The host scaffold of the calls over the keyframe ring's semi-dense maps (ellc_keyframe_map_points, _render_depth, _fuse_depth,
-// _depth_consistency, _sim3_step / _align, _light_step, _sim3_step_lit / _align_lit, _trial_propagate, _refine_depth, _sweep_depth, ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes): what they
+// _depth_consistency, _sim3_step / _align, _light_step, _sim3_step_lit / _align_lit, _trial_propagate, _refine_depth, _sweep_depth, _cull_depth, ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes): what they
 // refuse alike, the view map_keep reads, the timing window of the diagnostic hooks, grow-only buffers and the launch loop of the pair
 // reductions. Included at the end of ellc_hip.hip in front of the *_impl.hpp of those calls (the library is one translation unit).
 // A new call of the family supplies a record type with rec_zero / rec_add / rec_wave_sum (ellc_pair_reduce.hpp), a pass kernel and a

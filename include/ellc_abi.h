@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 21   /* ellc_keyframe_sweep_depth, ellc_sweep_default_params; 20: ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 22   /* ellc_keyframe_cull_depth, ellc_cull_default_params; 21: ellc_keyframe_sweep_depth, ellc_sweep_default_params; 20: ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -936,6 +936,82 @@ ellc_status ellc_keyframe_sweep_depth(ellc_ctx* ctx, int kf_slot, int level, int
                                       const float* T12, const float* light /* may be NULL */, const ellc_sweep_params* params,
                                       int dst_kf_slot, float* depth, float* var, uint8_t* views, uint8_t* status,
                                       ellc_sweep_stats* out /* each may be NULL */);
+
+/* ---- hypotheses the other views contradict, removed (v22) -----------------------------------------------------------
+ * The geometric consistency filter behind the steps above: the only call that REMOVES a hypothesis. Every kept pixel of keyframe slot
+ * kf_slot (K) is put to a vote of B other views, and a pixel the views contradict loses its hypothesis. K, `level`, the views,
+ * views_are_keyframes, T12, light and dst_kf_slot mean what they mean in ellc_keyframe_refine_depth: K's camera goes into view b's
+ * through T12 + 12 * b (a Sim(3)'s scale folded in), light + 2 * b is (gain, offset) with K as the source (NULL: (1, 0)). Slots may
+ * repeat and K may be among the views: K at the identity agrees with itself, which is the caller's business. A view's depth and
+ * variance planes on `level` are read iff views_are_keyframes == 1 and the slot holds a depth; every other view (a frame slot, or a
+ * keyframe slot with an image only) votes photometrically only and is no error. Per pixel of K, all arithmetic IEEE f32 in this
+ * order, no contraction, correctly rounded divisions:
+ *   1. TAKING PART. Iff ellc_keyframe_map_points would KEEP the pixel under `filter` (n_kept).
+ *   2. VOTES, the views in any order (every count is an integer). The candidate is ellc_keyframe_render_depth's for (px, py, Z0, V0)
+ *      at view b's T, with its drops: target, nid, u, v, nvar. A view without a candidate votes nothing.
+ *      GEOMETRIC VOTE, where the view has depth planes: steps 3-6 of ellc_keyframe_depth_consistency word for word. Zt and Vt are read
+ *      at the target; the vote takes part iff Zt > 0 && Zt <= FLT_MAX && Vt >= 0;  idt = 1 / Zt;  d = nid - idt;  s = nvar + Vt;
+ *      AGREE iff d * d <= agree_k2 * s; IN_FRONT iff it does not agree and d > 0 (the view sees through K's point); BEHIND otherwise
+ *      (the point is hidden in that view).
+ *      PHOTOMETRIC VOTE, iff photo_k > 0, the view's geometric vote was not BEHIND and the view has four taps (the four-tap condition
+ *      and Iw: rule 3 of ellc_keyframe_sim3_step):  rp = Iw - (gain * Is + offset);  e = |rp| * sp, sp = sqrtf(1 / sigma_i2) rounded
+ *      on the host as elsewhere. The view counts in n_photo, and in n_bad iff !(e <= photo_k).
+ *   3. DECISION, a / f / h the numbers of AGREE / IN_FRONT / BEHIND votes, in this order:
+ *        CULLED_FREE_SPACE   f >= min_in_front && f > a
+ *        CULLED_UNSUPPORTED  a + f + h >= min_judged && a < min_support
+ *        CULLED_PHOTO        photo_k > 0 && n_photo >= min_photo && 2 * n_bad > n_photo
+ *        UNSEEN              a + f + h == 0 && n_photo == 0 (the pixel is kept)
+ *        KEPT                otherwise
+ *   4. OUTPUTS (host pointers, dense cols x rows of the level, each may be NULL). A culled pixel gets depth 0.0f and var -1.0f,
+ *      ellc_keyframe_set_depth's "no hypothesis". Every other pixel keeps K's own depth and variance BITS (pixels not taking part and
+ *      K's inf / NaN / negative pixels included). votes = a | f << 8 | h << 16 | n_bad << 24; photo = n_photo; `status` is an
+ *      ellc_cull_status. No count can pass 64.
+ *   5. STATS. n_retained + n_unseen + n_culled_free_space + n_culled_unsupported + n_culled_photo == n_kept; the five sums add a, f,
+ *      h, n_photo and n_bad over the pixels taking part. Everything is an integer: nothing depends on an order of summation.
+ *   6. dst_kf_slot is -1 or a keyframe slot, at level 0 only, exactly as in ellc_keyframe_refine_depth: afterwards the slot is what
+ *      ellc_keyframe_set_depth(dst_kf_slot, depth, var) with the returned planes would leave. It may be K itself (the main use) or
+ *      a view: the kernel has read its inputs before the copy, in stream order.
+ *   The result is a function of the intrinsics, the level, K's three planes, the views' planes, the T's, the lights, the filter and
+ *   the params ALONE; cfg.arith, cfg.grid_batch, whatever else is in flight and the ORDER of the views do not enter it. A view in
+ *   which no point of K has a candidate changes no byte. A second call gives the same bytes.
+ *   Synchronous, ordered like every other non-batch entry point. A refused call changes nothing and writes nothing.
+ * The defaults {1, 16, 3, 1, 2, 1, 2} are DESIGN CHOICES, not measured optima: the agreement of ellc_keyframe_depth_consistency, the
+ * grey-value variance of the refinement, a residual of three sigma, one agreeing view among at least two that judge.
+ * ELLC_ERR_BAD_ARG, in this order: a NULL view_slots, T12, filter or params; B outside 1..ELLC_REFINE_MAX_VIEWS; views_are_keyframes
+ * outside 0..1; the level out of range or more than 2^24 pixels on it; the filter errors of ellc_keyframe_map_points; a value of T12
+ * or light that is not finite; agree_k2 negative or not finite, sigma_i2 <= 0, or a param that is not finite; min_support,
+ * min_in_front or min_photo outside 1..B, or min_judged outside 1..B; the destination errors of the fusion; a slot out of range.
+ * ELLC_ERR_NOT_READY: K without image or depth, a view without image. A keyframe view without depth is accepted. */
+typedef enum {
+  ELLC_CULL_NOT_TAKING_PART = 0,
+  ELLC_CULL_KEPT = 1,
+  ELLC_CULL_CULLED_FREE_SPACE = 2,
+  ELLC_CULL_CULLED_UNSUPPORTED = 3,
+  ELLC_CULL_CULLED_PHOTO = 4,
+  ELLC_CULL_UNSEEN = 5
+} ellc_cull_status;
+
+typedef struct {
+  float agree_k2;        /* >= 0: d * d <= agree_k2 * (nvar + Vt), as in ellc_keyframe_depth_consistency */
+  float sigma_i2;        /* > 0: variance of a grey value, as in ellc_refine_params */
+  float photo_k;         /* <= 0: no photometric vote; otherwise a view is bad iff !(|rp| / sigma_i <= photo_k) */
+  int   min_support;     /* 1..B: agreeing views a judged pixel needs */
+  int   min_judged;      /* 1..B: geometric votes from which the support test applies */
+  int   min_in_front;    /* 1..B: views that see through the point before free space culls it */
+  int   min_photo;       /* 1..B: photometric votes from which the photometric test applies */
+} ellc_cull_params;      /* 28 bytes */
+void ellc_cull_default_params(ellc_cull_params* params);   /* {1, 16, 3, 1, 2, 1, 2}: design choices */
+
+typedef struct {
+  int32_t n_kept;            /* pixels taking part: the sum of the five counts below */
+  int32_t n_retained, n_unseen, n_culled_free_space, n_culled_unsupported, n_culled_photo;
+  int64_t sum_agree, sum_in_front, sum_behind, sum_photo, sum_photo_bad;   /* over the pixels taking part (offset 24) */
+} ellc_cull_stats;           /* 64 bytes, every field naturally aligned */
+
+ellc_status ellc_keyframe_cull_depth(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                     const float* T12, const float* light /* may be NULL */, const ellc_map_filter* filter,
+                                     const ellc_cull_params* params, int dst_kf_slot, float* depth, float* var, uint32_t* votes,
+                                     uint8_t* photo, uint8_t* status, ellc_cull_stats* out /* each may be NULL */);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

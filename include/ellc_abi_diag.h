@@ -93,6 +93,13 @@ ellc_status ellc_profile_sweep_depth(ellc_ctx* ctx, int kf_slot, int level, int 
                                      const float* T12, const float* light, const ellc_sweep_params* params, int dst_kf_slot, float* depth,
                                      float* var, uint8_t* views, uint8_t* status, ellc_sweep_stats* out, float* launches_ms);
 
+/* ellc_keyframe_cull_depth with HIP events around its launches (cull_pixels, cull_finish): launches_ms receives their device time,
+ * without the staging copy in front and the downloads behind. Everything else as the product call. */
+ellc_status ellc_profile_cull_depth(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                    const float* T12, const float* light, const ellc_map_filter* filter, const ellc_cull_params* params,
+                                    int dst_kf_slot, float* depth, float* var, uint32_t* votes, uint8_t* photo, uint8_t* status,
+                                    ellc_cull_stats* out, float* launches_ms);
+
 /* Counter calibration: stream `bytes` of device memory once per launch with 4-byte-per-lane loads (the access
  * width of the compacted pixel arrays), `reps` launches, so FETCH_SIZE can be scaled against a known byte count
  * (MI355X_MICROARCH.md, HBM section). Returns average milliseconds per launch. */

@@ -486,6 +486,17 @@ class globalOptimize {
   ellc_sweep_stats lastSweepStats = ellc_sweep_stats();
   int lastSweepViews = 0;
   std::ofstream sweep_matches_file;
+  // The consistency filter behind that refinement (ellc_keyframe_cull_depth; off by default: nothing changes; it needs refineMatchSim3,
+  // with or without matchAffineLight, sweepMatchDepth and refineMatchDepth): the hypotheses of the pushed keyframe's ring map that the
+  // same views at the same inverted transforms and lights contradict are removed - level 0, the no-op filter {0, 0, 1, 1}, the default
+  // ellc_cull_params with the four counts lowered to min(default, views), the keyframe's own ring slot as the destination - AFTER
+  // refineMatchDepth ran, where both are asked for. lastCullStats / lastCullViews keep the record (zeros: no candidates) and
+  // cull_matches_file (when open) gets "frameId views n_kept n_retained n_unseen n_culled_free_space n_culled_unsupported
+  // n_culled_photo sum_agree sum_in_front sum_behind sum_photo sum_photo_bad" per push that had candidates. The ring copy alone is touched.
+  bool cullMatchDepth = false;
+  ellc_cull_stats lastCullStats = ellc_cull_stats();
+  int lastCullViews = 0;
+  std::ofstream cull_matches_file;
   // What a closed loop teaches, kept in the TRACKING context (ellc_depth_absorb_keyframes): every candidate of the push's batch is folded
   // into the live depth map of the pushed keyframe at its refined Sim(3). Off by default: nothing changes. On: pushToArray runs
   // findMatchParallel synchronously with the Sim(3) refinement, copies the ring slot of every entry of lastMatchSim3 into the tracking
@@ -961,6 +972,8 @@ class globalOptimize {
     lastRefineViews = 0;
     lastSweepStats = ellc_sweep_stats();
     lastSweepViews = 0;
+    lastCullStats = ellc_cull_stats();
+    lastCullViews = 0;
     loopFrameArray[nextArrayId].frameId = testFrame.frameId;
     lastTestedLoopClosureArrayId = -1;
     firstTestedLoopClosureArrayId = -1;
@@ -1091,10 +1104,10 @@ class globalOptimize {
           q.offset = light[(size_t)b * 2 + 1];
         }
       }
-      // the views of the two structure steps: the candidates' ring slots, each at the INVERSE of its refined transform and light
+      // the views of the three structure steps: the candidates' ring slots, each at the INVERSE of its refined transform and light
       const int V = std::min(B, (int)ELLC_REFINE_MAX_VIEWS);
       std::vector<float> T, light;
-      if (refineMatchSim3 && (sweepMatchDepth || refineMatchDepth)) {
+      if (refineMatchSim3 && (sweepMatchDepth || refineMatchDepth || cullMatchDepth)) {
         T.resize((size_t)V * 12); light.resize((size_t)V * 2);
         for (int b = 0; b < V; b++) {
           const MatchSim3& q = lastMatchSim3[(size_t)b];
@@ -1136,6 +1149,28 @@ class globalOptimize {
                               << " " << r.n_too_few_views << " " << r.n_no_information << " " << r.n_bad_step << " " << r.n_views_changed << " "
                               << r.n_cost_rose << " " << r.sum_views << " " << r.sum_cost_before << " " << r.sum_cost_after << "\n";
           refine_matches_file.flush();
+        }
+      }
+      if (refineMatchSim3 && cullMatchDepth) {
+        ellc_map_filter filter;   // every hypothesis takes part
+        filter.max_var = 0.0f; filter.min_support = 0; filter.support_k2 = 1.0f; filter.stride = 1;
+        ellc_cull_params params;
+        ellc_cull_default_params(&params);
+        params.min_support = std::min(params.min_support, V);
+        params.min_judged = std::min(params.min_judged, V);
+        params.min_in_front = std::min(params.min_in_front, V);
+        params.min_photo = std::min(params.min_photo, V);
+        lastCullStats = ellc_cull_stats();
+        lastCullViews = V;
+        ring.check(ellc_keyframe_cull_depth(ring.ctx, testFrame.ring_slot, 0, V, 1, kf.data(), T.data(), light.data(), &filter, &params,
+                                            testFrame.ring_slot, nullptr, nullptr, nullptr, nullptr, nullptr, &lastCullStats),
+                   "ellc_keyframe_cull_depth");
+        if (cull_matches_file.is_open()) {
+          const ellc_cull_stats& r = lastCullStats;
+          cull_matches_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << V << " " << r.n_kept << " " << r.n_retained << " " << r.n_unseen << " "
+                            << r.n_culled_free_space << " " << r.n_culled_unsupported << " " << r.n_culled_photo << " " << r.sum_agree << " "
+                            << r.sum_in_front << " " << r.sum_behind << " " << r.sum_photo << " " << r.sum_photo_bad << "\n";
+          cull_matches_file.flush();
         }
       }
       for (int b = 0; b < B; b++) {
