@@ -39,6 +39,7 @@ DIAG_SYMBOLS = [
     "ellc_profile_gn_kernel", "ellc_profile_align", "ellc_profile_depth_stage", "ellc_profile_calibrate_read", "ellc_profile_stream_read",
     "ellc_selftest_div_pair", "ellc_selftest_lu", "ellc_debug_persist_delay", "ellc_debug_set_persist_epoch", "ellc_debug_persist_counters", "ellc_debug_set_eager_lists", "ellc_debug_set_hinv_cache", "ellc_debug_set_fold_staging",
     "ellc_debug_set_count_cache", "ellc_debug_count_cache_counters", "ellc_debug_set_packed_taps", "ellc_debug_row_tap_launches", "ellc_debug_get_packed_level",
+    "ellc_debug_set_mask_scatter", "ellc_debug_mask_scatter_counters", "ellc_debug_get_valid_mask",
     "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_fuse_depth", "ellc_profile_depth_absorb", "ellc_profile_trial_propagate", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
     "ellc_profile_light_step", "ellc_profile_sim3_step_lit", "ellc_profile_refine_depth", "ellc_profile_sweep_depth", "ellc_profile_cull_depth",
 ]

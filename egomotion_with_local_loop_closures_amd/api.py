@@ -683,6 +683,27 @@ class Context:
         self._need_diag("ellc_debug_set_count_cache")
         self._ck(self._l.ellc_debug_set_count_cache(self.h, int(bool(on))), "ellc_debug_set_count_cache")
 
+    def debug_set_mask_scatter(self, on):
+        """1 (default): a launch group's compaction ranks its pixels from the kept valid-bit masks; 0: from the depth planes."""
+        self._need_diag("ellc_debug_set_mask_scatter")
+        self._ck(self._l.ellc_debug_set_mask_scatter(self.h, int(bool(on))), "ellc_debug_set_mask_scatter")
+
+    def debug_mask_scatter_counters(self):
+        """(scatter launches in the masked form, in the depth-reading form behind a count) enqueued or captured so far."""
+        self._need_diag("ellc_debug_mask_scatter_counters")
+        a = C.c_longlong(0); b = C.c_longlong(0)
+        self._ck(self._l.ellc_debug_mask_scatter_counters(self.h, C.byref(a), C.byref(b)), "ellc_debug_mask_scatter_counters")
+        return a.value, b.value
+
+    def debug_get_valid_mask(self, kf_slot, level):
+        """The valid-bit mask the last count launch left for a keyframe slot at `level`: a (tiles, 64) uint32 array, bit i of a
+        tile = (depth > 0) of pixel tile * 2048 + i."""
+        self._need_diag("ellc_debug_get_valid_mask")
+        tiles = ((self.cfg.height >> level) * (self.cfg.width >> level) + 2047) // 2048
+        out = np.zeros((tiles, 64), np.uint32)
+        self._ck(self._l.ellc_debug_get_valid_mask(self.h, int(kf_slot), int(level), out.ctypes.data_as(C.c_void_p)), "ellc_debug_get_valid_mask")
+        return out
+
     def debug_set_packed_taps(self, on):
         """Tolerance mode: 1 (default) the interior taps as one load from the row-packed plane, 0 as four row loads."""
         self._need_diag("ellc_debug_set_packed_taps")

@@ -47,6 +47,8 @@ struct LaunchPlan {
   int count_n = 0;                     //     (the plane's size; 0: none)
   bool row_taps = false;      // diagnostic library only (ellc_debug_set_packed_taps): the tolerance mode's interior taps as four row loads from
                               // FrLevelDev::img, not one load from the row-packed plane (GnArgs::row_taps)
+  bool depth_scatter = false; // diagnostic library only (ellc_debug_set_mask_scatter(0)): the compaction of a launch group ranks its pixels
+                              // from the depth planes, not from the valid-bit masks kept with the tile counts (prep_scatter<NEED, false>)
 };
 
 // ellc_track_frame's request to align_enqueue_impl: the alignment is its own (LaunchPlan::track), and the count it would like taken along
@@ -58,16 +60,16 @@ struct TrackRequest {
 // What tells one captured launch sequence from another: the plan's members that change what is captured, and cfg.grid_batch (the
 // grids). resident, direct and the count request are absent: such sequences are never captured.
 struct GraphKey {
-  int B, nu, mode, save_weights, continuation, track, pollable, adaptive_first, grid_batch, dense, need, skip_count, set, row_taps;
+  int B, nu, mode, save_weights, continuation, track, pollable, adaptive_first, grid_batch, dense, need, skip_count, set, row_taps, depth_scatter;
   bool operator<(const GraphKey& o) const {
     auto t = [](const GraphKey& k) {
-      return std::tie(k.B, k.nu, k.mode, k.save_weights, k.continuation, k.track, k.pollable, k.adaptive_first, k.grid_batch, k.dense, k.need, k.skip_count, k.set, k.row_taps);
+      return std::tie(k.B, k.nu, k.mode, k.save_weights, k.continuation, k.track, k.pollable, k.adaptive_first, k.grid_batch, k.dense, k.need, k.skip_count, k.set, k.row_taps, k.depth_scatter);
     };
     return t(*this) < t(o);
   }
 };
 inline GraphKey graph_key(const LaunchPlan& p, int grid_batch) {
-  return GraphKey{p.B, p.nu, p.mode, p.save_weights ? 1 : 0, p.continuation, p.track, p.pollable, p.adaptive_first, grid_batch, p.dense, p.need, p.skip_count, p.set, p.row_taps};
+  return GraphKey{p.B, p.nu, p.mode, p.save_weights ? 1 : 0, p.continuation, p.track, p.pollable, p.adaptive_first, grid_batch, p.dense, p.need, p.skip_count, p.set, p.row_taps, p.depth_scatter};
 }
 
 // Staging and scratch of a call that reduces B (source, destination) pairs to one record each (ellc_ring_common.hpp: pair_reserve,
@@ -128,9 +130,14 @@ struct ellc_ctx {
   // integers depend on the depth planes alone. kf_counts_ok[slot]: KfLevelDev::tile_count of every level of the slot holds the plain
   // counts a prep_count launch left, and the depth planes have not been written since (every writer clears it through
   // invalidate_records; the count-free form, which stores tagged words there, clears it too): a group whose rebuilt slots all
-  // carry the mark launches prep_scatter alone, which reads the kept counts as it reads fresh ones
+  // carry the mark launches prep_scatter alone, which reads the kept counts as it reads fresh ones.
+  // Behind the counts, in the same allocation, prep_count leaves one valid bit per pixel (prep_mask_offset): same inputs, same only
+  // writer, so the same mark covers it. prep_scatter of a launch group ranks its pixels from those bits and never reads a depth
+  // plane for its validity.
   std::vector<char> kf_counts_ok;
   bool count_cache = true;
+  bool depth_scatter = false;   // ellc_debug_set_mask_scatter(0), diagnostic library only: see LaunchPlan::depth_scatter
+  long long scatters_masked = 0, scatters_from_depth = 0;   //   scatter launches behind a count, enqueued or captured, of either form (ellc_debug_mask_scatter_counters)
   long long groups_counted = 0, groups_count_skipped = 0;   // groups launch_group launched with / without a count launch (those that compact at all; the count-free form is neither)
   bool cache_records = false;
   std::vector<std::array<int, ELLC_MAX_LEVELS>> kf_num_weights;

@@ -347,15 +347,28 @@ ellc_status run_prep_levels(ellc_ctx* c, const LaunchPlan& p, int lvl_lo, int lv
   } else if (!p.skip_count) {   // (skip_count: the counts an earlier launch left in the slots are current, launch_group)
     hipLaunchKernelGGL(prep_count, dim3(tiles, n_unique), dim3(256), 0, st, a);
   }
+  // with a count launch in front of it, now or earlier (kf_counts_ok), the scatter ranks its pixels from the mask that launch left;
+  // the count-free form reads the depth planes
+  bool mask = a.lb_tag == 0;
+#ifdef ELLC_DIAG_ABI
+  mask = mask && !p.depth_scatter;   // (the tests' second source: ellc_debug_set_mask_scatter)
+  if (a.lb_tag == 0) (mask ? c->scatters_masked : c->scatters_from_depth)++;
+#endif
+#define ELLC_SCATTER(NEED)                                                                                      \
+  case NEED:                                                                                                    \
+    if (mask) hipLaunchKernelGGL((prep_scatter<NEED, true>), dim3(tiles, n_unique), dim3(256), 0, st, a);       \
+    else hipLaunchKernelGGL((prep_scatter<NEED, false>), dim3(tiles, n_unique), dim3(256), 0, st, a);           \
+    break;
   switch (p.need) {
-    case 1: hipLaunchKernelGGL(prep_scatter<1>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(prep_scatter<2>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;
-    case 4: hipLaunchKernelGGL(prep_scatter<4>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;
-    case 20: hipLaunchKernelGGL(prep_scatter<20>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL(prep_scatter<16>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;   // fast ICA records only: the slots' H^-1 are current
-    case 8: hipLaunchKernelGGL(prep_scatter<8>, dim3(tiles, n_unique), dim3(256), 0, st, a); break;
+    ELLC_SCATTER(1)
+    ELLC_SCATTER(2)
+    ELLC_SCATTER(4)
+    ELLC_SCATTER(20)
+    ELLC_SCATTER(16)   // fast ICA records only: the slots' H^-1 are current
+    ELLC_SCATTER(8)
     default: return fail(c, ELLC_ERR_BAD_ARG, "run_prep: unknown record set");
   }
+#undef ELLC_SCATTER
   ELLC_HIP(c, hipGetLastError());
   return ELLC_OK;
 }
@@ -705,8 +718,8 @@ ellc_status enqueue_eager_lists(ellc_ctx* c, int slot) {
   a.slot_inline = slot;
   c->prep_tag = c->prep_tag % 0xfffffu + 1u;
   a.lb_tag = c->prep_tag;
-  if (need == 8) hipLaunchKernelGGL(prep_scatter<8>, dim3(tiles, 1), dim3(256), 0, c->stream, a);
-  else if (need == 2) hipLaunchKernelGGL(prep_scatter<2>, dim3(tiles, 1), dim3(256), 0, c->stream, a);
+  if (need == 8) hipLaunchKernelGGL((prep_scatter<8, false>), dim3(tiles, 1), dim3(256), 0, c->stream, a);
+  else if (need == 2) hipLaunchKernelGGL((prep_scatter<2, false>), dim3(tiles, 1), dim3(256), 0, c->stream, a);
   else return ELLC_OK;
   ELLC_HIP(c, hipGetLastError());
   c->kf_counts_ok[slot] = 0;   // (tagged words in the slot's tile counts; the export that precedes this call has cleared it already)
@@ -1046,7 +1059,7 @@ ellc_status ellc_ctx_create(const ellc_config* cfg, ellc_ctx** out) {
       TRY(dev_alloc(c, &k.depth, n)); TRY(dev_alloc(c, &k.var, n)); TRY(dev_alloc(c, &k.weight, n));
       TRY(dev_alloc(c, &k.cxy, n)); TRY(dev_alloc(c, &k.cZ, n)); TRY(dev_alloc(c, &k.cI, n));
       TRY(dev_alloc(c, &k.crec, n)); TRY(dev_alloc(c, &k.cW, n)); TRY(dev_alloc(c, &k.wlast, n)); TRY(dev_alloc(c, &k.sd, 6 * n));
-      TRY(dev_alloc(c, &k.count, 4)); TRY(dev_alloc(c, &k.tile_count, tiles + 1)); TRY(dev_alloc(c, &k.idepth, n));
+      TRY(dev_alloc(c, &k.count, 4)); TRY(dev_alloc(c, &k.tile_count, prep_count_words(tiles))); TRY(dev_alloc(c, &k.idepth, n));   // (counts, then the valid-bit masks: prep_mask_offset)
       k.invz = nullptr;
       if (!c->fast) TRY(dev_alloc(c, &k.invz, n));   // (the exact mode's list-free kernel: KfLevelDev::invz)
       TRY(dev_alloc(c, &k.irec, n)); TRY(dev_alloc(c, &k.hpart, (size_t)(tiles + 1) * ELLC_PART_STRIDE)); TRY(dev_alloc(c, &k.hinv, 36));
@@ -1335,6 +1348,30 @@ ellc_status ellc_debug_set_count_cache(ellc_ctx* c, int on) {
   if (!c) return ELLC_ERR_BAD_ARG;
   ELLC_ENTER(c);
   c->count_cache = on != 0;
+  return ELLC_OK;
+}
+ellc_status ellc_debug_set_mask_scatter(ellc_ctx* c, int on) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  ELLC_ENTER(c);
+  c->depth_scatter = !on;   // (read by make_plan and the diagnostic plans: LaunchPlan::depth_scatter)
+  return ELLC_OK;
+}
+ellc_status ellc_debug_mask_scatter_counters(ellc_ctx* c, long long* masked, long long* from_depth) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  ELLC_ENTER(c);
+  if (masked) *masked = c->scatters_masked;
+  if (from_depth) *from_depth = c->scatters_from_depth;
+  return ELLC_OK;
+}
+ellc_status ellc_debug_get_valid_mask(ellc_ctx* c, int kf_slot, int level, uint32_t* out) {
+  if (!c || !out || level < 0 || level >= c->L || !slot_ok(kf_slot, c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, "bad argument");
+  ELLC_ENTER(c);
+  if (c->n_inflight > 0 || c->open_set >= 0) return fail(c, ELLC_ERR_NOT_READY, "ellc_debug_get_valid_mask: fetch the enqueued batches first");
+  if (!c->kf_counts_ok[kf_slot]) return fail(c, ELLC_ERR_NOT_READY, "ellc_debug_get_valid_mask: the slot's counts and mask are stale (no count launch since its depth planes were written)");
+  const int tiles = c->tile_begin[level + 1] - c->tile_begin[level];
+  const int* words = c->kf_tab_h[(size_t)level * c->cfg.max_keyframes + kf_slot].tile_count + prep_mask_offset(tiles);
+  ELLC_HIP(c, hipMemcpyAsync(out, words, (size_t)tiles * ELLC_MASK_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
   return ELLC_OK;
 }
 ellc_status ellc_debug_set_packed_taps(ellc_ctx* c, int on) {
@@ -1754,6 +1791,7 @@ static LaunchPlan make_plan(const ellc_ctx* c, int B, int nu, int mode, int save
   p.adaptive_first = schedule_is_adaptive(c, mode, B) ? adaptive_first_launches(c, resident) : 0;   // (it varies with the context's hint)
   p.direct = launches_directly(c, mode, B);
   p.row_taps = c->row_taps;
+  p.depth_scatter = c->depth_scatter;
   return p;
 }
 
@@ -2224,7 +2262,8 @@ ellc_status ellc_gn_iterate(ellc_ctx* c, int kf_slot, int frame_slot, int level,
   if (s != ELLC_OK) return s;
   LaunchPlan plan;   // (not a production sequence: staged through the pinned record, with a count launch)
   plan.row_taps = c->row_taps;
-  plan.B = 1;
+  plan.depth_scatter = c->depth_scatter;
+  plan.B =1;
   plan.nu = nu;
   plan.mode = mode;
   plan.need = mode == ELLC_MODE_ICA ? 1 : (c->fast ? 8 : 2);   // the single-step API builds its own record set
@@ -2356,7 +2395,8 @@ ellc_status ellc_gn_display_planes(ellc_ctx* c, int kf_slot, int frame_slot, int
   if (s != ELLC_OK) return s;
   LaunchPlan plan;
   plan.row_taps = c->row_taps;
-  plan.B = 1;
+  plan.depth_scatter = c->depth_scatter;
+  plan.B =1;
   enqueue_stage_in(c, plan, 0);   // staging only
   hipLaunchKernelGGL(gn_set_pose0, dim3(1), dim3(1), 0, c->stream, c->state_d, c->init_pose_d);
   const LevelGeom& g = c->geom_h[level];
@@ -2417,7 +2457,8 @@ ellc_status ellc_profile_gn_kernel(ellc_ctx* c, int B, const int* kf_slots, cons
   const bool dense = group_is_dense(c, ELLC_MODE_FCA, B, 0, kf_slots, B);
   LaunchPlan plan;   // (staged through the pinned record, with a count launch, whatever the production sequence would do)
   plan.row_taps = c->row_taps;
-  plan.B = B;
+  plan.depth_scatter = c->depth_scatter;
+  plan.B =B;
   plan.nu = dense ? 0 : nu;
   plan.dense = dense;
   plan.need = c->fast ? 8 : 2;

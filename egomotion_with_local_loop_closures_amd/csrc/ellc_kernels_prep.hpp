@@ -12,6 +12,12 @@ namespace ellc {
 // Compaction of the keyframe's valid pixels (mask = depth_pyramid[l] > 0, Frame.cpp:295-301), raster
 // order preserved. Two launches (count per tile, then scatter) cover all levels of all listed keyframe slots.
 #define ELLC_TILE 2048          // pixels per block: 256 threads x 8 consecutive pixels (two float4 loads)
+// The valid-bit mask of a level lives behind its tile counts in KfLevelDev::tile_count: ELLC_MASK_WORDS words per tile, bit i of a tile
+// = (depth > 0) of pixel local * ELLC_TILE + i, zeros past the end of the plane. prep_count is its only writer, so it is current
+// exactly when the counts are (ellc_ctx::kf_counts_ok). `tiles`: the level's tile count; the offset keeps the words 16-byte aligned.
+#define ELLC_MASK_WORDS (ELLC_TILE / 32)
+__host__ __device__ __forceinline__ constexpr int prep_mask_offset(int tiles) { return (tiles + 1 + 3) & ~3; }
+__host__ __device__ __forceinline__ constexpr int prep_count_words(int tiles) { return prep_mask_offset(tiles) + tiles * ELLC_MASK_WORDS; }
 
 struct PrepArgs {
   const LevelGeom* geom;
@@ -25,7 +31,7 @@ struct PrepArgs {
   int tile_begin[ELLC_MAX_LEVELS + 1];   // prefix of tiles per level
   int tile0, level0;           // this launch covers tiles tile0 + blockIdx.x (count / scatter), levels level0 + blockIdx.x (scan)
   int slot_inline;             // the slot itself when `slots` is null (one keyframe; a scalar: a dynamically indexed member would send the whole argument struct through private memory)
-  unsigned lb_tag;             // 0: prep_count has left the tiles' counts. Else (r05, the tracking call: one or two keyframes, launched
+  unsigned lb_tag;             // 0: prep_count has left the tiles' counts and valid-bit masks (prep_scatter<NEED, true> ranks from them). Else (r05, the tracking call: one or two keyframes, launched
                                // kernel by kernel) there is NO count launch: a scatter block publishes `lb_tag << 12 | its tile's count`
                                // as soon as it has it and sums the tagged counts of the tiles of its level in front of it as they
                                // appear (agent-scope stores / loads, no fence; blocks are dispatched in tile order, so the tiles a block
@@ -77,9 +83,17 @@ __global__ __launch_bounds__(256) void prep_count(PrepArgs a) {
   const int i0 = local * ELLC_TILE + threadIdx.x * 8;
   float d[8];
   prep_load8(K.depth, i0, n, d);
-  int c = 0;
+  uint32_t bits = 0u;   // this thread's eight consecutive pixels: one byte of the tile's mask
 #pragma unroll
-  for (int j = 0; j < 8; j++) c += (d[j] > 0.0f) ? 1 : 0;
+  for (int j = 0; j < 8; j++) bits |= (d[j] > 0.0f) ? (1u << j) : 0u;
+  const int c = __popc(bits);
+  {   // four lanes' bytes make a word: a wave stores 16 words
+    uint32_t w = bits << (8 * (threadIdx.x & 3));
+    w |= (uint32_t)__shfl_xor((int)w, 1, 64);
+    w |= (uint32_t)__shfl_xor((int)w, 2, 64);
+    const int T = a.tile_begin[level + 1] - a.tile_begin[level];
+    if ((threadIdx.x & 3) == 0) ((uint32_t*)K.tile_count)[prep_mask_offset(T) + local * ELLC_MASK_WORDS + (int)(threadIdx.x >> 2)] = w;
+  }
   __shared__ int ws[4];
   int tot;
   wave_inclusive_scan(c, tot);
@@ -96,7 +110,13 @@ __global__ __launch_bounds__(256) void prep_count(PrepArgs a) {
 // parked entries — every lane has a valid pixel — computes the record (three IEEE divisions) and stores it; consecutive
 // lanes write consecutive records. Without the LDS step the divisions would run for every wave that holds at least one
 // valid pixel, i.e. about four times as often on a semi-dense map.
-template <int NEED>   // compile-time copy of PrepArgs::need: the FCA variant carries no Jacobian / H-sum code (and registers)
+//
+// MASK (launch groups, lb_tag == 0): phase 1 reads no depth. Thread t owns byte t of the tile's valid-bit mask (prep_mask_offset) —
+// eight consecutive pixels in raster order — ranks it by a block scan of the popcounts and parks its valid pixel indices; the order
+// is the raster order again, hence the same records at the same positions. Phase 2 gathers the depth where it gathers the variance:
+// 256 B of mask per tile instead of 8 KB of depth, one dependent memory round trip and 8 KB of LDS less. The count-free form
+// (lb_tag != 0) has no count launch that could have left a mask and keeps the depth-reading phase 1 (MASK = false).
+template <int NEED, bool MASK>   // NEED: compile-time copy of PrepArgs::need: the FCA variant carries no Jacobian / H-sum code (and registers)
 __global__ __launch_bounds__(256) void prep_scatter(PrepArgs a) {
   int local;
   const int level = prep_level_of(a, a.tile0 + (int)blockIdx.x, local);
@@ -105,70 +125,98 @@ __global__ __launch_bounds__(256) void prep_scatter(PrepArgs a) {
   const int n = g.n;
   const int base = local * ELLC_TILE + (int)threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ int cnt[33];   // [j][wave] exclusive offsets, [32] = tile total
+  __shared__ int cnt[33];   // [j][wave] exclusive offsets, [32] = tile total (MASK: [wave] the waves' totals)
   __shared__ int before[4]; // per wave: valid pixels in the tiles of this level that precede this one
   __shared__ uint32_t s_idx[ELLC_TILE];
-  __shared__ float s_Z[ELLC_TILE];
-  // the eight depth loads first, then the loads of the tile counts: both sets are in flight together (r03: a block's life is a
-  // chain of memory round trips of 2-3 us each under load — table entry, counts, depths, gathers, stores: 12 us for 2048 pixels)
-  float d[8];
+  __shared__ float s_Z[MASK ? 1 : ELLC_TILE];
+  int nvalid;
+  if constexpr (MASK) {
+    const int T = a.tile_begin[level + 1] - a.tile_begin[level];
+    const ELLC_GLOBAL uint8_t* mbytes = (const ELLC_GLOBAL uint8_t*)(gptr(K.tile_count) + (unsigned)(prep_mask_offset(T) + local * ELLC_MASK_WORDS));
+    uint32_t bits = mbytes[threadIdx.x];
+    {   // this tile's offset in the level's list = sum of the counts prep_count left for the tiles before it (at most a few hundred)
+      int part = 0, tot;
+      for (int i = (int)threadIdx.x; i < local; i += 256) part += gptr(K.tile_count)[(unsigned)i];
+      wave_inclusive_scan(part, tot);
+      if (lane == 0) before[wave] = tot;
+    }
+    const int c = __popc(bits);
+    int wtot;
+    int r = wave_inclusive_scan(c, wtot) - c;
+    if (lane == 0) cnt[wave] = wtot;
+    __syncthreads();
+    const int w0 = cnt[0], w1 = cnt[1], w2 = cnt[2], w3 = cnt[3];
+    r += (wave > 0 ? w0 : 0) + (wave > 1 ? w1 : 0) + (wave > 2 ? w2 : 0);
+    nvalid = w0 + w1 + w2 + w3;
+    const uint32_t i0 = (uint32_t)(local * ELLC_TILE) + threadIdx.x * 8u;
+    while (bits) {
+      const int j = __builtin_ctz(bits);
+      bits &= bits - 1u;
+      s_idx[r++] = i0 + (uint32_t)j;
+    }
+    __syncthreads();
+  } else {
+    // the eight depth loads first, then the loads of the tile counts: both sets are in flight together (r03: a block's life is a
+    // chain of memory round trips of 2-3 us each under load — table entry, counts, depths, gathers, stores: 12 us for 2048 pixels)
+    float d[8];
 #pragma unroll
-  for (int j = 0; j < 8; j++) {
-    const int i = base + j * 256;
-    d[j] = (i < n) ? gptr(K.depth)[(unsigned)i] : 0.0f;
-  }
-  if (!a.lb_tag) {   // this tile's offset in the level's list = sum of the counts prep_count left for the tiles before it (at most a few hundred)
-    int part = 0, tot;
-    for (int i = (int)threadIdx.x; i < local; i += 256) part += gptr(K.tile_count)[(unsigned)i];
-    wave_inclusive_scan(part, tot);
-    if (lane == 0) before[wave] = tot;
-  }
-  unsigned long long m[8];
+    for (int j = 0; j < 8; j++) {
+      const int i = base + j * 256;
+      d[j] = (i < n) ? gptr(K.depth)[(unsigned)i] : 0.0f;
+    }
+    if (!a.lb_tag) {   // this tile's offset in the level's list = sum of the counts prep_count left for the tiles before it (at most a few hundred)
+      int part = 0, tot;
+      for (int i = (int)threadIdx.x; i < local; i += 256) part += gptr(K.tile_count)[(unsigned)i];
+      wave_inclusive_scan(part, tot);
+      if (lane == 0) before[wave] = tot;
+    }
+    unsigned long long m[8];
 #pragma unroll
-  for (int j = 0; j < 8; j++) {
-    m[j] = __ballot(d[j] > 0.0f);
-    if (lane == 0) cnt[j * 4 + wave] = __popcll(m[j]);
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {   // exclusive scan of the 32 (j, wave) counts
-    int v = (lane < 32) ? cnt[lane] : 0, tot;
-    const int inc = wave_inclusive_scan(v, tot);
-    if (lane < 32) cnt[lane] = inc - v;
-    if (lane == 0) cnt[32] = tot;
-  }
-  __syncthreads();
-  if (a.lb_tag) {   // block-uniform: see PrepArgs::lb_tag
-    const unsigned tag = a.lb_tag << 12;
-    unsigned* tc = (unsigned*)K.tile_count;
-    if (threadIdx.x == 0) __hip_atomic_store(tc + local, tag | (unsigned)cnt[32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int part = 0, tot;
-    for (int i = (int)threadIdx.x; i < local; i += 256) {
-      unsigned w = 0u, polls = 0u;
-      do { w = __hip_atomic_load(tc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((w & 0xfffff000u) != tag && ++polls < 4096u);
-      if ((w & 0xfffff000u) == tag) {
-        part += (int)(w & 0xfffu);
-      } else {   // (does not happen with blocks dispatched in tile order; a count is a function of the plane: no wait can be endless)
-        const int e0 = i * ELLC_TILE, e1 = min(n, e0 + ELLC_TILE);
-        int cnt_i = 0;
-        for (int e = e0; e < e1; e++) cnt_i += (gptr(K.depth)[(unsigned)e] > 0.0f) ? 1 : 0;
-        part += cnt_i;
+    for (int j = 0; j < 8; j++) {
+      m[j] = __ballot(d[j] > 0.0f);
+      if (lane == 0) cnt[j * 4 + wave] = __popcll(m[j]);
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {   // exclusive scan of the 32 (j, wave) counts
+      int v = (lane < 32) ? cnt[lane] : 0, tot;
+      const int inc = wave_inclusive_scan(v, tot);
+      if (lane < 32) cnt[lane] = inc - v;
+      if (lane == 0) cnt[32] = tot;
+    }
+    __syncthreads();
+    if (a.lb_tag) {   // block-uniform: see PrepArgs::lb_tag
+      const unsigned tag = a.lb_tag << 12;
+      unsigned* tc = (unsigned*)K.tile_count;
+      if (threadIdx.x == 0) __hip_atomic_store(tc + local, tag | (unsigned)cnt[32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      int part = 0, tot;
+      for (int i = (int)threadIdx.x; i < local; i += 256) {
+        unsigned w = 0u, polls = 0u;
+        do { w = __hip_atomic_load(tc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((w & 0xfffff000u) != tag && ++polls < 4096u);
+        if ((w & 0xfffff000u) == tag) {
+          part += (int)(w & 0xfffu);
+        } else {   // (does not happen with blocks dispatched in tile order; a count is a function of the plane: no wait can be endless)
+          const int e0 = i * ELLC_TILE, e1 = min(n, e0 + ELLC_TILE);
+          int cnt_i = 0;
+          for (int e = e0; e < e1; e++) cnt_i += (gptr(K.depth)[(unsigned)e] > 0.0f) ? 1 : 0;
+          part += cnt_i;
+        }
+      }
+      wave_inclusive_scan(part, tot);
+      if (lane == 0) before[wave] = tot;
+      __syncthreads();
+    }
+    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      if (d[j] > 0.0f) {
+        const int r = cnt[j * 4 + wave] + __popcll(m[j] & lt);
+        s_idx[r] = (uint32_t)(base + j * 256);
+        s_Z[r] = d[j];
       }
     }
-    wave_inclusive_scan(part, tot);
-    if (lane == 0) before[wave] = tot;
     __syncthreads();
+    nvalid = cnt[32];
   }
-  const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    if (d[j] > 0.0f) {
-      const int r = cnt[j * 4 + wave] + __popcll(m[j] & lt);
-      s_idx[r] = (uint32_t)(base + j * 256);
-      s_Z[r] = d[j];
-    }
-  }
-  __syncthreads();
-  const int nvalid = cnt[32];
   const unsigned tile_off = (unsigned)(before[0] + before[1] + before[2] + before[3]);
   if (threadIdx.x == 0 && local == a.tile_begin[level + 1] - a.tile_begin[level] - 1) *K.count = (int)tile_off + nvalid;   // last tile: the level's total
   const float inv_cols = 1.0f / (float)g.cols;
@@ -209,7 +257,7 @@ __global__ __launch_bounds__(256) void prep_scatter(PrepArgs a) {
         act[k] = r < nvalid;
         const int rr = act[k] ? r : 0;   // (an idle lane reads entry 0: a valid address, nothing is stored)
         ii[k] = (int)s_idx[rr];
-        ZZ[k] = s_Z[rr];
+        if constexpr (!MASK) ZZ[k] = s_Z[rr];
         int y = (int)(((float)ii[k] + 0.5f) * inv_cols);   // i < 2^24: exact conversion; corrected below
         if (y * cols > ii[k]) y--;
         if ((y + 1) * cols <= ii[k]) y++;
@@ -217,6 +265,7 @@ __global__ __launch_bounds__(256) void prep_scatter(PrepArgs a) {
         xx[k] = ii[k] - y * cols;
         Ib[k] = img[(unsigned)(y * sw + xx[k])];
         vv[k] = var[(unsigned)ii[k]];
+        if constexpr (MASK) ZZ[k] = gptr(K.depth)[(unsigned)ii[k]];   // (the same trip as the variance)
       }
 #pragma unroll
       for (int k = 0; k < U; k++) {
@@ -244,7 +293,7 @@ __global__ __launch_bounds__(256) void prep_scatter(PrepArgs a) {
     const int r = r0 + (int)threadIdx.x;
     if (r < nvalid) {
     const int i = (int)s_idx[r];
-    const float Z = s_Z[r];
+    const float Z = MASK ? gptr(K.depth)[(unsigned)i] : s_Z[r];
     const unsigned pos = tile_off + (unsigned)r;
     int y = (int)(((float)i + 0.5f) * inv_cols);   // i < 2^24: exact conversion; corrected below
     if (y * cols > i) y--;

@@ -158,6 +158,19 @@ ellc_status ellc_debug_set_count_cache(ellc_ctx* ctx, int on);
 /* Groups of this context that compacted with a count launch, and without one because the kept counts were current. (A tracking
  * call's count-free compaction and groups that build no lists are in neither.) Either pointer may be NULL. */
 ellc_status ellc_debug_count_cache_counters(ellc_ctx* ctx, long long* groups_counted, long long* groups_skipped);
+/* The compaction of a launch group ranks its pixels from the valid-bit masks the count launch leaves behind the tile counts and
+ * gathers the depth of the valid ones only (default on). 0: it reads the whole depth planes, as up to r09 (kept in this library
+ * only) - the same pixels in the same order, so the results must not change by a bit (tests). A plan-time choice, as the packed
+ * taps are. The count-free form of a tracking call reads the depth planes either way. */
+ellc_status ellc_debug_set_mask_scatter(ellc_ctx* ctx, int on);
+/* Scatter launches behind a count launch (now or kept) that this context has enqueued or captured in the masked form and in the
+ * depth-reading form - the tests' evidence that the two sides of their comparison ran different kernels. A count-free compaction
+ * is in neither. Either pointer may be NULL. */
+ellc_status ellc_debug_mask_scatter_counters(ellc_ctx* ctx, long long* masked, long long* from_depth);
+/* The valid-bit mask of a keyframe slot at `level`, as the last count launch left it: 64 words per tile of 2048 pixels, bit i of a
+ * tile = (depth > 0) of pixel tile * 2048 + i in raster order, zeros past the end of the plane. `out` holds 64 * ceil(n / 2048)
+ * words. ELLC_ERR_NOT_READY while the slot's counts are stale (a writer of its depth planes, or a count-free compaction, since). */
+ellc_status ellc_debug_get_valid_mask(ellc_ctx* ctx, int kf_slot, int level, uint32_t* out);
 /* Tolerance mode: the interior taps of a warped point come as ONE 16-byte load from the frame slot's row-packed plane (default on).
  * 0: as four unaligned row loads from the image plane, as up to r07 (kept in this library only) - the same twelve bytes reach the
  * same arithmetic, so the results must not change by a bit (tests). A plan-time choice: sequences captured under either are kept apart. */
