@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "ellc_keyframe_refine_depth", "ellc_refine_default_params", "ellc_sim3_invert",
     "ellc_keyframe_sweep_depth", "ellc_sweep_default_params",
     "ellc_keyframe_cull_depth", "ellc_cull_default_params",
+    "ellc_keyframe_joint_step", "ellc_joint_solve", "ellc_keyframe_joint_apply", "ellc_keyframe_joint_refine", "ellc_joint_default_params",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
     "ellc_gather_start", "ellc_gather_finish", "ellc_gather_results",
@@ -42,6 +43,7 @@ DIAG_SYMBOLS = [
     "ellc_debug_set_mask_scatter", "ellc_debug_mask_scatter_counters", "ellc_debug_get_valid_mask",
     "ellc_debug_schedule_sums", "ellc_profile_map_points", "ellc_profile_render_depth", "ellc_profile_fuse_depth", "ellc_profile_depth_absorb", "ellc_profile_trial_propagate", "ellc_profile_depth_consistency", "ellc_profile_sim3_step",
     "ellc_profile_light_step", "ellc_profile_sim3_step_lit", "ellc_profile_refine_depth", "ellc_profile_sweep_depth", "ellc_profile_cull_depth",
+    "ellc_profile_joint_step", "ellc_profile_joint_apply",
 ]
 
 
@@ -162,6 +164,31 @@ class EllcCullStats(C.Structure):
 CULL_STATS_FIELDS = tuple(f[0] for f in EllcCullStats._fields_)
 
 
+JOINT_MAX_VIEWS = 8
+
+
+class EllcJointParams(C.Structure):
+    """ellc_joint_params: the weights, the step bound and the view limit of the joint refinement (20 bytes)."""
+    _fields_ = [("sigma_i2", C.c_float), ("huber_k", C.c_float), ("prior_weight", C.c_float), ("max_step_rel", C.c_float), ("min_views", C.c_int)]
+
+
+JOINT_STATUS = ("NOT_TAKING_PART", "STEPPED", "TOO_FEW_VIEWS", "NO_INFORMATION", "BAD_STEP")
+
+
+class EllcJointNormal(C.Structure):
+    """ellc_joint_normal: what ellc_keyframe_joint_step returns (11600 bytes)."""
+    _fields_ = [("A", (C.c_double * 21) * JOINT_MAX_VIEWS), ("a", (C.c_double * 6) * JOINT_MAX_VIEWS), ("S", C.c_double * 1176), ("s", C.c_double * 48),
+                ("chi2_photo", C.c_double), ("chi2_prior", C.c_double), ("n_terms", C.c_int64),
+                ("n_kept", C.c_int32), ("n_taking_part", C.c_int32), ("n_used", C.c_int32), ("n_too_few_views", C.c_int32),
+                ("n_no_information", C.c_int32), ("B", C.c_int32), ("n_view_terms", C.c_int32 * JOINT_MAX_VIEWS)]
+
+
+class EllcJointApplyStats(C.Structure):
+    """ellc_joint_apply_stats: what ellc_keyframe_joint_apply counts (32 bytes)."""
+    _fields_ = [("n_kept", C.c_int32), ("n_taking_part", C.c_int32), ("n_stepped", C.c_int32), ("n_too_few_views", C.c_int32),
+                ("n_no_information", C.c_int32), ("n_bad_step", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class EllcAbsorbParams(C.Structure):
     """ellc_absorb_params: the gates and limits of ellc_depth_absorb_keyframes."""
     _fields_ = [("agree_k2", C.c_float), ("max_fold", C.c_int), ("photo_gate", C.c_int), ("src_validity", C.c_int), ("finalise", C.c_int)]
@@ -254,6 +281,8 @@ def _bind(path, symbols, what):
         h.ellc_sweep_default_params.restype = None
     if hasattr(h, "ellc_cull_default_params"):
         h.ellc_cull_default_params.restype = None
+    if hasattr(h, "ellc_joint_default_params"):
+        h.ellc_joint_default_params.restype = None
     if hasattr(h, "ellc_absorb_default_params"):
         h.ellc_absorb_default_params.restype = None
     for name in symbols:

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcSweepParams, EllcSweepStats, SWEEP_STATUS, SWEEP_STATS_FIELDS, EllcCullParams, EllcCullStats, CULL_STATUS, CULL_STATS_FIELDS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcSweepParams, EllcSweepStats, SWEEP_STATUS, SWEEP_STATS_FIELDS, EllcCullParams, EllcCullStats, CULL_STATUS, CULL_STATS_FIELDS, EllcJointParams, EllcJointNormal, EllcJointApplyStats, JOINT_STATUS, JOINT_MAX_VIEWS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -12,6 +12,7 @@ ERR_CAPACITY = -5
 MAP_POINT_DTYPE = np.dtype(EllcMapPoint)   # x y z var (f32), px py (u16), intensity support (u8), source (u16): 24 bytes
 LIGHT_NORMAL_DTYPE = np.dtype(EllcLightNormal)   # sum_w, sum_w_s, sum_w_t, sum_w_ss, sum_w_st, sum_w_tt, chi2_photo (f64), four int32 counts: 72 bytes
 SIM3_NORMAL_DTYPE = np.dtype(EllcSim3Normal)   # H (28 f64), b (7 f64), chi2_photo, chi2_depth (f64), six int32 counts: 320 bytes
+JOINT_NORMAL_DTYPE = np.dtype(EllcJointNormal)   # A (8 x 21), a (8 x 6), S (1176), s (48), chi2_photo, chi2_prior (f64), n_terms (i64), six int32 counts and B, n_view_terms (8 int32): 11600 bytes
 HYP_FIELDS = ("invDepth", "invDepthSmoothed", "variance", "varianceSmoothed", "validity", "blacklisted", "valid")
 
 
@@ -654,6 +655,96 @@ class Context:
         return self._cull("ellc_keyframe_cull_depth", (), kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support,
                           support_k2, stride, params)
 
+    # ---- poses and depths refined in one step
+    def _joint_args(self, view_slots, Ts, lights, level, max_var, min_support, support_k2, stride, params, inv_depth):
+        vs = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
+        B = vs.size
+        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
+        li = self._lights(lights, B)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        prm = params if isinstance(params, EllcJointParams) else joint_default_params(**(params or {}))
+        rows, cols = self.level_shape(level)
+        d = None if inv_depth is None else np.ascontiguousarray(inv_depth, np.float32).reshape(rows, cols)
+        return B, vs, T, li, flt, prm, d, (rows, cols)
+
+    @staticmethod
+    def _joint_planes(shape):
+        return dict(inv_depth=np.zeros(shape, np.float32), depth=np.zeros(shape, np.float32), var=np.zeros(shape, np.float32),
+                    views=np.zeros(shape, np.uint8), status=np.zeros(shape, np.uint8))
+
+    def joint_step(self, kf_slot, view_slots, Ts, lights=None, level=0, views_are_keyframes=True, inv_depth=None, max_var=0.0, min_support=0,
+                   support_k2=1.0, stride=1, params=None, _profile=None):
+        """The normal equations of one joint Gauss-Newton step over the SE(3) of the views and the inverse depths of keyframe slot
+        kf_slot (ellc_keyframe_joint_step), the depths eliminated: kf_slot, view_slots, Ts, lights, level, views_are_keyframes and the
+        filter as in refine_depth; inv_depth: the plane of inverse depths to evaluate at (None, or a value that is not > 0: the slot's
+        own). params: an ellc_joint_params (joint_default_params()) or a dict of sigma_i2, huber_k, prior_weight, max_step_rel, min_views
+        (defaults 16, 1.345, 1, 0.5, 2). Returns a 0-d structured array, one ellc_joint_normal: A, a per view, S, s of the Schur
+        complement, chi2_photo, chi2_prior, the counts and B. joint_solve turns it into the views' pose steps."""
+        B, vs, T, li, flt, prm, d, _ = self._joint_args(view_slots, Ts, lights, level, max_var, min_support, support_k2, stride, params, inv_depth)
+        out = np.zeros(1, JOINT_NORMAL_DTYPE)
+        name = "ellc_profile_joint_step" if _profile is not None else "ellc_keyframe_joint_step"
+        tail = (C.byref(_profile),) if _profile is not None else ()
+        self._ck(getattr(self._l, name)(self.h, int(kf_slot), int(level), B, int(views_are_keyframes), _p(vs), _p(T), _p(li), C.byref(flt), C.byref(prm),
+                                        _p(d), _p(out), *tail), name)
+        return out[0]
+
+    def joint_apply(self, kf_slot, view_slots, Ts, xi, lights=None, level=0, views_are_keyframes=True, inv_depth=None, dst_slot=-1, max_var=0.0,
+                    min_support=0, support_k2=1.0, stride=1, params=None, _profile=None):
+        """The joint step taken (ellc_keyframe_joint_apply): xi is [B][6] f64, rotation then translation per view, as joint_solve returns
+        it. Returns dict(T = [B][12] f32 the moved transforms, inv_depth, depth, var (f32), views, status (u8; JOINT_STATUS names the
+        values), stats = the fields of ellc_joint_apply_stats). var is the variance CONDITIONAL on the poses (optimistic). dst_slot >= 0
+        (level 0 only) stores depth and var into that keyframe slot as keyframe_set_depth would."""
+        B, vs, T, li, flt, prm, d, shape = self._joint_args(view_slots, Ts, lights, level, max_var, min_support, support_k2, stride, params, inv_depth)
+        x = np.ascontiguousarray(xi, np.float64).reshape(6 * B)
+        res = self._joint_planes(shape)
+        res["T"] = np.zeros((B, 12), np.float32)
+        st = EllcJointApplyStats()
+        name = "ellc_profile_joint_apply" if _profile is not None else "ellc_keyframe_joint_apply"
+        tail = (C.byref(_profile),) if _profile is not None else ()
+        self._ck(getattr(self._l, name)(self.h, int(kf_slot), int(level), B, int(views_are_keyframes), _p(vs), _p(T), _p(li), C.byref(flt), C.byref(prm),
+                                        _p(d), _p(x), int(dst_slot), _p(res["T"]), _p(res["inv_depth"]), _p(res["depth"]), _p(res["var"]),
+                                        _p(res["views"]), _p(res["status"]), C.byref(st), *tail), name)
+        res["stats"] = {f[0]: getattr(st, f[0]) for f in EllcJointApplyStats._fields_ if f[0] != "reserved"}
+        return res
+
+    def joint_refine(self, kf_slot, view_slots, Ts, lights=None, level=0, views_are_keyframes=True, inv_depth=None, max_iter=6, eps=1e-6, lam=0.0,
+                     dst_slot=-1, max_var=0.0, min_support=0, support_k2=1.0, stride=1, params=None, trace=False):
+        """The loop over joint_step, joint_solve and joint_apply (ellc_keyframe_joint_refine): a trial state is accepted iff the next
+        step's (chi2_photo + chi2_prior) / (n_terms + n_used) did not rise; a refused trial, a refused solve or max |xi| < eps ends the
+        loop at the last accepted state. lam: the factor (1 + lam) on the reduced matrix's diagonal. Returns dict(T, rec, iters and the
+        five planes of joint_apply) and, with trace=True, trace_T, trace_rec, trace_xi, trace_accepted over the steps made."""
+        B, vs, T, li, flt, prm, d, shape = self._joint_args(view_slots, Ts, lights, level, max_var, min_support, support_k2, stride, params, inv_depth)
+        cap = max(int(max_iter), 1) + 1
+        res = self._joint_planes(shape)
+        res.update(T=np.zeros((B, 12), np.float32), rec=np.zeros(1, JOINT_NORMAL_DTYPE))
+        iters = C.c_int(0)
+        tr = dict(trace_T=np.zeros((cap, B, 12), np.float32), trace_rec=np.zeros(cap, JOINT_NORMAL_DTYPE), trace_xi=np.zeros((cap, B, 6), np.float64),
+                  trace_accepted=np.zeros(cap, np.int32)) if trace else {}
+        name = "ellc_keyframe_joint_refine"
+        self._ck(getattr(self._l, name)(self.h, int(kf_slot), int(level), B, int(views_are_keyframes), _p(vs), _p(T), _p(li), C.byref(flt), C.byref(prm),
+                                        _p(d), int(max_iter), C.c_float(eps), C.c_double(lam), int(dst_slot), _p(res["T"]), _p(res["rec"]),
+                                        C.byref(iters), _p(res["inv_depth"]), _p(res["depth"]), _p(res["var"]), _p(res["views"]), _p(res["status"]),
+                                        _p(tr.get("trace_T")), _p(tr.get("trace_rec")), _p(tr.get("trace_xi")), _p(tr.get("trace_accepted")),
+                                        cap if trace else 0), name)
+        res["rec"] = res["rec"][0]
+        res["iters"] = iters.value
+        if trace:
+            n = int((tr["trace_rec"]["n_kept"] >= 0).sum())
+            res.update({k: v[:n].copy() for k, v in tr.items()})
+        return res
+
+    def profile_joint_step(self, *args, **kw):
+        """joint_step through ellc_profile_joint_step: (record, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_joint_step")
+        ms = C.c_float(0.0)
+        return self.joint_step(*args, _profile=ms, **kw), ms.value
+
+    def profile_joint_apply(self, *args, **kw):
+        """joint_apply through ellc_profile_joint_apply: (result, launches_ms), the device time of the launches."""
+        self._need_diag("ellc_profile_joint_apply")
+        ms = C.c_float(0.0)
+        return self.joint_apply(*args, _profile=ms, **kw), ms.value
+
     # ---- measurement hooks, self-tests, test hooks: contexts created with diag=True only (include/ellc_abi_diag.h)
     def _need_diag(self, what):
         if not self.diag and _lib.DIAG_SO_PATH != _lib.SO_PATH:
@@ -1043,6 +1134,25 @@ def absorb_params(agree_k2=None, max_fold=None, photo_gate=None, src_validity=No
         if v is not None:
             setattr(p, k, v)
     return p
+
+
+def joint_default_params(sigma_i2=None, huber_k=None, prior_weight=None, max_step_rel=None, min_views=None):
+    """ellc_joint_params: the library's defaults (ellc_joint_default_params) with the given fields replaced."""
+    p = EllcJointParams()
+    _lib.lib().ellc_joint_default_params(C.byref(p))
+    for k, v in (("sigma_i2", sigma_i2), ("huber_k", huber_k), ("prior_weight", prior_weight), ("max_step_rel", max_step_rel), ("min_views", min_views)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def joint_solve(rec, lam=0.0):
+    """ellc_joint_solve of one ellc_joint_normal record: (xi [B][6] f64, refused). A refused solve leaves xi as zeros."""
+    r = np.ascontiguousarray(np.asarray(rec, JOINT_NORMAL_DTYPE).reshape(1))
+    B = int(r["B"][0])
+    xi = np.zeros(6 * min(max(B, 1), JOINT_MAX_VIEWS), np.float64)
+    refused = _lib.lib().ellc_joint_solve(_p(r), C.c_double(lam), _p(xi))
+    return xi.reshape(-1, 6), bool(refused)
 
 
 def sim3_solve(rec):

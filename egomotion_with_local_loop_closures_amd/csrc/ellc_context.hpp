@@ -288,6 +288,11 @@ struct ellc_ctx {
   ellc::PairScratch cull;
   void* cull_planes_d = nullptr;            // [n] f32 depth, [n] f32 variance, [n] u32 votes, [n] u8 photo, [n] u8 status of the largest level asked for
   size_t cull_planes_cap = 0;               //   pixels it holds
+  // ellc_keyframe_joint_step / _apply / _refine: a PairScratch for the views' staging and the records of joint_pairs, one for the counts of
+  // the per-pixel kernels, and the family's planes
+  ellc::PairScratch joint, joint_count;
+  void* joint_planes_d = nullptr;           // ten f32 and five u8 planes of the largest level asked for (ellc_joint_impl.hpp names them)
+  size_t joint_planes_cap = 0;              //   pixels each holds
   float *scratch_a = nullptr, *scratch_b = nullptr;   // W*H f32 each
   int tile_begin[ELLC_MAX_LEVELS + 1];
   int cap[ELLC_MAX_LEVELS];                            // compact capacity per level (= n)

@@ -25,28 +25,14 @@ ellc_status cull_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int view
   const std::string w(who);
   // validated first: a refused call leaves the context and every slot as they were and writes nothing
   if (!view_slots || !T12 || !f || !p) return fail(c, ELLC_ERR_BAD_ARG, w + ": null pointer");
-  if (B < 1 || B > ELLC_REFINE_MAX_VIEWS) return fail(c, ELLC_ERR_BAD_ARG, w + ": B out of range");
-  if (views_are_kf < 0 || views_are_kf > 1) return fail(c, ELLC_ERR_BAD_ARG, w + ": views_are_keyframes not 0 or 1");
-  if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, w + ": level out of range");
+  ELLC_TRY(ring_views_check(c, who, B, ELLC_REFINE_MAX_VIEWS, views_are_kf, level, f, T12, light));
   const LevelGeom& g = c->geom_h[level];
-  if (g.n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, w + ": more than 2^24 pixels on the level");
-  ELLC_TRY(ring_check_filter(c, who, f));
-  for (int k = 0; k < 12 * B; k++)
-    if (!std::isfinite(T12[k])) return fail(c, ELLC_ERR_BAD_ARG, w + ": transform not finite");
-  ELLC_TRY(light_check(c, who, B, light));
   if (!std::isfinite(p->agree_k2) || !std::isfinite(p->sigma_i2) || !std::isfinite(p->photo_k) || !(p->agree_k2 >= 0.0f) || !(p->sigma_i2 > 0.0f))
     return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
   if (p->min_support < 1 || p->min_support > B || p->min_in_front < 1 || p->min_in_front > B || p->min_photo < 1 || p->min_photo > B ||
       p->min_judged < 1 || p->min_judged > B)
     return fail(c, ELLC_ERR_BAD_ARG, w + ": a count outside 1..B");
-  if (dst < -1 || dst >= c->cfg.max_keyframes) return fail(c, ELLC_ERR_BAD_ARG, w + ": destination slot out of range");
-  if (dst >= 0 && level != 0) return fail(c, ELLC_ERR_BAD_ARG, w + ": a destination slot takes level 0 only");
-  ELLC_TRY(ring_check_slots(c, who, 1, &kf_slot, c->cfg.max_keyframes));
-  ELLC_TRY(ring_check_slots(c, who, B, view_slots, views_are_kf ? c->cfg.max_keyframes : c->cfg.max_frames));
-  ELLC_TRY(ring_check_ready(c, who, 1, &kf_slot));
-  for (int b = 0; b < B; b++)
-    if (!(views_are_kf ? c->kf_has_image[view_slots[b]] : c->fr_has_image[view_slots[b]]))
-      return fail(c, ELLC_ERR_NOT_READY, w + ": view slot lacks an image");
+  ELLC_TRY(ring_views_check_slots(c, who, dst, level, kf_slot, B, view_slots, views_are_kf));
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
   const size_t n = (size_t)g.n;
   const int blocks = (int)((n + 255) / 256);
@@ -54,7 +40,7 @@ ellc_status cull_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int view
   ELLC_TRY(dev_grow(c, &c->cull_planes_d, &c->cull_planes_cap, n, 14));   // two f32 planes, one u32 plane and two u8 planes
   CullView* vw = (CullView*)c->cull.stage_h;
   for (int b = 0; b < B; b++) {
-    const size_t e = (size_t)level * (views_are_kf ? c->cfg.max_keyframes : c->cfg.max_frames) + view_slots[b];
+    const size_t e = ring_view_entry(c, level, views_are_kf, view_slots[b]);
     const bool has_depth = views_are_kf && c->kf_has_depth[view_slots[b]];
     vw[b].img = views_are_kf ? c->kf_tab_h[e].img : c->fr_tab_h[e].img;
     vw[b].depth = has_depth ? c->kf_tab_h[e].depth : nullptr;
@@ -93,31 +79,14 @@ ellc_status cull_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int view
   hipLaunchKernelGGL(cull_finish, dim3(1), dim3(64), 0, c->stream, a);
   ELLC_HIP(c, hipGetLastError());
   ELLC_TRY(t.end());
-  if (!views_are_kf) {   // a later upload into a frame slot waits for this reader
-    std::vector<char> seen((size_t)c->cfg.max_frames, 0);
-    for (int b = 0; b < B; b++)
-      if (!seen[view_slots[b]]) {
-        seen[view_slots[b]] = 1;
-        ELLC_TRY(mark_frame_use(c, view_slots[b]));
-      }
-  }
+  ELLC_TRY(ring_views_mark_use(c, B, view_slots, views_are_kf));
   if (depth) ELLC_HIP(c, hipMemcpyAsync(depth, a.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (var) ELLC_HIP(c, hipMemcpyAsync(var, a.var, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (votes) ELLC_HIP(c, hipMemcpyAsync(votes, a.votes, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (photo) ELLC_HIP(c, hipMemcpyAsync(photo, a.photo, n, hipMemcpyDeviceToHost, c->stream));
   if (status) ELLC_HIP(c, hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToHost, c->stream));
   const CullRec* rec = (const CullRec*)c->cull.out_h;
-  if (dst >= 0) {
-    // the level-0 planes into keyframe slot dst, behind the kernel that read K and the views: ellc_keyframe_refine_depth's store
-    const KfLevelDev& k = c->kf_tab_h[dst];
-    invalidate_records(c, dst);
-    ELLC_HIP(c, hipMemcpyAsync(k.depth, a.depth, n * 4, hipMemcpyDeviceToDevice, c->stream));
-    ELLC_HIP(c, hipMemcpyAsync(k.var, a.var, n * 4, hipMemcpyDeviceToDevice, c->stream));
-    ELLC_TRY(finish_depth_planes(c, dst, [&]() {
-      (void)hipStreamSynchronize(c->stream);
-      return (size_t)rec->n[6];
-    }));
-  }
+  if (dst >= 0) ELLC_TRY(ring_views_store_dst(c, dst, a.depth, a.var, n, &rec->n[6]));
   ELLC_HIP(c, hipStreamSynchronize(c->stream));
   if (out) {
     std::memset(out, 0, sizeof(*out));

@@ -1261,6 +1261,9 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   ellc::pair_free(c->sweep);
   ellc::pair_free(c->cull);
   if (c->refine_planes_d) (void)hipFree(c->refine_planes_d);
+  ellc::pair_free(c->joint);
+  ellc::pair_free(c->joint_count);
+  if (c->joint_planes_d) (void)hipFree(c->joint_planes_d);
   if (c->cull_planes_d) (void)hipFree(c->cull_planes_d);
   if (c->trial_bits_d) (void)hipFree(c->trial_bits_d);
   if (c->ingest_map) (void)hipFree(c->ingest_map);
@@ -2788,3 +2791,4 @@ ellc_status ellc_profile_stream_read(ellc_ctx* c, size_t bytes, int reps, float*
 #include "ellc_refine_impl.hpp"
 #include "ellc_sweep_impl.hpp"
 #include "ellc_cull_impl.hpp"
+#include "ellc_joint_impl.hpp"

@@ -48,6 +48,13 @@
 //                    globalOptimize::sweepMatchDepth); PATH gets one line per push that had candidates: "frameId views n_ok n_swept
 //                    n_created n_no_valid_sample n_at_range_end n_cost_too_high n_not_distinct n_flat sum_views sum_cost". Without the
 //                    flag every output file is as before
+// --joint-matches PATH (LC mode, with --match-sim3 only: a usage error otherwise) behind the Sim(3) refinement and --sweep-matches' step,
+//                    in place of --refine-matches' step where both are given and before --cull-matches' step, the transforms of the
+//                    first eight candidates and the pushed keyframe's ring map are refined together (ellc_keyframe_joint_refine, level 0,
+//                    the filter of --map, default parameters, six iterations at most, into the keyframe's own ring slot;
+//                    globalOptimize::refineMatchJoint); the refined transforms replace the Sim(3) refinement's for what follows. PATH
+//                    gets one line per push that had candidates: "frameId views iters n_kept n_taking_part n_used n_too_few_views
+//                    n_no_information n_terms chi2_photo chi2_prior". Without the flag every output file is as before
 // --cull-matches PATH  (LC mode, with --match-sim3 only: a usage error otherwise) behind the Sim(3) refinement, and behind
 //                    --refine-matches' step where both are given, the hypotheses of the pushed keyframe's ring map that its
 //                    candidates contradict at the inverted refined transforms and lights are removed (ellc_keyframe_cull_depth,
@@ -95,7 +102,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--sweep-matches PATH] [--refine-matches PATH] [--cull-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--sweep-matches PATH] [--refine-matches PATH] [--joint-matches PATH] [--cull-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -105,7 +112,7 @@ int main(int argc, char** argv) {
   std::string save_mats, replicate, init_poses;
   bool bgr = false, undistort = true, no_fused = false, match_light = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
-  std::string comm_id_file, match_quality, match_geometry, match_sim3, refine_matches, sweep_matches, cull_matches, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
+  std::string comm_id_file, match_quality, match_geometry, match_sim3, refine_matches, sweep_matches, cull_matches, joint_matches, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
   for (int i = 6; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "LC") lc = true;
@@ -128,6 +135,7 @@ int main(int argc, char** argv) {
     else if (a == "--refine-matches" && i + 1 < argc) refine_matches = argv[++i];
     else if (a == "--sweep-matches" && i + 1 < argc) sweep_matches = argv[++i];
     else if (a == "--cull-matches" && i + 1 < argc) cull_matches = argv[++i];
+    else if (a == "--joint-matches" && i + 1 < argc) joint_matches = argv[++i];
     else if (a == "--map" && i + 1 < argc) map_file = argv[++i];
     else if (a == "--render" && i + 1 < argc) render_file = argv[++i];
     else if (a == "--fuse" && i + 1 < argc) fuse_file = argv[++i];
@@ -151,6 +159,10 @@ int main(int argc, char** argv) {
   }
   if (!cull_matches.empty() && match_sim3.empty()) {
     std::fprintf(stderr, "--cull-matches needs --match-sim3 PATH: the vote runs at the transforms the Sim(3) refinement returns\n");
+    return -1;
+  }
+  if (!joint_matches.empty() && match_sim3.empty()) {
+    std::fprintf(stderr, "--joint-matches needs --match-sim3 PATH: the joint refinement starts at the transforms the Sim(3) refinement returns\n");
     return -1;
   }
   if (!match_quality.empty() && world > 1) {
@@ -244,6 +256,11 @@ int main(int argc, char** argv) {
       globalOptimizeLoop->cull_matches_file.open(cull_matches.c_str());
       if (!globalOptimizeLoop->cull_matches_file) { std::fprintf(stderr, "cannot open %s\n", cull_matches.c_str()); return -1; }
       globalOptimizeLoop->cullMatchDepth = true;
+    }
+    if (lc && !joint_matches.empty()) {
+      globalOptimizeLoop->joint_matches_file.open(joint_matches.c_str());
+      if (!globalOptimizeLoop->joint_matches_file) { std::fprintf(stderr, "cannot open %s\n", joint_matches.c_str()); return -1; }
+      globalOptimizeLoop->refineMatchJoint = true;
     }
     if (lc && !absorb_matches.empty()) {
       globalOptimizeLoop->absorb_file.open(absorb_matches.c_str());

@@ -24,27 +24,13 @@ ellc_status refine_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vi
   const std::string w(who);
   // validated first: a refused call leaves the context and every slot as they were and writes nothing
   if (!view_slots || !T12 || !f || !p) return fail(c, ELLC_ERR_BAD_ARG, w + ": null pointer");
-  if (B < 1 || B > ELLC_REFINE_MAX_VIEWS) return fail(c, ELLC_ERR_BAD_ARG, w + ": B out of range");
-  if (views_are_kf < 0 || views_are_kf > 1) return fail(c, ELLC_ERR_BAD_ARG, w + ": views_are_keyframes not 0 or 1");
-  if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, w + ": level out of range");
+  ELLC_TRY(ring_views_check(c, who, B, ELLC_REFINE_MAX_VIEWS, views_are_kf, level, f, T12, light));
   const LevelGeom& g = c->geom_h[level];
-  if (g.n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, w + ": more than 2^24 pixels on the level");
-  ELLC_TRY(ring_check_filter(c, who, f));
-  for (int k = 0; k < 12 * B; k++)
-    if (!std::isfinite(T12[k])) return fail(c, ELLC_ERR_BAD_ARG, w + ": transform not finite");
-  ELLC_TRY(light_check(c, who, B, light));
   if (!std::isfinite(p->sigma_i2) || !std::isfinite(p->huber_k) || !std::isfinite(p->prior_weight) || !std::isfinite(p->max_step_rel) ||
       !(p->sigma_i2 > 0.0f) || !(p->huber_k > 0.0f) || !(p->prior_weight >= 0.0f) || !(p->max_step_rel > 0.0f) || p->n_iter < 1 || p->n_iter > 8 ||
       p->min_views < 1 || p->min_views > B)
     return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
-  if (dst < -1 || dst >= c->cfg.max_keyframes) return fail(c, ELLC_ERR_BAD_ARG, w + ": destination slot out of range");
-  if (dst >= 0 && level != 0) return fail(c, ELLC_ERR_BAD_ARG, w + ": a destination slot takes level 0 only");
-  ELLC_TRY(ring_check_slots(c, who, 1, &kf_slot, c->cfg.max_keyframes));
-  ELLC_TRY(ring_check_slots(c, who, B, view_slots, views_are_kf ? c->cfg.max_keyframes : c->cfg.max_frames));
-  ELLC_TRY(ring_check_ready(c, who, 1, &kf_slot));
-  for (int b = 0; b < B; b++)
-    if (!(views_are_kf ? c->kf_has_image[view_slots[b]] : c->fr_has_image[view_slots[b]]))
-      return fail(c, ELLC_ERR_NOT_READY, w + ": view slot lacks an image");
+  ELLC_TRY(ring_views_check_slots(c, who, dst, level, kf_slot, B, view_slots, views_are_kf));
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
   const size_t n = (size_t)g.n;
   const int blocks = (int)((n + 255) / 256);
@@ -52,8 +38,7 @@ ellc_status refine_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vi
   ELLC_TRY(dev_grow(c, &c->refine_planes_d, &c->refine_planes_cap, n, 10));   // two f32 planes and two u8 planes
   RefineView* vw = (RefineView*)c->refine.stage_h;
   for (int b = 0; b < B; b++) {
-    const size_t e = (size_t)level * (views_are_kf ? c->cfg.max_keyframes : c->cfg.max_frames) + view_slots[b];
-    vw[b].img = views_are_kf ? c->kf_tab_h[e].img : c->fr_tab_h[e].img;
+    vw[b].img = ring_view_image(c, level, views_are_kf, view_slots[b]);
     std::memcpy(vw[b].T, T12 + (size_t)12 * b, 12 * sizeof(float));
     vw[b].gain = light ? light[2 * b] : 1.0f;
     vw[b].offset = light ? light[2 * b + 1] : 0.0f;
@@ -87,31 +72,13 @@ ellc_status refine_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vi
   hipLaunchKernelGGL(refine_finish, dim3(1), dim3(64), 0, c->stream, a);
   ELLC_HIP(c, hipGetLastError());
   ELLC_TRY(t.end());
-  if (!views_are_kf) {   // a later upload into a frame slot waits for this reader
-    std::vector<char> seen((size_t)c->cfg.max_frames, 0);
-    for (int b = 0; b < B; b++)
-      if (!seen[view_slots[b]]) {
-        seen[view_slots[b]] = 1;
-        ELLC_TRY(mark_frame_use(c, view_slots[b]));
-      }
-  }
+  ELLC_TRY(ring_views_mark_use(c, B, view_slots, views_are_kf));
   if (depth) ELLC_HIP(c, hipMemcpyAsync(depth, a.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (var) ELLC_HIP(c, hipMemcpyAsync(var, a.var, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (views) ELLC_HIP(c, hipMemcpyAsync(views, a.nviews, n, hipMemcpyDeviceToHost, c->stream));
   if (status) ELLC_HIP(c, hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToHost, c->stream));
   const RefineRec* rec = (const RefineRec*)c->refine.out_h;
-  if (dst >= 0) {
-    // the level-0 planes into keyframe slot dst, behind the kernel that read K and the views: device to device; the rest is what
-    // ellc_keyframe_set_depth does behind its upload (render_store_dst's shape)
-    const KfLevelDev& k = c->kf_tab_h[dst];
-    invalidate_records(c, dst);
-    ELLC_HIP(c, hipMemcpyAsync(k.depth, a.depth, n * 4, hipMemcpyDeviceToDevice, c->stream));
-    ELLC_HIP(c, hipMemcpyAsync(k.var, a.var, n * 4, hipMemcpyDeviceToDevice, c->stream));
-    ELLC_TRY(finish_depth_planes(c, dst, [&]() {
-      (void)hipStreamSynchronize(c->stream);
-      return (size_t)rec->n[8];
-    }));
-  }
+  if (dst >= 0) ELLC_TRY(ring_views_store_dst(c, dst, a.depth, a.var, n, &rec->n[8]));
   ELLC_HIP(c, hipStreamSynchronize(c->stream));
   if (out) {
     std::memset(out, 0, sizeof(*out));

@@ -1,5 +1,5 @@
 // The host scaffold of the calls over the keyframe ring's semi-dense maps (ellc_keyframe_map_points, _render_depth, _fuse_depth,
-// _depth_consistency, _sim3_step / _align, _light_step, _sim3_step_lit / _align_lit, _trial_propagate, _refine_depth, _sweep_depth, _cull_depth, ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes): what they
+// _depth_consistency, _sim3_step / _align, _light_step, _sim3_step_lit / _align_lit, _trial_propagate, _refine_depth, _sweep_depth, _cull_depth, _joint_step / _apply / _refine, ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes): what they
 // refuse alike, the view map_keep reads, the timing window of the diagnostic hooks, grow-only buffers and the launch loop of the pair
 // reductions. Included at the end of ellc_hip.hip in front of the *_impl.hpp of those calls (the library is one translation unit).
 // A new call of the family supplies a record type with rec_zero / rec_add / rec_wave_sum (ellc_pair_reduce.hpp), a pass kernel and a
@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 using namespace ellc;
 
@@ -66,6 +67,81 @@ MapView ring_view(const ellc_ctx* c, int level, const ellc_map_filter* f) {
   v.support_k2 = f->support_k2;
   v.stride = f->stride;
   return v;
+}
+
+// a given light: every value finite (NULL means (1, 0) for every pair)
+ellc_status light_check(ellc_ctx* c, const char* who, int B, const float* light) {
+  if (!light) return ELLC_OK;
+  for (int k = 0; k < 2 * B; k++)
+    if (!std::isfinite(light[k])) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": light not finite");
+  return ELLC_OK;
+}
+
+// ---- the calls of one keyframe slot K against B views (ellc_keyframe_refine_depth, _sweep_depth, _cull_depth, _joint_step / _apply /
+// _refine): what they refuse alike, in two runs around the call's own parameter check, the views' images, the frame slots' reader
+// marks and the store into a destination slot.
+
+// B, views_are_keyframes, the level and its size, the filter (NULL: the call has none), the transforms and the lights
+ellc_status ring_views_check(ellc_ctx* c, const char* who, int B, int max_B, int views_are_kf, int level, const ellc_map_filter* f, const float* T12,
+                             const float* light) {
+  const std::string w(who);
+  if (B < 1 || B > max_B) return fail(c, ELLC_ERR_BAD_ARG, w + ": B out of range");
+  if (views_are_kf < 0 || views_are_kf > 1) return fail(c, ELLC_ERR_BAD_ARG, w + ": views_are_keyframes not 0 or 1");
+  if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, w + ": level out of range");
+  if (c->geom_h[level].n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, w + ": more than 2^24 pixels on the level");
+  if (f) ELLC_TRY(ring_check_filter(c, who, f));
+  for (int k = 0; k < 12 * B; k++)
+    if (!std::isfinite(T12[k])) return fail(c, ELLC_ERR_BAD_ARG, w + ": transform not finite");
+  return light_check(c, who, B, light);
+}
+
+// the destination, K's slot and the views' slots, and what they have to hold
+ellc_status ring_views_check_slots(ellc_ctx* c, const char* who, int dst, int level, int kf_slot, int B, const int* view_slots, int views_are_kf) {
+  const std::string w(who);
+  if (dst < -1 || dst >= c->cfg.max_keyframes) return fail(c, ELLC_ERR_BAD_ARG, w + ": destination slot out of range");
+  if (dst >= 0 && level != 0) return fail(c, ELLC_ERR_BAD_ARG, w + ": a destination slot takes level 0 only");
+  ELLC_TRY(ring_check_slots(c, who, 1, &kf_slot, c->cfg.max_keyframes));
+  ELLC_TRY(ring_check_slots(c, who, B, view_slots, views_are_kf ? c->cfg.max_keyframes : c->cfg.max_frames));
+  ELLC_TRY(ring_check_ready(c, who, 1, &kf_slot));
+  for (int b = 0; b < B; b++)
+    if (!(views_are_kf ? c->kf_has_image[view_slots[b]] : c->fr_has_image[view_slots[b]]))
+      return fail(c, ELLC_ERR_NOT_READY, w + ": view slot lacks an image");
+  return ELLC_OK;
+}
+
+// the table entry of a view's slot on `level`, and its image there
+size_t ring_view_entry(const ellc_ctx* c, int level, int views_are_kf, int slot) {
+  return (size_t)level * (views_are_kf ? c->cfg.max_keyframes : c->cfg.max_frames) + slot;
+}
+const uint8_t* ring_view_image(const ellc_ctx* c, int level, int views_are_kf, int slot) {
+  const size_t e = ring_view_entry(c, level, views_are_kf, slot);
+  return views_are_kf ? c->kf_tab_h[e].img : c->fr_tab_h[e].img;
+}
+
+// behind the launches that read the views: a later upload into a frame slot waits for this reader
+ellc_status ring_views_mark_use(ellc_ctx* c, int B, const int* view_slots, int views_are_kf) {
+  if (views_are_kf) return ELLC_OK;
+  std::vector<char> seen((size_t)c->cfg.max_frames, 0);
+  for (int b = 0; b < B; b++)
+    if (!seen[view_slots[b]]) {
+      seen[view_slots[b]] = 1;
+      ELLC_TRY(mark_frame_use(c, view_slots[b]));
+    }
+  return ELLC_OK;
+}
+
+// The level-0 planes (device) into keyframe slot dst, behind the kernel that read K and the views: device to device; the rest is what
+// ellc_keyframe_set_depth does behind its upload (render_store_dst's shape). *dense is the pinned count of pixels whose depth is > 0,
+// read once the stream has been waited for.
+ellc_status ring_views_store_dst(ellc_ctx* c, int dst, const float* depth_d, const float* var_d, size_t n, const int32_t* dense) {
+  const KfLevelDev& k = c->kf_tab_h[dst];
+  invalidate_records(c, dst);
+  ELLC_HIP(c, hipMemcpyAsync(k.depth, depth_d, n * 4, hipMemcpyDeviceToDevice, c->stream));
+  ELLC_HIP(c, hipMemcpyAsync(k.var, var_d, n * 4, hipMemcpyDeviceToDevice, c->stream));
+  return finish_depth_planes(c, dst, [&]() {
+    (void)hipStreamSynchronize(c->stream);
+    return (size_t)*dense;
+  });
 }
 
 // ---- timing (the diagnostic hooks only): HIP events around a window of launches; read() adds the window's device time to *out, so a

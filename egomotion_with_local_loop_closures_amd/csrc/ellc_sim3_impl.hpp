@@ -4,6 +4,7 @@
 #pragma once
 #include "ellc_ring_common.hpp"
 #include "ellc_kernels_light.hpp"
+#include "ellc_joint_solve.hpp"
 #include <vector>
 
 using namespace ellc;
@@ -35,14 +36,6 @@ ellc_status sim3_validate(ellc_ctx* c, const char* who, int B, const int* src, c
   ELLC_TRY(ring_check_slots(c, who, B, dst, c->cfg.max_keyframes));
   ELLC_TRY(ring_check_ready(c, who, B, src));
   return ring_check_ready(c, who, B, dst);
-}
-
-// a given light: every value finite (NULL means (1, 0) for every pair)
-ellc_status light_check(ellc_ctx* c, const char* who, int B, const float* light) {
-  if (!light) return ELLC_OK;
-  for (int k = 0; k < 2 * B; k++)
-    if (!std::isfinite(light[k])) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": light not finite");
-  return ELLC_OK;
 }
 
 ellc_status light_check_params(ellc_ctx* c, const char* who, const ellc_light_params* p) {
@@ -259,37 +252,10 @@ void ellc_sim3_default_params(ellc_sim3_params* p) {
 
 int ellc_sim3_solve(const ellc_sim3_normal* n, double* xi7) {
   for (int i = 0; i < 7; i++) xi7[i] = 0.0;
-  double A[7][7], Lm[7][7], d[7];
+  double A[49];
   for (int i = 0, k = 0; i < 7; i++)
-    for (int j = i; j < 7; j++, k++) A[i][j] = A[j][i] = n->H[k];
-  double big = A[0][0];
-  for (int j = 1; j < 7; j++) big = std::max(big, A[j][j]);   // (a NaN on the diagonal fails its own pivot test below)
-  const double thr = 1e-10 * big;
-  for (int j = 0; j < 7; j++) {
-    double dj = A[j][j];
-    for (int k = 0; k < j; k++) dj -= Lm[j][k] * Lm[j][k] * d[k];
-    if (!(dj > thr)) return 1;
-    d[j] = dj;
-    for (int i = j + 1; i < 7; i++) {
-      double s = A[i][j];
-      for (int k = 0; k < j; k++) s -= Lm[i][k] * Lm[j][k] * d[k];
-      Lm[i][j] = s / dj;
-    }
-  }
-  double y[7];
-  for (int i = 0; i < 7; i++) {   // L y = -b
-    double s = -n->b[i];
-    for (int k = 0; k < i; k++) s -= Lm[i][k] * y[k];
-    y[i] = s;
-  }
-  for (int i = 0; i < 7; i++) y[i] /= d[i];
-  for (int i = 6; i >= 0; i--) {   // L^T xi = y
-    double s = y[i];
-    for (int k = i + 1; k < 7; k++) s -= Lm[k][i] * y[k];
-    y[i] = s;
-  }
-  for (int i = 0; i < 7; i++) xi7[i] = y[i];
-  return 0;
+    for (int j = i; j < 7; j++, k++) A[7 * i + j] = A[7 * j + i] = n->H[k];
+  return ldlt_solve_neg(7, A, n->b, xi7);   // (the routine ellc_joint_solve uses at 6 B unknowns)
 }
 
 void ellc_sim3_apply(const double* xi7, const float* T12_in, float* T12_out) {

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 22   /* ellc_keyframe_cull_depth, ellc_cull_default_params; 21: ellc_keyframe_sweep_depth, ellc_sweep_default_params; 20: ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 23   /* ellc_keyframe_joint_step, ellc_joint_solve, ellc_keyframe_joint_apply, ellc_keyframe_joint_refine, ellc_joint_default_params; 22: ellc_keyframe_cull_depth, ellc_cull_default_params; 21: ellc_keyframe_sweep_depth, ellc_sweep_default_params; 20: ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -1012,6 +1012,128 @@ ellc_status ellc_keyframe_cull_depth(ellc_ctx* ctx, int kf_slot, int level, int 
                                      const float* T12, const float* light /* may be NULL */, const ellc_map_filter* filter,
                                      const ellc_cull_params* params, int dst_kf_slot, float* depth, float* var, uint32_t* votes,
                                      uint8_t* photo, uint8_t* status, ellc_cull_stats* out /* each may be NULL */);
+
+/* ---- poses and depths refined in one step (v23) ------------------------------------------------------------------------
+ * The refinement above moves K's map with the transforms held fixed, ellc_keyframe_sim3_align(_lit) moves a transform with the map
+ * held fixed. These calls move both: one photometric Gauss-Newton step over the SE(3) of B <= ELLC_JOINT_MAX_VIEWS views and the
+ * inverse depths of K's kept pixels TOGETHER, K's own hypotheses as the prior, the depths eliminated per pixel (Schur complement), so
+ * that the host solves 6 B <= 48 unknowns. step / solve / apply / refine stand to each other as ellc_keyframe_sim3_step,
+ * ellc_sim3_solve, ellc_sim3_apply and ellc_keyframe_sim3_align do. K, `level`, the views, views_are_keyframes, T12, light, filter
+ * and dst_kf_slot mean what they mean in ellc_keyframe_refine_depth, word for word. Per pixel of K, all arithmetic IEEE f32 in this
+ * order, no contraction, correctly rounded divisions:
+ *   1. TAKING PART, d0 and hp: rule 1 of ellc_keyframe_refine_depth. The pixel is evaluated at d = inv_depth_in's value where that
+ *      plane is given (a host plane, dense cols x rows of the level) and the value is > 0 && <= FLT_MAX, and at d0 otherwise.
+ *   2. EVALUATION at d, Z = 1 / d: rule 2 of ellc_keyframe_refine_depth word for word, the views in ascending b, which gives per
+ *      view with a term rp, wp and Jd (the refinement's J), and H, g, E and n. Such a view also has the six pose entries of rule 3 of
+ *      ellc_keyframe_sim3_step, rotation then translation, a left perturbation exp(xi^) T in the VIEW's camera:
+ *        Jp = (Cq y' - Bv z',  A z' - Cq x',  Bv x' - A y',  A,  Bv,  Cq).
+ *      TOO_FEW_VIEWS if n < min_views.  Ht = H + hp;  gd = g + hp * (d - d0);  NO_INFORMATION unless Ht > 0 && Ht <= FLT_MAX;
+ *      otherwise the pixel is USED and ih = 1 / Ht.
+ *   3. SUMS over the used pixels, in double; every term is the product of two f32 values, exact in double (rule 6 of
+ *      ellc_keyframe_sim3_step). With wJp[k] = wp * Jp[k], c_b[k] = (wp * Jd) * Jp[k] and m_b[k] = c_b[k] * ih, per view b with a
+ *      term (and per pair of views b <= c that both have one):
+ *        A[b][(k,l)]      += wJp_b[k] * Jp_b[l]   k <= l, row-major upper triangle of a 6 x 6: 21 sums a view
+ *        a[b][k]          += wJp_b[k] * rp_b
+ *        S[(6b+k, 6c+l)]  += m_b[k] * c_c[l]      6b+k <= 6c+l, row-major upper triangle of the 6B x 6B matrix
+ *        s[6b+k]          += m_b[k] * gd
+ *        chi2_photo       += (double)E;    chi2_prior += (double)((hp * (d - d0)) * (d - d0)).
+ *      The reduced system is H = blockdiag(A) - S, b = a - s; the record returns A, a, S and s apart, so that every sum has its own
+ *      bound and the host takes the differences. The pixels are partitioned by the level's size alone, partial sums are combined in
+ *      a fixed order in double, no floating-point atomics: the same bytes on every call.
+ *   4. COUNTS, all exact: n_kept, n_taking_part (the sum of the next three), n_used, n_too_few_views, n_no_information; n_terms,
+ *      the sum of n over the used pixels, and n_view_terms[b], view b's share of it. Entries of views >= B are zero.
+ *   The record is a function of the intrinsics, the level, K's three planes, the views' images, the T's, the lights, the filter, the
+ *   params and inv_depth_in ALONE; cfg.arith, cfg.grid_batch and whatever is in flight do not enter it. THE ORDER OF THE VIEWS DOES
+ *   (H and g are f32 sums in ascending b). A view from which no pixel gets four taps changes no byte of the other views' sums.
+ * ellc_keyframe_joint_step refuses what ellc_keyframe_refine_depth refuses, in its order (ELLC_JOINT_MAX_VIEWS for its limit, no
+ * n_iter, no destination), and a NULL `out`; prior_weight == 0 is accepted here. Synchronous; a refused call writes nothing. */
+#define ELLC_JOINT_MAX_VIEWS 8
+
+typedef enum {
+  ELLC_JOINT_NOT_TAKING_PART = 0,
+  ELLC_JOINT_STEPPED = 1,        /* (USED, in the step's counts) */
+  ELLC_JOINT_TOO_FEW_VIEWS = 2,
+  ELLC_JOINT_NO_INFORMATION = 3,
+  ELLC_JOINT_BAD_STEP = 4
+} ellc_joint_status;
+
+typedef struct {
+  float sigma_i2;      /* > 0: variance of a grey value, as in ellc_refine_params */
+  float huber_k;       /* > 0: Huber threshold on |rp| / sigma_i */
+  float prior_weight;  /* >= 0: factor on the prior's information 1 / V0 (ellc_keyframe_joint_refine: > 0) */
+  float max_step_rel;  /* > 0: a depth step beyond max_step_rel * d leaves the pixel where it was (BAD_STEP) */
+  int   min_views;     /* 1..B views with four taps a pixel needs */
+} ellc_joint_params;   /* 20 bytes */
+void ellc_joint_default_params(ellc_joint_params* params);   /* {16, 1.345, 1, 0.5, 2}: the refinement's */
+
+typedef struct {
+  double  A[ELLC_JOINT_MAX_VIEWS][21];   /* offset 0 */
+  double  a[ELLC_JOINT_MAX_VIEWS][6];    /* 1344 */
+  double  S[1176];                       /* 1728: the first 6B (6B + 1) / 2 entries are used */
+  double  s[48];                         /* 11136 */
+  double  chi2_photo, chi2_prior;        /* 11520, 11528 */
+  int64_t n_terms;                       /* 11536 */
+  int32_t n_kept;                        /* 11544 (-1 in a trace entry that was not written) */
+  int32_t n_taking_part, n_used, n_too_few_views, n_no_information;
+  int32_t B;                             /* 11564: the views of the call: what ellc_joint_solve sizes the system by */
+  int32_t n_view_terms[ELLC_JOINT_MAX_VIEWS];   /* 11568 */
+} ellc_joint_normal;                     /* 11600 bytes, every field naturally aligned */
+
+ellc_status ellc_keyframe_joint_step(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                     const float* T12, const float* light /* may be NULL */, const ellc_map_filter* filter,
+                                     const ellc_joint_params* params, const float* inv_depth_in /* may be NULL */,
+                                     ellc_joint_normal* out);
+
+/* Host only, no device work. Forms H and b of rule 3 from the record (6 B unknowns, B = rec->B), multiplies H's diagonal by
+ * (1 + lambda) and solves H xi = -b by L D L^T in double without pivoting: the routine of ellc_sim3_solve at another size. Returns
+ * non-zero and writes NOTHING when B is outside 1..ELLC_JOINT_MAX_VIEWS, lambda is negative or not finite, a sum or a component of
+ * the step is not finite, or a pivot is not above 1e-10 times the largest diagonal entry. xi + 6 b is view b's (rotation,
+ * translation). */
+int ellc_joint_solve(const ellc_joint_normal* rec, double lambda, double* xi /* [6 * rec->B] */);
+
+/* The step taken. POSES (host): T12_out + 12 b = ellc_sim3_apply((xi_b, log-scale 0), T12 + 12 b). DEPTHS, per pixel that takes part:
+ * the evaluation of rules 1 and 2 at the GIVEN T12 and inv_depth_in, and with xf = (float)xi
+ *        q = 0;  q = q + c_b[k] * xf[6b+k]  for the views with a term in ascending b, k = 0 .. 5;
+ *        delta = -((gd + q) * ih);  dn = d + delta;
+ * BAD_STEP unless dn > 0 && dn <= FLT_MAX && fabsf(delta) <= max_step_rel * d (NaN fails); otherwise the pixel is STEPPED.
+ * OUTPUTS (host pointers, dense cols x rows of the level, each may be NULL): a STEPPED pixel gets inv_depth_out = dn, depth = 1 / dn,
+ * var = ih; every other pixel keeps K's own depth and variance BITS, its inv_depth_out is d where it takes part and 0 where not.
+ * `views` is n (0 where the pixel does not take part), `status` an ellc_joint_status. var = ih is the variance of the inverse depth
+ * CONDITIONAL on the poses: it leaves out what the poses' own uncertainty adds and is OPTIMISTIC. The stats are exact counts.
+ * dst_kf_slot is -1 or a keyframe slot, at level 0 only, exactly as in ellc_keyframe_refine_depth (depth and var are stored).
+ * Refusals: the step's, a NULL xi or T12_out, an xi that is not finite, the destination errors of the refinement. */
+typedef struct {
+  int32_t n_kept, n_taking_part;   /* as in the step */
+  int32_t n_stepped, n_too_few_views, n_no_information, n_bad_step;
+  int32_t reserved[2];             /* 0 */
+} ellc_joint_apply_stats;          /* 32 bytes */
+
+ellc_status ellc_keyframe_joint_apply(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                      const float* T12, const float* light /* may be NULL */, const ellc_map_filter* filter,
+                                      const ellc_joint_params* params, const float* inv_depth_in /* may be NULL */, const double* xi,
+                                      int dst_kf_slot, float* T12_out, float* inv_depth_out, float* depth, float* var, uint8_t* views,
+                                      uint8_t* status, ellc_joint_apply_stats* out /* the six last may be NULL */);
+
+/* The loop. State: the transforms and an inverse-depth plane (T12, inv_depth_in at the start). rec = step(state); then up to
+ * max_iter times: solve(rec, lambda) - a refused solve ends the loop; max |xi_i| < eps ends it; trial = apply(state, xi);
+ * rec' = step(trial); the trial is ACCEPTED iff c(rec') <= c(rec), c = (chi2_photo + chi2_prior) / (n_terms + n_used) (a c that is
+ * NaN, or n_used == 0, refuses) - a refused trial ends the loop at the last accepted state; otherwise state = trial, rec = rec'.
+ * The depth plane stays on the device between the iterations; records, xi and the final planes cross to the host.
+ * OUTPUTS: T12_out and `out`, the accepted state's transforms and record; *iters_out, the accepted trials; the five planes of the
+ * apply that made the accepted state - with no accepted trial K's own depth and variance, inv_depth_in's values where given (0
+ * elsewhere) and zeros; dst_kf_slot receives depth and var as in the apply. TRACE (each may be NULL; trace_capacity >= max_iter + 1
+ * where one is given): entry e is the e-th step's T12 [B][12] and record, trace_xi's entry e the xi [6 B] solved from it (zeros
+ * where no solve succeeded), trace_accepted[e] whether entry e became the state (entry 0 does). Entries not written have
+ * n_kept = -1. Everything is held aside until the call has succeeded.
+ * Refusals: the apply's without xi, and prior_weight == 0 (the scale gauge is free without a prior and the reduced matrix singular
+ * by construction), max_iter outside 1..16, eps or lambda negative or not finite, a trace_capacity that is too small. */
+ellc_status ellc_keyframe_joint_refine(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                       const float* T12_in, const float* light /* may be NULL */, const ellc_map_filter* filter,
+                                       const ellc_joint_params* params, const float* inv_depth_in /* may be NULL */, int max_iter,
+                                       float eps, double lambda, int dst_kf_slot, float* T12_out, ellc_joint_normal* out, int* iters_out,
+                                       float* inv_depth_out, float* depth, float* var, uint8_t* views, uint8_t* status,
+                                       float* trace_T12, ellc_joint_normal* trace_rec, double* trace_xi, int* trace_accepted,
+                                       int trace_capacity);
 
 /* ---- semi-dense depth map: class depthMap (DepthPropagation.cpp) -----------------------------------
  * One depth map per context (the reference's currentDepthMap). State is SoA on device:

@@ -100,6 +100,18 @@ ellc_status ellc_profile_cull_depth(ellc_ctx* ctx, int kf_slot, int level, int B
                                     int dst_kf_slot, float* depth, float* var, uint32_t* votes, uint8_t* photo, uint8_t* status,
                                     ellc_cull_stats* out, float* launches_ms);
 
+/* ellc_keyframe_joint_step and ellc_keyframe_joint_apply with HIP events around their launches (joint_pixels, joint_count_finish,
+ * joint_pairs, joint_pair_finish; joint_apply_pixels, joint_count_finish): launches_ms receives their device time, without the
+ * staging copies in front and the downloads behind. Everything else as the product calls. */
+ellc_status ellc_profile_joint_step(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                    const float* T12, const float* light, const ellc_map_filter* filter, const ellc_joint_params* params,
+                                    const float* inv_depth_in, ellc_joint_normal* out, float* launches_ms);
+ellc_status ellc_profile_joint_apply(ellc_ctx* ctx, int kf_slot, int level, int B, int views_are_keyframes, const int* view_slots,
+                                     const float* T12, const float* light, const ellc_map_filter* filter, const ellc_joint_params* params,
+                                     const float* inv_depth_in, const double* xi, int dst_kf_slot, float* T12_out, float* inv_depth_out,
+                                     float* depth, float* var, uint8_t* views, uint8_t* status, ellc_joint_apply_stats* out,
+                                     float* launches_ms);
+
 /* Counter calibration: stream `bytes` of device memory once per launch with 4-byte-per-lane loads (the access
  * width of the compacted pixel arrays), `reps` launches, so FETCH_SIZE can be scaled against a known byte count
  * (MI355X_MICROARCH.md, HBM section). Returns average milliseconds per launch. */

@@ -497,6 +497,19 @@ class globalOptimize {
   ellc_cull_stats lastCullStats = ellc_cull_stats();
   int lastCullViews = 0;
   std::ofstream cull_matches_file;
+  // Poses and depths together (ellc_keyframe_joint_refine; off by default: nothing changes; it needs refineMatchSim3): the first
+  // min(candidates, ELLC_JOINT_MAX_VIEWS) candidates' transforms and the pushed keyframe's ring map are refined in one Gauss-Newton loop -
+  // level 0, the filter of ellc_main --map, the default ellc_joint_params with min_views = min(2, views), six iterations at most, eps
+  // 1e-6, lambda 0, the keyframe's own ring slot as the destination - AFTER sweepMatchDepth, IN PLACE OF refineMatchDepth where both are
+  // asked for, and BEFORE cullMatchDepth, which then votes at the refined transforms. The refined transforms go back into
+  // lastMatchSim3[b].T (inverted again: candidate -> keyframe), so that absorbMatches and match_sim3_file see them. lastJointRecord /
+  // lastJointViews / lastJointIters keep the accepted state's record (zeros: no candidates) and joint_matches_file (when open) gets
+  // "frameId views iters n_kept n_taking_part n_used n_too_few_views n_no_information n_terms chi2_photo chi2_prior" per push that had
+  // candidates. The ring copy alone is touched.
+  bool refineMatchJoint = false;
+  ellc_joint_normal lastJointRecord = ellc_joint_normal();
+  int lastJointViews = 0, lastJointIters = 0;
+  std::ofstream joint_matches_file;
   // What a closed loop teaches, kept in the TRACKING context (ellc_depth_absorb_keyframes): every candidate of the push's batch is folded
   // into the live depth map of the pushed keyframe at its refined Sim(3). Off by default: nothing changes. On: pushToArray runs
   // findMatchParallel synchronously with the Sim(3) refinement, copies the ring slot of every entry of lastMatchSim3 into the tracking
@@ -974,6 +987,8 @@ class globalOptimize {
     lastSweepViews = 0;
     lastCullStats = ellc_cull_stats();
     lastCullViews = 0;
+    lastJointRecord = ellc_joint_normal();
+    lastJointViews = lastJointIters = 0;
     loopFrameArray[nextArrayId].frameId = testFrame.frameId;
     lastTestedLoopClosureArrayId = -1;
     firstTestedLoopClosureArrayId = -1;
@@ -1107,7 +1122,7 @@ class globalOptimize {
       // the views of the three structure steps: the candidates' ring slots, each at the INVERSE of its refined transform and light
       const int V = std::min(B, (int)ELLC_REFINE_MAX_VIEWS);
       std::vector<float> T, light;
-      if (refineMatchSim3 && (sweepMatchDepth || refineMatchDepth || cullMatchDepth)) {
+      if (refineMatchSim3 && (sweepMatchDepth || refineMatchDepth || refineMatchJoint || cullMatchDepth)) {
         T.resize((size_t)V * 12); light.resize((size_t)V * 2);
         for (int b = 0; b < V; b++) {
           const MatchSim3& q = lastMatchSim3[(size_t)b];
@@ -1132,7 +1147,31 @@ class globalOptimize {
           sweep_matches_file.flush();
         }
       }
-      if (refineMatchSim3 && refineMatchDepth) {
+      if (refineMatchSim3 && refineMatchJoint) {
+        ellc_map_filter filter;   // the filter of ellc_main --map
+        filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
+        ellc_joint_params params;
+        ellc_joint_default_params(&params);
+        const int VJ = std::min(V, (int)ELLC_JOINT_MAX_VIEWS);
+        params.min_views = std::min(params.min_views, VJ);
+        lastJointViews = VJ;
+        std::vector<float> Tj((size_t)VJ * 12);
+        ring.check(ellc_keyframe_joint_refine(ring.ctx, testFrame.ring_slot, 0, VJ, 1, kf.data(), T.data(), light.data(), &filter, &params, nullptr, 6, 1e-6f,
+                                              0.0, testFrame.ring_slot, Tj.data(), &lastJointRecord, &lastJointIters, nullptr, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr, nullptr, nullptr, nullptr, 0),
+                   "ellc_keyframe_joint_refine");
+        for (int b = 0; b < VJ; b++) {   // for the cull below (keyframe -> candidate) and for the absorb (candidate -> keyframe)
+          for (int k = 0; k < 12; k++) T[(size_t)b * 12 + k] = Tj[(size_t)b * 12 + k];
+          ellc_sim3_invert(&Tj[(size_t)b * 12], nullptr, lastMatchSim3[(size_t)b].T, nullptr);
+        }
+        if (joint_matches_file.is_open()) {
+          const ellc_joint_normal& r = lastJointRecord;
+          joint_matches_file << (testFrame.frameId + rt->BATCH_START_ID - 1) << " " << VJ << " " << lastJointIters << " " << r.n_kept << " "
+                             << r.n_taking_part << " " << r.n_used << " " << r.n_too_few_views << " " << r.n_no_information << " " << r.n_terms << " "
+                             << r.chi2_photo << " " << r.chi2_prior << "\n";
+          joint_matches_file.flush();
+        }
+      } else if (refineMatchSim3 && refineMatchDepth) {
         ellc_map_filter filter;   // the filter of ellc_main --map
         filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
         ellc_refine_params params;
