@@ -485,6 +485,22 @@ __device__ __forceinline__ int cvt_floor_i32(float x) {   // floor, then the sat
   asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(i) : "v"(x));
   return i;
 }
+// Register pairs for the packed f32 instructions (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32). A packed instruction takes either half
+// of each source pair for either lane (op_sel, op_sel_hi) and a sign per lane (neg_lo, neg_hi), so a value needs one home only: what
+// the compiler's own pairing of scalar code (the SLP vectoriser) does not know, it assembles its pairs with v_mov_b32 (r11).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// (a.y - b.x, b.y - a.x): the builtins cannot say a half and a sign per lane; each lane is one IEEE subtraction (x - y = -y + x)
+__device__ __forceinline__ f32x2 pk_sub_cross(f32x2 a, f32x2 b) {
+  f32x2 r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float fma_free_dst(float a, float b, float c) {   // fma(a, b, c) into any register (three-address form)
+  float r;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
 // Two halves: tap_request_f decides interior / border for the wave and requests the four words (r09: a border wave's at the clamped
 // origin); tap_finish_f turns them (or, under the diagnostic library's row loads, the synchronous per-tap loads of a border wave) into the taps. (r04 put the next pixel's request in front of the current pixel's
 // finish — a software pipeline over pixels: 1280x960 dense 387 against 389 us, 640x480 5 % slower, 125 registers: not kept.)
@@ -503,8 +519,10 @@ __device__ __forceinline__ TapReq tap_request_f(const TapRows& tr, int sw, int c
   const int x0 = cvt_floor_i32(x1), y0 = cvt_floor_i32(y1);
   // x0 in [1, cols - 3] and y0 in [1, rows - 3] (all 16 neighbours in range, none of the four taps on a border column / row); a
   // NaN coordinate converts to 0 and an infinite one saturates: neither is interior
-  const bool interior = ((unsigned)(x0 - 1) <= (unsigned)(cols - 4)) & ((unsigned)(y0 - 1) <= (unsigned)(rows - 4));
-  q.interior = (__builtin_amdgcn_ballot_w64(!interior) == 0ull);
+  // r11: the OR of two ballots, not the ballot of an OR: a bool built from two compares goes through v_cndmask_b32 0, 1 and a
+  // v_cmp_ne_u32 on its way into the ballot (two slow-class instructions a pixel); each compare's own mask is a ballot already
+  const bool x_out = (unsigned)(x0 - 1) > (unsigned)(cols - 4), y_out = (unsigned)(y0 - 1) > (unsigned)(rows - 4);
+  q.interior = ((__builtin_amdgcn_ballot_w64(x_out) | __builtin_amdgcn_ballot_w64(y_out)) == 0ull);
   q.clamped = false;
   // (r04 measured the straight-line form — the rows requested unconditionally, a lane that is not interior asking for the image's
   // first bytes — which a software pipeline over pixels needs: 5 % slower on the batch pipeline, the coarse levels' waves on the
@@ -583,9 +601,6 @@ __device__ __forceinline__ Taps tap_finish_f(const TapReq& q, g_u8 img, int sw, 
 #ifdef ELLC_ROW_TAPS
     if (q.rows) { Pbb = cvt_ubyte<1>(q.wb); Pbc = cvt_ubyte<2>(q.wb); Pcb = cvt_ubyte<1>(q.wc); Pcc = cvt_ubyte<2>(q.wc); }
 #endif
-    const float top = __builtin_fmaf(wx, Pbc - Pbb, Pbb);
-    const float btm = __builtin_fmaf(wx, Pcc - Pcb, Pcb);
-    o.I = __builtin_fmaf(wy, btm - top, top);
     if (WANT_GRAD) {
       float Pba = cvt_ubyte<1>(q.wa), Pbd = cvt_ubyte<1>(q.wd), Pca = cvt_ubyte<2>(q.wa), Pcd = cvt_ubyte<2>(q.wd);
       float Pab = cvt_ubyte<0>(q.wb), Pac = cvt_ubyte<0>(q.wc), Pdb = cvt_ubyte<3>(q.wb), Pdc = cvt_ubyte<3>(q.wc);
@@ -595,15 +610,26 @@ __device__ __forceinline__ Taps tap_finish_f(const TapReq& q, g_u8 img, int sw, 
         Pab = cvt_ubyte<1>(q.wa); Pac = cvt_ubyte<2>(q.wa); Pdb = cvt_ubyte<1>(q.wd); Pdc = cvt_ubyte<2>(q.wd);
       }
 #endif
-      const float g00 = Pbc - Pba, g01 = Pbd - Pbb, g10 = Pcc - Pca, g11 = Pcd - Pcb;   // twice the central differences
-      float t2 = __builtin_fmaf(wx, g01 - g00, g00);
-      float b2 = __builtin_fmaf(wx, g11 - g10, g10);
-      o.gx = __builtin_fmaf(wy, b2 - t2, t2);   // TWICE the gradient (the caller folds the 0.5 in)
-      const float h00 = Pcb - Pab, h01 = Pcc - Pac, h10 = Pdb - Pbb, h11 = Pdc - Pbc;
-      t2 = __builtin_fmaf(wx, h01 - h00, h00);
-      b2 = __builtin_fmaf(wx, h11 - h10, h10);
-      o.gy = __builtin_fmaf(wy, b2 - t2, t2);
+      // r11: each sample has ONE home, the (b, c) rows of a column or the (a, d) rows of a middle column as a register pair; every
+      // difference and every interpolation along x is then a packed instruction on whole pairs (lanes: the upper and the lower
+      // tap), and no value is moved. The same subtractions and fused multiply-adds on the same operands as the scalar form below
+      // (the !WANT_GRAD branch has the intensity's): top = fma(wx, Pbc - Pbb, Pbb), g00 = Pbc - Pba, h00 = Pcb - Pab, ...
+      const f32x2 X = {Pbb, Pcb}, A1 = {Pbc, Pcc}, B1 = {Pba, Pca}, A2 = {Pbd, Pcd}, Y = {Pab, Pdb}, Y1 = {Pac, Pdc};
+      const f32x2 wx2 = (f32x2)(wx);
+      const f32x2 I2 = fma2(wx2, A1 - X, X);                 // (top, btm) of the intensity
+      const f32x2 G0 = A1 - B1, G1 = A2 - X;                 // (g00, g10), (g01, g11): twice the central differences along x
+      const f32x2 GX = fma2(wx2, G1 - G0, G0);
+      const f32x2 H0 = pk_sub_cross(X, Y), H1 = pk_sub_cross(A1, Y1);   // (h00, h10) = (Pcb - Pab, Pdb - Pbb), (h01, h11) = (Pcc - Pac, Pdc - Pbc)
+      const f32x2 GY = fma2(wx2, H1 - H0, H0);
+      o.I = __builtin_fmaf(wy, I2.y - I2.x, I2.x);
+      // (v_fma_f32 with a destination of its own: as v_fmac_f32, which the compiler prefers, the result lands on GX.x / GY.x and is
+      // moved from there into the (gy, gx) pair that fcaf_stage_b multiplies)
+      o.gx = fma_free_dst(wy, GX.y - GX.x, GX.x);   // TWICE the gradient (the caller folds the 0.5 in)
+      o.gy = fma_free_dst(wy, GY.y - GY.x, GY.x);
     } else {
+      const float top = __builtin_fmaf(wx, Pbc - Pbb, Pbb);
+      const float btm = __builtin_fmaf(wx, Pcc - Pcb, Pcb);
+      o.I = __builtin_fmaf(wy, btm - top, top);
       o.gx = 0.0f; o.gy = 0.0f;
     }
     return o;
@@ -977,6 +1003,7 @@ struct FcafConst {
   float rfy, qc;     // q = (y - cy) / fy = y rfy + qc
   float rfx, pc;     // p = (x - cx) / fx = x rfx + pc
   float hfx, hfy;    // fx / 2, fy / 2 (the taps return twice the gradient)
+  float hP3, hP7, hP11;   // P[3] / 2, P[7] / 2, P[11] / 2: the 0.5 of the depth derivative (fcaf_stage_b), once per block (r11)
 };
 __device__ __forceinline__ FcafConst fcaf_const(const LevelGeom& g, const float* S) {
   FcafConst c;
@@ -993,6 +1020,8 @@ __device__ __forceinline__ FcafConst fcaf_const(const LevelGeom& g, const float*
 #pragma unroll
   for (int k = 0; k < 12; k++) asm volatile("" : "+v"(c.P[k]));
   asm volatile("" : "+v"(c.rfy), "+v"(c.qc), "+v"(c.hfx), "+v"(c.hfy));
+  // (from the vector copies, and not pinned themselves: a kernel that does not use them keeps its instruction stream)
+  c.hP3 = 0.5f * c.P[3]; c.hP7 = 0.5f * c.P[7]; c.hP11 = 0.5f * c.P[11];
   return c;
 }
 
@@ -1036,20 +1065,33 @@ __device__ __forceinline__ FcaPix fcaf_stage_b(const GnArgs& a, const KfLevelDev
   //   J = [-(q T + B), p T + A, B p - A q, A d, B d, -d T]
   // (the taps return twice the gradients.) Entries 0 and 5 are carried with the opposite sign — the accumulators then hold
   // sign-flipped sums, exactly (rounding is symmetric), and fca_acc_unpack<true> flips them back
-  const float A = c.hfx * t.gx, B = c.hfy * t.gy;
+  // (r11: (B, A) and (-J[0], J[1]) as pairs, one packed instruction each: the gradients have their home side by side)
+  const f32x2 BA = (f32x2){c.hfy, c.hfx} * (f32x2){t.gy, t.gx};
+  const float A = BA.y, B = BA.x;
   const float T = __builtin_fmaf(A, p, B * q);
-  o.J[0] = __builtin_fmaf(q, T, B);   // -J[0]
-  o.J[1] = __builtin_fmaf(p, T, A);
+  const f32x2 J01 = fma2((f32x2){q, p}, (f32x2)(T), BA);
+  o.J[0] = J01.x;   // -J[0] = fma(q, T, B)
+  o.J[1] = J01.y;   //  J[1] = fma(p, T, A)
   o.J[2] = __builtin_fmaf(B, p, -(A * q));
   o.J[3] = A * d;
   o.J[4] = B * d;
-  o.J[5] = d * T;                     // -J[5]
+  // (r11: kept a scalar product, opaque to the vectoriser: paired with J[4] as (B, T) * (d, d) it costs a move of T next to B and
+  // two copies of d for one multiplication saved)
+  float J5 = d * T;                   // -J[5]
+  asm("" : "+v"(J5));
+  o.J[5] = J5;
   const float res = t.I - s.Ikf;
   // weight (:341-358): w_p = 1 / D, sqrt(w_p) = rsq(D);  Huber: w_p below the knee (|r| sqrt(w_p) < 1.5), 1.5 sqrt(w_p) / |r|
   // above it — the smaller of the two. With the point in pixel units, t' = K t:  fx (tx pz - tz px) = t'x pz - tz px', so
   // drpdd = (A n0 + B n1) rz^2 = (gx2 n0' + gy2 n1') rz^2 / 2  (gx2, gy2: twice the gradients)
-  const float n0 = __builtin_fmaf(c.P[3], s.pz, -(c.P[11] * s.px)), n1 = __builtin_fmaf(c.P[7], s.pz, -(c.P[11] * s.py));
-  const float drpdd = __builtin_fmaf(t.gx, n0, t.gy * n1) * (0.5f * (s.rz * s.rz));
+  // r11: the 0.5 sits in the block's halved copies of P[3], P[7], P[11]: n0 / 2, n1 / 2 and the sum below are the former values
+  // halved exactly (a power of two commutes with every rounding on the way), and (s / 2) rz^2 rounds as s (rz^2 / 2) did
+  // The kernels that store the weights (SAVEW = 1) carry the record's index around the loop as well; with three more constants
+  // gn_fca_fused<.., 1> would need 97 registers, four waves a SIMD instead of five. They keep the multiplication: the same bits.
+  constexpr bool HALVED = (SAVEW <= 0);
+  const float P3 = HALVED ? c.hP3 : c.P[3], P7 = HALVED ? c.hP7 : c.P[7], P11 = HALVED ? c.hP11 : c.P[11];
+  const float n0 = __builtin_fmaf(P3, s.pz, -(P11 * s.px)), n1 = __builtin_fmaf(P7, s.pz, -(P11 * s.py));
+  const float drpdd = __builtin_fmaf(t.gx, n0, t.gy * n1) * (HALVED ? s.rz * s.rz : 0.5f * (s.rz * s.rz));
   const float D = __builtin_fmaf(s.var * drpdd, drpdd, 16.0f);
   const float r = __builtin_amdgcn_rsqf(D);
   // r min(r, k) = min(r r, r k), the middle one of (0, r r, r k); a NaN (a point at pz = 0: it is out of bounds, its J is zero, and
@@ -1084,7 +1126,6 @@ __device__ __forceinline__ FcaPix fcaf_pixel(const GnArgs& a, const KfLevelDev& 
 // The accumulators are kept as register pairs so that every update is one packed fma (v_pk_fma_f32) of a J pair with a
 // broadcast (w J[r]): rows 1, 3 and 5 carry one unused lane each (the element left of the diagonal) to keep the J pairs
 // aligned. Each of the 27 used lanes still performs exactly acc = fma(J[r] * w, J[c], acc) per pixel.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct FcaAcc {
   f32x2 h[12];   // (00,01)(02,03)(04,05) (10*,11)(12,13)(14,15) (22,23)(24,25) (32*,33)(34,35) (44,45) (54*,55)
   f32x2 b[3];
@@ -1095,7 +1136,6 @@ __device__ __forceinline__ void fca_acc_zero(FcaAcc& A) {
 #pragma unroll
   for (int i = 0; i < 3; i++) A.b[i] = (f32x2)(0.0f);
 }
-__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ void fca_accumulate_pixel(FcaAcc& A, const FcaPix& p) {
   const f32x2 J01 = {p.J[0], p.J[1]}, J23 = {p.J[2], p.J[3]}, J45 = {p.J[4], p.J[5]};
   const f32x2 w2 = (f32x2)(p.wgt);
