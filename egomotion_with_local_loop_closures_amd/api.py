@@ -573,15 +573,19 @@ class Context:
         return self._align("ellc_keyframe_sim3_align_lit", True, src_slots, dst_slots, Ts, lights, level_from, level_to, max_iter, eps, max_var,
                            min_support, support_k2, stride, params, light_params, trace)
 
-    # ---- a keyframe's map refined against other views
-    def _refine(self, name, tail, kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support, support_k2, stride, params):
+    # ---- one keyframe slot against B views: what refine_depth, sweep_depth, cull_depth and the joint calls make of their arguments
+    def _views_args(self, view_slots, Ts, lights, level, flt=None):
+        """(B, view slots, [B][12] transforms, lights or None, (rows, cols) of the level) and, with flt = (max_var, min_support,
+        support_k2, stride), the ellc_map_filter behind them."""
         vs = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
         B = vs.size
-        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
-        li = self._lights(lights, B)
-        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        out = (B, vs, np.ascontiguousarray(Ts, np.float32).reshape(B, 12), self._lights(lights, B), self.level_shape(level))
+        return out if flt is None else out + (EllcMapFilter(flt[0], int(flt[1]), flt[2], int(flt[3])),)
+
+    # ---- a keyframe's map refined against other views
+    def _refine(self, name, tail, kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support, support_k2, stride, params):
+        B, vs, T, li, (rows, cols), flt = self._views_args(view_slots, Ts, lights, level, (max_var, min_support, support_k2, stride))
         prm = params if isinstance(params, EllcRefineParams) else refine_default_params(**(params or {}))
-        rows, cols = self.level_shape(level)
         res = dict(depth=np.zeros((rows, cols), np.float32), var=np.zeros((rows, cols), np.float32), views=np.zeros((rows, cols), np.uint8),
                    status=np.zeros((rows, cols), np.uint8))
         st = EllcRefineStats()
@@ -604,12 +608,8 @@ class Context:
 
     # ---- hypotheses created in a keyframe's map by a depth sweep against other views
     def _sweep(self, name, tail, kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, params):
-        vs = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
-        B = vs.size
-        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
-        li = self._lights(lights, B)
+        B, vs, T, li, (rows, cols) = self._views_args(view_slots, Ts, lights, level)
         prm = params if isinstance(params, EllcSweepParams) else sweep_params(**(params or {}))
-        rows, cols = self.level_shape(level)
         depth, var = np.zeros((rows, cols), np.float32), np.zeros((rows, cols), np.float32)
         views, status = np.zeros((rows, cols), np.uint8), np.zeros((rows, cols), np.uint8)
         st = EllcSweepStats()
@@ -627,13 +627,8 @@ class Context:
 
     # ---- the hypotheses of a keyframe's map that other views contradict, removed
     def _cull(self, name, tail, kf_slot, view_slots, Ts, lights, level, views_are_keyframes, dst_slot, max_var, min_support, support_k2, stride, params):
-        vs = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
-        B = vs.size
-        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
-        li = self._lights(lights, B)
-        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        B, vs, T, li, (rows, cols), flt = self._views_args(view_slots, Ts, lights, level, (max_var, min_support, support_k2, stride))
         prm = params if isinstance(params, EllcCullParams) else cull_default_params(**(params or {}))
-        rows, cols = self.level_shape(level)
         res = dict(depth=np.zeros((rows, cols), np.float32), var=np.zeros((rows, cols), np.float32), votes=np.zeros((rows, cols), np.uint32),
                    photo=np.zeros((rows, cols), np.uint8), status=np.zeros((rows, cols), np.uint8))
         st = EllcCullStats()
@@ -657,15 +652,10 @@ class Context:
 
     # ---- poses and depths refined in one step
     def _joint_args(self, view_slots, Ts, lights, level, max_var, min_support, support_k2, stride, params, inv_depth):
-        vs = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
-        B = vs.size
-        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
-        li = self._lights(lights, B)
-        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        B, vs, T, li, shape, flt = self._views_args(view_slots, Ts, lights, level, (max_var, min_support, support_k2, stride))
         prm = params if isinstance(params, EllcJointParams) else joint_default_params(**(params or {}))
-        rows, cols = self.level_shape(level)
-        d = None if inv_depth is None else np.ascontiguousarray(inv_depth, np.float32).reshape(rows, cols)
-        return B, vs, T, li, flt, prm, d, (rows, cols)
+        d = None if inv_depth is None else np.ascontiguousarray(inv_depth, np.float32).reshape(shape)
+        return B, vs, T, li, flt, prm, d, shape
 
     @staticmethod
     def _joint_planes(shape):

@@ -1,7 +1,8 @@
 // ellc_keyframe_cull_depth, ellc_cull_default_params (include/ellc_abi.h): the host side of the vote that removes the hypotheses of a
-// keyframe slot which other views contradict. Included at the end of ellc_hip.hip behind ellc_sweep_impl.hpp:
-// ellc_keyframe_refine_depth's refusals and destination store are used here as they stand; the views' staging (CullView: a view also
-// carries its depth and variance planes), the record, the scratch and the five planes are this call's own.
+// keyframe slot which other views contradict. Included at the end of ellc_hip.hip behind ellc_sweep_impl.hpp: the refusals and the run
+// of a call of K against views (ellc_ring_common.hpp) are used here as they stand; the staged view's two further fields (CullView: a
+// view also carries its depth and variance planes), the parameter refusals, the Args, the record, the scratch and the five planes
+// are this call's own.
 #pragma once
 #include "ellc_ring_common.hpp"
 #include "ellc_refine_impl.hpp"
@@ -26,7 +27,6 @@ ellc_status cull_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int view
   // validated first: a refused call leaves the context and every slot as they were and writes nothing
   if (!view_slots || !T12 || !f || !p) return fail(c, ELLC_ERR_BAD_ARG, w + ": null pointer");
   ELLC_TRY(ring_views_check(c, who, B, ELLC_REFINE_MAX_VIEWS, views_are_kf, level, f, T12, light));
-  const LevelGeom& g = c->geom_h[level];
   if (!std::isfinite(p->agree_k2) || !std::isfinite(p->sigma_i2) || !std::isfinite(p->photo_k) || !(p->agree_k2 >= 0.0f) || !(p->sigma_i2 > 0.0f))
     return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
   if (p->min_support < 1 || p->min_support > B || p->min_in_front < 1 || p->min_in_front > B || p->min_photo < 1 || p->min_photo > B ||
@@ -34,38 +34,24 @@ ellc_status cull_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int view
     return fail(c, ELLC_ERR_BAD_ARG, w + ": a count outside 1..B");
   ELLC_TRY(ring_views_check_slots(c, who, dst, level, kf_slot, B, view_slots, views_are_kf));
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
-  const size_t n = (size_t)g.n;
-  const int blocks = (int)((n + 255) / 256);
-  ELLC_TRY(pair_reserve(c, c->cull, ELLC_REFINE_MAX_VIEWS, sizeof(CullView), sizeof(CullRec), (size_t)blocks));
-  ELLC_TRY(dev_grow(c, &c->cull_planes_d, &c->cull_planes_cap, n, 14));   // two f32 planes, one u32 plane and two u8 planes
-  CullView* vw = (CullView*)c->cull.stage_h;
-  for (int b = 0; b < B; b++) {
-    const size_t e = ring_view_entry(c, level, views_are_kf, view_slots[b]);
-    const bool has_depth = views_are_kf && c->kf_has_depth[view_slots[b]];
-    vw[b].img = views_are_kf ? c->kf_tab_h[e].img : c->fr_tab_h[e].img;
-    vw[b].depth = has_depth ? c->kf_tab_h[e].depth : nullptr;
-    vw[b].var = has_depth ? c->kf_tab_h[e].var : nullptr;
-    std::memcpy(vw[b].T, T12 + (size_t)12 * b, 12 * sizeof(float));
-    vw[b].gain = light ? light[2 * b] : 1.0f;
-    vw[b].offset = light ? light[2 * b + 1] : 0.0f;
-  }
-  ELLC_HIP(c, hipMemcpyAsync(c->cull.stage_d, c->cull.stage_h, (size_t)B * sizeof(CullView), hipMemcpyHostToDevice, c->stream));
+  const size_t n = (size_t)c->geom_h[level].n;
   CullArgs a{};
   a.v = ring_view(c, level, f);
-  a.views = (const CullView*)c->cull.stage_d;
-  a.partials = (CullRec*)c->cull.partials_d;
-  a.out = (CullRec*)c->cull.out_dev_alias;
-  char* planes = (char*)c->cull_planes_d;
-  const size_t cap = c->cull_planes_cap;
-  a.depth = (float*)planes;
-  a.var = (float*)(planes + 4 * cap);
-  a.votes = (uint32_t*)(planes + 8 * cap);
-  a.photo = (uint8_t*)(planes + 12 * cap);
-  a.status = (uint8_t*)(planes + 13 * cap);
-  a.kf_slot = kf_slot;
-  a.B = B;
-  a.blocks = blocks;
-  a.first = 0;
+  ELLC_TRY(ring_views_scratch(c, c->cull, ELLC_REFINE_MAX_VIEWS, n, kf_slot, B, a));
+  ELLC_TRY(dev_grow(c, &c->cull_planes_d, &c->cull_planes_cap, n, 14));   // two f32 planes, one u32 plane and two u8 planes
+  // a view also carries its depth and variance planes, where it is a keyframe slot that holds them (null otherwise: the staging's zeros)
+  ELLC_TRY(ring_views_stage<CullView>(c, c->cull, level, B, views_are_kf, view_slots, T12, light, [&](CullView& vw, int b) {
+    if (!views_are_kf || !c->kf_has_depth[view_slots[b]]) return;
+    const KfLevelDev& k = c->kf_tab_h[ring_view_entry(c, level, 1, view_slots[b])];
+    vw.depth = k.depth;
+    vw.var = k.var;
+  }));
+  const PlaneCarve planes{c->cull_planes_d, c->cull_planes_cap};
+  a.depth = planes.at<float>(0);
+  a.var = planes.at<float>(4);
+  a.votes = planes.at<uint32_t>(8);
+  a.photo = planes.at<uint8_t>(12);
+  a.status = planes.at<uint8_t>(13);
   a.agree_k2 = p->agree_k2;
   a.sp = sqrtf(1.0f / p->sigma_i2);
   a.photo_k = p->photo_k;
@@ -73,21 +59,9 @@ ellc_status cull_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int view
   a.min_judged = p->min_judged;
   a.min_in_front = p->min_in_front;
   a.min_photo = p->min_photo;
-  LaunchTimer t(c, launches_ms);
-  ELLC_TRY(t.begin());
-  hipLaunchKernelGGL(cull_pixels, dim3(blocks), dim3(256), 0, c->stream, a);
-  hipLaunchKernelGGL(cull_finish, dim3(1), dim3(64), 0, c->stream, a);
-  ELLC_HIP(c, hipGetLastError());
-  ELLC_TRY(t.end());
-  ELLC_TRY(ring_views_mark_use(c, B, view_slots, views_are_kf));
-  if (depth) ELLC_HIP(c, hipMemcpyAsync(depth, a.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (var) ELLC_HIP(c, hipMemcpyAsync(var, a.var, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (votes) ELLC_HIP(c, hipMemcpyAsync(votes, a.votes, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (photo) ELLC_HIP(c, hipMemcpyAsync(photo, a.photo, n, hipMemcpyDeviceToHost, c->stream));
-  if (status) ELLC_HIP(c, hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToHost, c->stream));
   const CullRec* rec = (const CullRec*)c->cull.out_h;
-  if (dst >= 0) ELLC_TRY(ring_views_store_dst(c, dst, a.depth, a.var, n, &rec->n[6]));
-  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  const RingFetch fetch[5] = {{depth, a.depth, n * 4}, {var, a.var, n * 4}, {votes, a.votes, n * 4}, {photo, a.photo, n}, {status, a.status, n}};
+  ELLC_TRY(ring_views_run(c, a, cull_pixels, cull_finish, view_slots, views_are_kf, fetch, dst, n, &rec->n[6], launches_ms));
   if (out) {
     std::memset(out, 0, sizeof(*out));
     out->n_kept = rec->n[0]; out->n_retained = rec->n[1];
@@ -96,7 +70,7 @@ ellc_status cull_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int view
     out->sum_agree = rec->s[0]; out->sum_in_front = rec->s[1]; out->sum_behind = rec->s[2];
     out->sum_photo = rec->s[3]; out->sum_photo_bad = rec->s[4];
   }
-  return t.read();
+  return ELLC_OK;
 }
 
 }  // namespace

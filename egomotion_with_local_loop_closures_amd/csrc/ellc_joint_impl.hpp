@@ -1,7 +1,8 @@
 // ellc_keyframe_joint_step / _apply / _refine, ellc_joint_solve, ellc_joint_default_params (include/ellc_abi.h): the host side of the
 // joint refinement of B views' poses and keyframe slot K's inverse depths. Included at the end of ellc_hip.hip behind
-// ellc_ring_common.hpp: the refusals, view images, reader marks and destination store of the calls of K against views are used here;
-// the staging (JointView), the planes and the assembly of the record are this family's own.
+// ellc_ring_common.hpp: the refusals (the parameters' included), staging, plane carve, fetches, reader marks and destination store of
+// the calls of K against views are used here; the staged view's pose step (JointView), the names of the planes, the launches of a
+// step (four) and of an apply (two) with the wait the loop needs between them, and the assembly of the record are this family's own.
 #pragma once
 #include "ellc_ring_common.hpp"
 #include "ellc_sim3_impl.hpp"
@@ -20,12 +21,12 @@ static_assert(sizeof(JointView) == 96 && ELLC_JOINT_VIEWS == ELLC_JOINT_MAX_VIEW
 namespace {
 
 const int JOINT_MAX_REQUESTS = (ELLC_JOINT_MAX_VIEWS * (ELLC_JOINT_MAX_VIEWS + 1)) / 2 + ELLC_JOINT_MAX_VIEWS;   // pairs b <= c, then views
-// the planes of the family in one grow-only buffer of `cap` pixels: ten f32 planes, then five u8 planes
-enum { JP_STATE = 0, JP_D, JP_IH, JP_GD, JP_INV_OUT, JP_DEPTH, JP_VAR, JP_KEPT_DEPTH, JP_KEPT_VAR, JP_F32_PLANES = 10 };
-enum { JP_PSTATUS = 0, JP_VIEWS, JP_STATUS, JP_KEPT_VIEWS, JP_KEPT_STATUS, JP_U8_PLANES };
+// the planes of the family in one grow-only buffer, each named by the bytes a pixel in front of it (PlaneCarve): ten f32 planes (one
+// spare), then five u8 planes
+enum { JP_STATE = 0, JP_D = 4, JP_IH = 8, JP_GD = 12, JP_INV_OUT = 16, JP_DEPTH = 20, JP_VAR = 24, JP_KEPT_DEPTH = 28, JP_KEPT_VAR = 32,
+       JP_PSTATUS = 40, JP_VIEWS, JP_STATUS, JP_KEPT_VIEWS, JP_KEPT_STATUS, JP_BYTES };
 
-float* joint_f32(ellc_ctx* c, int k) { return (float*)((char*)c->joint_planes_d + 4 * c->joint_planes_cap * (size_t)k); }
-uint8_t* joint_u8(ellc_ctx* c, int k) { return (uint8_t*)c->joint_planes_d + c->joint_planes_cap * (size_t)(4 * JP_F32_PLANES + k); }
+PlaneCarve joint_planes(ellc_ctx* c) { return PlaneCarve{c->joint_planes_d, c->joint_planes_cap}; }
 
 // what all three calls refuse, in ellc_keyframe_refine_depth's order; dst is -1 for the step
 ellc_status joint_validate(ellc_ctx* c, const char* who, int kf_slot, int level, int B, int views_are_kf, const int* view_slots, const float* T12,
@@ -33,9 +34,7 @@ ellc_status joint_validate(ellc_ctx* c, const char* who, int kf_slot, int level,
   const std::string w(who);
   if (!view_slots || !T12 || !f || !p) return fail(c, ELLC_ERR_BAD_ARG, w + ": null pointer");
   ELLC_TRY(ring_views_check(c, who, B, ELLC_JOINT_MAX_VIEWS, views_are_kf, level, f, T12, light));
-  if (!std::isfinite(p->sigma_i2) || !std::isfinite(p->huber_k) || !std::isfinite(p->prior_weight) || !std::isfinite(p->max_step_rel) ||
-      !(p->sigma_i2 > 0.0f) || !(p->huber_k > 0.0f) || !(p->prior_weight >= 0.0f) || !(p->max_step_rel > 0.0f) || p->min_views < 1 || p->min_views > B)
-    return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
+  ELLC_TRY(ring_views_check_params(c, who, p, B));
   return ring_views_check_slots(c, who, dst, level, kf_slot, B, view_slots, views_are_kf);
 }
 
@@ -47,17 +46,18 @@ ellc_status joint_prepare(ellc_ctx* c, int kf_slot, int level, int B, const ellc
   a.blocks = (int)((n + 255) / 256);
   ELLC_TRY(pair_reserve(c, c->joint, JOINT_MAX_REQUESTS, sizeof(JointView), sizeof(JointPairRec), (size_t)JOINT_MAX_REQUESTS * a.v.tiles));
   ELLC_TRY(pair_reserve(c, c->joint_count, 1, sizeof(int), sizeof(JointCountRec), (size_t)a.blocks));
-  ELLC_TRY(dev_grow(c, &c->joint_planes_d, &c->joint_planes_cap, n, 4 * JP_F32_PLANES + JP_U8_PLANES));
+  ELLC_TRY(dev_grow(c, &c->joint_planes_d, &c->joint_planes_cap, n, JP_BYTES));
+  const PlaneCarve jp = joint_planes(c);
   a.views = (const JointView*)c->joint.stage_d;
   a.partials = (JointPairRec*)c->joint.partials_d;
   a.out = (JointPairRec*)c->joint.out_dev_alias;
   a.cpartials = (JointCountRec*)c->joint_count.partials_d;
   a.cout = (JointCountRec*)c->joint_count.out_dev_alias;
-  a.d_in = joint_f32(c, JP_STATE);
-  a.d = joint_f32(c, JP_D); a.ih = joint_f32(c, JP_IH); a.gd = joint_f32(c, JP_GD);
-  a.pstatus = joint_u8(c, JP_PSTATUS);
-  a.inv_depth_out = joint_f32(c, JP_INV_OUT); a.depth = joint_f32(c, JP_DEPTH); a.var = joint_f32(c, JP_VAR);
-  a.nviews = joint_u8(c, JP_VIEWS); a.status = joint_u8(c, JP_STATUS);
+  a.d_in = jp.at<float>(JP_STATE);
+  a.d = jp.at<float>(JP_D); a.ih = jp.at<float>(JP_IH); a.gd = jp.at<float>(JP_GD);
+  a.pstatus = jp.at<uint8_t>(JP_PSTATUS);
+  a.inv_depth_out = jp.at<float>(JP_INV_OUT); a.depth = jp.at<float>(JP_DEPTH); a.var = jp.at<float>(JP_VAR);
+  a.nviews = jp.at<uint8_t>(JP_VIEWS); a.status = jp.at<uint8_t>(JP_STATUS);
   a.kf_slot = kf_slot;
   a.B = B;
   a.first = 0;
@@ -72,24 +72,18 @@ ellc_status joint_prepare(ellc_ctx* c, int kf_slot, int level, int B, const ellc
 
 // the state plane: the caller's inverse depths, or zeros (a zero sends a pixel to its own d0)
 ellc_status joint_set_state(ellc_ctx* c, size_t n, const float* inv_depth_in) {
-  if (inv_depth_in) ELLC_HIP(c, hipMemcpyAsync(joint_f32(c, JP_STATE), inv_depth_in, n * 4, hipMemcpyHostToDevice, c->stream));
-  else ELLC_HIP(c, hipMemsetAsync(joint_f32(c, JP_STATE), 0, n * 4, c->stream));
+  const PlaneCarve jp = joint_planes(c);
+  if (inv_depth_in) ELLC_HIP(c, hipMemcpyAsync(jp.at<float>(JP_STATE), inv_depth_in, n * 4, hipMemcpyHostToDevice, c->stream));
+  else ELLC_HIP(c, hipMemsetAsync(jp.at<float>(JP_STATE), 0, n * 4, c->stream));
   return ELLC_OK;
 }
 
-// the views on their way to the device (the stream has been waited for since the staging was last read). xi NULL: no pose steps
+// the views on their way to the device; a view also carries its pose step rounded to f32. xi NULL: no pose steps (the staging's zeros)
 ellc_status joint_stage(ellc_ctx* c, int level, int B, int views_are_kf, const int* view_slots, const float* T12, const float* light, const double* xi) {
-  JointView* vw = (JointView*)c->joint.stage_h;
-  for (int b = 0; b < B; b++) {
-    vw[b] = JointView{};
-    vw[b].img = ring_view_image(c, level, views_are_kf, view_slots[b]);
-    std::memcpy(vw[b].T, T12 + (size_t)12 * b, 12 * sizeof(float));
-    vw[b].gain = light ? light[2 * b] : 1.0f;
-    vw[b].offset = light ? light[2 * b + 1] : 0.0f;
-    for (int k = 0; k < 6; k++) vw[b].xf[k] = xi ? (float)xi[6 * b + k] : 0.0f;
-  }
-  ELLC_HIP(c, hipMemcpyAsync(c->joint.stage_d, c->joint.stage_h, (size_t)B * sizeof(JointView), hipMemcpyHostToDevice, c->stream));
-  return ELLC_OK;
+  return ring_views_stage<JointView>(c, c->joint, level, B, views_are_kf, view_slots, T12, light, [&](JointView& vw, int b) {
+    if (xi)
+      for (int k = 0; k < 6; k++) vw.xf[k] = (float)xi[6 * b + k];
+  });
 }
 
 // One step at the staged views and the state plane: the four launches, the wait, the record. launches_ms (the diagnostic hook only).
@@ -153,18 +147,6 @@ void joint_move_poses(int B, const double* xi, const float* T12, float* T12_out)
   }
 }
 
-// five device planes to the host, each may be NULL
-ellc_status joint_fetch(ellc_ctx* c, size_t n, const float* d_inv, const float* d_depth, const float* d_var, const uint8_t* d_views, const uint8_t* d_status,
-                        float* inv_depth_out, float* depth, float* var, uint8_t* views, uint8_t* status) {
-  if (inv_depth_out) ELLC_HIP(c, hipMemcpyAsync(inv_depth_out, d_inv, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (depth) ELLC_HIP(c, hipMemcpyAsync(depth, d_depth, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (var) ELLC_HIP(c, hipMemcpyAsync(var, d_var, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (views) ELLC_HIP(c, hipMemcpyAsync(views, d_views, n, hipMemcpyDeviceToHost, c->stream));
-  if (status) ELLC_HIP(c, hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c->stream));
-  ELLC_HIP(c, hipStreamSynchronize(c->stream));
-  return ELLC_OK;
-}
-
 ellc_status joint_step_impl(ellc_ctx* c, int kf_slot, int level, int B, int views_are_kf, const int* view_slots, const float* T12, const float* light,
                             const ellc_map_filter* f, const ellc_joint_params* p, const float* inv_depth_in, ellc_joint_normal* out, float* launches_ms) {
   const char* who = "ellc_keyframe_joint_step";
@@ -204,7 +186,9 @@ ellc_status joint_apply_impl(ellc_ctx* c, int kf_slot, int level, int B, int vie
   ELLC_TRY(joint_run_apply(c, a, &st, launches_ms));
   ELLC_TRY(ring_views_mark_use(c, B, view_slots, views_are_kf));
   if (dst >= 0) ELLC_TRY(ring_views_store_dst(c, dst, a.depth, a.var, n, &((const JointCountRec*)c->joint_count.out_h)->n_dense));
-  ELLC_TRY(joint_fetch(c, n, a.inv_depth_out, a.depth, a.var, a.nviews, a.status, inv_depth_out, depth, var, views, status));
+  const RingFetch fetch[5] = {{inv_depth_out, a.inv_depth_out, n * 4}, {depth, a.depth, n * 4}, {var, a.var, n * 4}, {views, a.nviews, n}, {status, a.status, n}};
+  ELLC_TRY(ring_fetch(c, fetch));
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
   std::vector<float> T((size_t)B * 12);
   joint_move_poses(B, xi, T12, T.data());
   std::memcpy(T12_out, T.data(), T.size() * sizeof(float));
@@ -267,6 +251,7 @@ ellc_status ellc_keyframe_joint_refine(ellc_ctx* c, int kf_slot, int level, int 
   const size_t n = (size_t)c->geom_h[level].n, T_len = (size_t)B * 12;
   JointArgs a;
   ELLC_TRY(joint_prepare(c, kf_slot, level, B, filter, params, a));
+  const PlaneCarve jp = joint_planes(c);
   // everything of the call is kept here (and in planes of the call's own) until it has succeeded
   std::vector<float> T(T12_in, T12_in + T_len), Tt(T_len), tT;
   std::vector<ellc_joint_normal> tR;
@@ -288,10 +273,10 @@ ellc_status ellc_keyframe_joint_refine(ellc_ctx* c, int kf_slot, int level, int 
   // the accepted state: the state plane and, for the caller, the planes of the apply that made it. With no accepted trial K's own
   const KfLevelDev& K = c->kf_tab_h[(size_t)level * c->cfg.max_keyframes + kf_slot];
   ELLC_TRY(joint_set_state(c, n, inv_depth_in));
-  ELLC_HIP(c, hipMemcpyAsync(joint_f32(c, JP_KEPT_DEPTH), K.depth, n * 4, hipMemcpyDeviceToDevice, c->stream));
-  ELLC_HIP(c, hipMemcpyAsync(joint_f32(c, JP_KEPT_VAR), K.var, n * 4, hipMemcpyDeviceToDevice, c->stream));
-  ELLC_HIP(c, hipMemsetAsync(joint_u8(c, JP_KEPT_VIEWS), 0, n, c->stream));
-  ELLC_HIP(c, hipMemsetAsync(joint_u8(c, JP_KEPT_STATUS), 0, n, c->stream));
+  ELLC_HIP(c, hipMemcpyAsync(jp.at<float>(JP_KEPT_DEPTH), K.depth, n * 4, hipMemcpyDeviceToDevice, c->stream));
+  ELLC_HIP(c, hipMemcpyAsync(jp.at<float>(JP_KEPT_VAR), K.var, n * 4, hipMemcpyDeviceToDevice, c->stream));
+  ELLC_HIP(c, hipMemsetAsync(jp.at<uint8_t>(JP_KEPT_VIEWS), 0, n, c->stream));
+  ELLC_HIP(c, hipMemsetAsync(jp.at<uint8_t>(JP_KEPT_STATUS), 0, n, c->stream));
   ellc_joint_normal rec, trial;
   ELLC_TRY(traced_step(T, &rec));
   if (trace_accepted) tA[0] = 1;
@@ -305,18 +290,18 @@ ellc_status ellc_keyframe_joint_refine(ellc_ctx* c, int kf_slot, int level, int 
     if (m < (double)eps) break;
     // the trial: the depths stepped at the state's transforms, then the transforms moved
     ELLC_TRY(joint_stage(c, level, B, views_are_keyframes, view_slots, T.data(), light, xi.data()));
-    a.d_in = joint_f32(c, JP_STATE);
+    a.d_in = jp.at<float>(JP_STATE);
     ELLC_TRY(joint_run_apply(c, a, nullptr, nullptr));
     const int trial_dense = ((const JointCountRec*)c->joint_count.out_h)->n_dense;
     joint_move_poses(B, xi.data(), T.data(), Tt.data());
     a.d_in = a.inv_depth_out;
     ELLC_TRY(traced_step(Tt, &trial));
-    a.d_in = joint_f32(c, JP_STATE);
+    a.d_in = jp.at<float>(JP_STATE);
     double c0, c1;
     if (!joint_cost(rec, c0) || !joint_cost(trial, c1) || !(c1 <= c0)) break;
-    const struct { void* to; const void* from; size_t bytes; } keep[5] = {{joint_f32(c, JP_STATE), a.inv_depth_out, n * 4}, {joint_f32(c, JP_KEPT_DEPTH), a.depth, n * 4},
-                                                                         {joint_f32(c, JP_KEPT_VAR), a.var, n * 4}, {joint_u8(c, JP_KEPT_VIEWS), a.nviews, n},
-                                                                         {joint_u8(c, JP_KEPT_STATUS), a.status, n}};
+    const struct { void* to; const void* from; size_t bytes; } keep[5] = {{jp.at<float>(JP_STATE), a.inv_depth_out, n * 4}, {jp.at<float>(JP_KEPT_DEPTH), a.depth, n * 4},
+                                                                         {jp.at<float>(JP_KEPT_VAR), a.var, n * 4}, {jp.at<uint8_t>(JP_KEPT_VIEWS), a.nviews, n},
+                                                                         {jp.at<uint8_t>(JP_KEPT_STATUS), a.status, n}};
     for (int k = 0; k < 5; k++) ELLC_HIP(c, hipMemcpyAsync(keep[k].to, keep[k].from, keep[k].bytes, hipMemcpyDeviceToDevice, c->stream));
     T = Tt;
     rec = trial;
@@ -330,15 +315,17 @@ ellc_status ellc_keyframe_joint_refine(ellc_ctx* c, int kf_slot, int level, int 
     int32_t hint = dense;
     if (!have_dense) {   // K's own planes: counted on a host copy, as ellc_keyframe_set_depth counts
       std::vector<float> z(n);
-      ELLC_HIP(c, hipMemcpyAsync(z.data(), joint_f32(c, JP_KEPT_DEPTH), n * 4, hipMemcpyDeviceToHost, c->stream));
+      ELLC_HIP(c, hipMemcpyAsync(z.data(), jp.at<float>(JP_KEPT_DEPTH), n * 4, hipMemcpyDeviceToHost, c->stream));
       ELLC_HIP(c, hipStreamSynchronize(c->stream));
       hint = 0;
       for (size_t i = 0; i < n; i++) hint += z[i] > 0.0f ? 1 : 0;
     }
-    ELLC_TRY(ring_views_store_dst(c, dst_kf_slot, joint_f32(c, JP_KEPT_DEPTH), joint_f32(c, JP_KEPT_VAR), n, &hint));
+    ELLC_TRY(ring_views_store_dst(c, dst_kf_slot, jp.at<float>(JP_KEPT_DEPTH), jp.at<float>(JP_KEPT_VAR), n, &hint));
   }
-  ELLC_TRY(joint_fetch(c, n, joint_f32(c, JP_STATE), joint_f32(c, JP_KEPT_DEPTH), joint_f32(c, JP_KEPT_VAR), joint_u8(c, JP_KEPT_VIEWS),
-                       joint_u8(c, JP_KEPT_STATUS), inv_depth_out, depth, var, views, status));
+  const RingFetch fetch[5] = {{inv_depth_out, jp.at<float>(JP_STATE), n * 4}, {depth, jp.at<float>(JP_KEPT_DEPTH), n * 4}, {var, jp.at<float>(JP_KEPT_VAR), n * 4},
+                              {views, jp.at<uint8_t>(JP_KEPT_VIEWS), n}, {status, jp.at<uint8_t>(JP_KEPT_STATUS), n}};
+  ELLC_TRY(ring_fetch(c, fetch));
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
   std::memcpy(T12_out, T.data(), T_len * sizeof(float));
   *out = rec;
   if (iters_out) *iters_out = iters;

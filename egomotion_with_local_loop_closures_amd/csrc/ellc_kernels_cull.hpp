@@ -7,17 +7,14 @@
 // record per block (pair_store_block), cull_finish sums the blocks (pair_finish).
 #pragma once
 #include <float.h>
-#include "ellc_kernels_sim3.hpp"
+#include "ellc_kernels_views.hpp"
 
 namespace ellc {
 
 // one view as the kernel reads it: 80 bytes, staged once per call, read with a wave-uniform index (scalar loads)
-struct CullView {
-  const uint8_t* img;        // the view's image on the level (stored pitch sw)
+struct CullView : RefineView {
   const float* depth;        // the view's depth and variance planes on the level (dense), both null where the view has none: a frame
   const float* var;          //   slot, or a keyframe slot that holds an image only
-  float T[12];               // K's camera -> the view's
-  float gain, offset;
 };
 
 // the stats as the kernels write them; a block's partial record has the same layout
@@ -68,27 +65,22 @@ __device__ __forceinline__ void rec_wave_sum(CullRec& r) {
 
 // grid (256-pixel blocks of the level): thread t of block k owns pixel 256 k + t
 __global__ __launch_bounds__(256) void cull_pixels(CullArgs a) {
-  const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + a.kf_slot];
-  const LevelGeom& g = a.v.geom[a.v.level];
-  const ELLC_GLOBAL float* depth = gptr(K.depth);
-  const ELLC_GLOBAL float* var = gptr(K.var);
-  const ELLC_GLOBAL uint8_t* img = gptr(K.img);
-  const int cols = g.cols, rows = g.rows, sw = g.sw;
-  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  const KfPixels k = kf_pixels(a.v, a.kf_slot, block_pixel());
+  const int i = k.i;
   CullRec r;
   rec_zero(r);
-  if (i < cols * rows) {
-    float Zout = depth[(unsigned)i], Vout = var[(unsigned)i];   // every pixel that is not culled keeps K's own bits
+  if (i < k.cols * k.rows) {
+    float Zout = k.depth[(unsigned)i], Vout = k.var[(unsigned)i];   // every pixel that is not culled keeps K's own bits
     int status = 0, na = 0, nf = 0, nh = 0, np = 0, nbad = 0;
     MapPixel p;
-    if (map_keep(a.v, depth, var, cols, rows, i, p)) {
+    if (map_keep(a.v, k.depth, k.var, k.cols, k.rows, i, p)) {
       r.n[0]++;
 #pragma unroll 1
       for (int b = 0; b < a.B; b++) {
         const CullView& vw = a.views[b];   // wave-uniform: scalar loads
         const RenderT T = load_T12(vw.T);
         RenderCand c;
-        if (!render_candidate(g, T, 0u, i, p.x, p.y, p.Z, p.V, c)) continue;   // (the request number only enters the key, which is not used here)
+        if (!render_candidate(k.g, T, 0u, i, p.x, p.y, p.Z, p.V, c)) continue;   // (the request number only enters the key, which is not used here)
         bool behind = false;
         if (vw.depth) {   // wave-uniform
           const ELLC_GLOBAL float* tdepth = (const ELLC_GLOBAL float*)vw.depth;
@@ -105,11 +97,10 @@ __global__ __launch_bounds__(256) void cull_pixels(CullArgs a) {
         }
         if (a.photo_k > 0.0f && !behind) {
           float Iw, gx, gy, Is;
-          if (sim3_photo_taps(c, p, img, (const ELLC_GLOBAL uint8_t*)vw.img, cols, rows, sw, Iw, gx, gy, Is)) {
-            const float rp = Iw - (vw.gain * Is + vw.offset);
-            const float e = fabsf(rp) * a.sp;
+          if (sim3_photo_taps(c, p, k.img, (const ELLC_GLOBAL uint8_t*)vw.img, k.cols, k.rows, k.sw, Iw, gx, gy, Is)) {
+            const PhotoTerm ph = photo_term(Iw, Is, vw.gain, vw.offset, 1.0f, a.sp, FLT_MAX);   // (e alone is read: no weight is asked for)
             np++;
-            if (!(e <= a.photo_k)) nbad++;
+            if (!(ph.e <= a.photo_k)) nbad++;
           }
         }
       }
@@ -119,9 +110,7 @@ __global__ __launch_bounds__(256) void cull_pixels(CullArgs a) {
       else if (a.photo_k > 0.0f && np >= a.min_photo && 2 * nbad > np) status = 4;
       else if (na + nf + nh == 0 && np == 0) status = 5;
       else status = 1;
-      // (compared, not indexed: an index known at run time only sends the record from registers into LDS)
-#pragma unroll
-      for (int k = 1; k <= 5; k++) r.n[k] += (status == k) ? 1 : 0;
+      rec_count_status<1, 5>(r.n, status);
       r.s[0] = na; r.s[1] = nf; r.s[2] = nh; r.s[3] = np; r.s[4] = nbad;
       if (status >= 2 && status <= 4) { Zout = 0.0f; Vout = -1.0f; }
     }

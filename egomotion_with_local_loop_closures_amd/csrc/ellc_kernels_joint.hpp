@@ -1,6 +1,6 @@
 // ellc_keyframe_joint_step / _apply: one photometric Gauss-Newton step over the SE(3) of B <= 8 views and the inverse depths of keyframe
 // slot K's kept pixels together, the depths eliminated per pixel (no reference counterpart: the reference optimises poses only,
-// GlobalOptimize.cpp). Three kernels over refine_evaluate's photometric lines, which stay as they are:
+// GlobalOptimize.cpp). Three kernels over view_term (ellc_kernels_views.hpp), the term refine_evaluate sums too:
 //   joint_pixels  one pixel per thread (refine_pixels' shape): every view's term at the pixel's d, the pixel's status, ih = 1 / Ht and gd
 //                 into planes, the counts and the two chi2 sums through pair_store_block / pair_finish;
 //   joint_pairs   grid (tiles of the level) x (view pairs b <= c, then the B views), sim3_pass's pixel layout: a block recomputes the
@@ -12,7 +12,7 @@
 //   joint_apply_pixels  one pixel per thread: the evaluation again, the back-substituted step and the five planes.
 #pragma once
 #include <float.h>
-#include "ellc_kernels_sim3.hpp"
+#include "ellc_kernels_views.hpp"
 
 namespace ellc {
 
@@ -20,10 +20,7 @@ namespace ellc {
 #define ELLC_JOINT_PAIR_SUMS 42   // 36 of u v^T (row-major), 6 of u r
 
 // one view as the kernels read it: 96 bytes, staged once per call, read with a wave-uniform index (scalar loads)
-struct JointView {
-  const uint8_t* img;        // the view's image on the level (stored pitch sw)
-  float T[12];               // K's camera -> the view's
-  float gain, offset;
+struct JointView : RefineView {
   float xf[6];               // the view's pose step rounded to f32 (joint_apply_pixels only)
   float pad_[2];
 };
@@ -114,31 +111,6 @@ __device__ __forceinline__ void rec_wave_sum(JointPairRec& r) {
   }
 }
 
-// One view's term at pixel i = (p.x, p.y) of K at the depth Z = 1 / d: refine_evaluate's lines (rp, wp, Jd is its J) and the six pose
-// entries of sim3_pass. False: the view has no candidate or no four taps there.
-struct JointTerm {
-  float rp, wp, Jd, Jp[6];
-};
-
-__device__ __forceinline__ bool joint_term(const JointArgs& a, const LevelGeom& g, const ELLC_GLOBAL uint8_t* img, const JointView& vw, const MapPixel& p,
-                                           int i, float Z, int cols, int rows, int sw, JointTerm& t) {
-  const RenderT T = load_T12(vw.T);
-  RenderCand c;
-  if (!render_candidate(g, T, 0u, i, p.x, p.y, Z, p.V, c)) return false;   // (the request number only enters the key, which is not used here)
-  float Iw, gx, gy, Is;
-  if (!sim3_photo_taps(c, p, img, (const ELLC_GLOBAL uint8_t*)vw.img, cols, rows, sw, Iw, gx, gy, Is)) return false;
-  t.rp = Iw - (vw.gain * Is + vw.offset);
-  const float A = (gx * g.fx) * c.nid, Bv = (gy * g.fy) * c.nid;
-  const float Cq = -(((A * c.x) + (Bv * c.y)) * c.nid);
-  t.Jp[0] = Cq * c.y - Bv * c.z; t.Jp[1] = A * c.z - Cq * c.x; t.Jp[2] = Bv * c.x - A * c.y; t.Jp[3] = A; t.Jp[4] = Bv; t.Jp[5] = Cq;
-  const float e = fabsf(t.rp) * a.sp;
-  t.wp = a.w0;
-  if (!(e <= a.huber_k)) t.wp = a.w0 * (a.huber_k / e);
-  const float qx = c.x - T.t[3], qy = c.y - T.t[7], qz = c.z - T.t[11];
-  t.Jd = -(Z * (((A * qx) + (Bv * qy)) + (Cq * qz)));
-  return true;
-}
-
 // What a pixel that takes part is at its d: the evaluation over the views in ascending b, the status (1 USED, 2 TOO_FEW_VIEWS,
 // 3 NO_INFORMATION), ih and gd; with STEP also q, the pose steps' pull on the pixel: q = 0, then q = q + c_b[k] * xf_b[k], b and k ascending.
 struct JointPixel {
@@ -148,13 +120,12 @@ struct JointPixel {
 };
 
 template <bool STEP>
-__device__ __forceinline__ void joint_pixel(const JointArgs& a, const LevelGeom& g, const ELLC_GLOBAL uint8_t* img, const MapPixel& p, int i, int cols,
-                                            int rows, int sw, JointPixel& o) {
+__device__ __forceinline__ void joint_pixel(const JointArgs& a, const KfPixels& k, const MapPixel& p, JointPixel& o) {
   o.d0 = 1.0f / p.Z;
   o.hp = (a.prior_weight == 0.0f) ? 0.0f : a.prior_weight / p.V;
   o.d = o.d0;
   if (a.d_in) {
-    const float di = a.d_in[(unsigned)i];
+    const float di = a.d_in[(unsigned)k.i];
     if (di > 0.0f && di <= FLT_MAX) o.d = di;
   }
   const float Z = 1.0f / o.d;
@@ -163,15 +134,15 @@ __device__ __forceinline__ void joint_pixel(const JointArgs& a, const LevelGeom&
 #pragma unroll 1
   for (int b = 0; b < a.B; b++) {
     const JointView& vw = a.views[b];   // wave-uniform: scalar loads
-    JointTerm t;
-    if (!joint_term(a, g, img, vw, p, i, Z, cols, rows, sw, t)) continue;
+    ViewTerm t;
+    if (!view_term<true>(a, k, vw, p, Z, t)) continue;
     const float wJ = t.wp * t.Jd;
     H = H + wJ * t.Jd;
     gs = gs + wJ * t.rp;
     o.E = o.E + (t.rp * t.rp) * t.wp;
     if (STEP) {
 #pragma unroll
-      for (int k = 0; k < 6; k++) o.q = o.q + (wJ * t.Jp[k]) * vw.xf[k];
+      for (int l = 0; l < 6; l++) o.q = o.q + (wJ * t.Jp[l]) * vw.xf[l];
     }
     o.n++;
     o.mask |= 1u << b;
@@ -185,35 +156,24 @@ __device__ __forceinline__ void joint_pixel(const JointArgs& a, const LevelGeom&
   o.ih = 1.0f / Ht;
 }
 
-// K's planes and the pixel's taking part, for the two per-pixel kernels
-#define ELLC_JOINT_PIXEL_PROLOGUE                                              \
-  const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + a.kf_slot];        \
-  const LevelGeom& g = a.v.geom[a.v.level];                                    \
-  const ELLC_GLOBAL float* depth = gptr(K.depth);                              \
-  const ELLC_GLOBAL float* var = gptr(K.var);                                  \
-  const ELLC_GLOBAL uint8_t* img = gptr(K.img);                                \
-  const int cols = g.cols, rows = g.rows, sw = g.sw;                           \
-  const int i = (int)(blockIdx.x * 256u + threadIdx.x);                        \
-  JointCountRec r;                                                             \
-  rec_zero(r)
-
 // grid (256-pixel blocks of the level): thread t of block k owns pixel 256 k + t
 __global__ __launch_bounds__(256) void joint_pixels(JointArgs a) {
-  ELLC_JOINT_PIXEL_PROLOGUE;
-  if (i < cols * rows) {
+  const KfPixels k = kf_pixels(a.v, a.kf_slot, block_pixel());
+  const int i = k.i;
+  JointCountRec r;
+  rec_zero(r);
+  if (i < k.cols * k.rows) {
     float d = 0.0f, ih = 0.0f, gd = 0.0f;
     int status = 0;
     MapPixel p;
-    if (map_keep(a.v, depth, var, cols, rows, i, p)) {
+    if (map_keep(a.v, k.depth, k.var, k.cols, k.rows, i, p)) {
       r.n[0]++;
       if (a.prior_weight == 0.0f || p.V > 0.0f) {
         r.n[1]++;
         JointPixel o;
-        joint_pixel<false>(a, g, img, p, i, cols, rows, sw, o);
+        joint_pixel<false>(a, k, p, o);
         d = o.d; ih = o.ih; gd = o.gd; status = o.status;
-        // (compared, not indexed: an index known at run time only sends the record from registers into LDS)
-#pragma unroll
-        for (int k = 1; k <= 3; k++) r.n[1 + k] += (status == k) ? 1 : 0;
+        rec_count_status<1, 3>(r.n + 1, status);
         if (status == 1) {
           r.n_terms = o.n;
 #pragma unroll
@@ -238,11 +198,8 @@ __global__ __launch_bounds__(64) void joint_count_finish(JointArgs a) {
 // grid (tiles of the level) x (B (B + 1) / 2 + B), map_count's pixel layout; blockIdx.y counts the pairs (b, c), b <= c, by rows, then
 // the views. Only joint_pixels' planes and K's variance and image are read: a used pixel was kept.
 __global__ __launch_bounds__(256) void joint_pairs(JointArgs a) {
-  const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + a.kf_slot];
-  const LevelGeom& g = a.v.geom[a.v.level];
-  const ELLC_GLOBAL float* var = gptr(K.var);
-  const ELLC_GLOBAL uint8_t* img = gptr(K.img);
-  const int cols = g.cols, rows = g.rows, sw = g.sw;
+  const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
+  KfPixels kp = kf_pixels(a.v, a.kf_slot, base);   // (.i moves with j below)
   const int n_pairs = (a.B * (a.B + 1)) / 2;
   int b = 0, c = 0;
   const bool per_view = (int)blockIdx.y >= n_pairs;
@@ -257,20 +214,19 @@ __global__ __launch_bounds__(256) void joint_pairs(JointArgs a) {
   c = __builtin_amdgcn_readfirstlane(c);
   const JointView& vb = a.views[b];   // block-uniform: scalar loads
   const JointView& vc = a.views[c];
-  const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
   JointPairRec r;
   rec_zero(r);
 #pragma unroll 1
   for (int j = 0; j < 8; j++) {
-    const int i = base + j * 256;
+    const int i = kp.i = base + j * 256;
     // a pixel without a term keeps these zeros and adds exact zeros below: the accumulators are updated in one place (sim3_pass)
     float u[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rr = 0.0f;
-    if (i < cols * rows && a.pstatus[(unsigned)i] == 1) {
+    if (i < kp.cols * kp.rows && a.pstatus[(unsigned)i] == 1) {
       MapPixel p;
-      p.y = i / cols; p.x = i - p.y * cols; p.V = var[(unsigned)i]; p.Z = 0.0f; p.support = 0;
+      p.y = i / kp.cols; p.x = i - p.y * kp.cols; p.V = kp.var[(unsigned)i]; p.Z = 0.0f; p.support = 0;
       const float Z = 1.0f / a.d[(unsigned)i];
-      JointTerm tb;
-      if (joint_term(a, g, img, vb, p, i, Z, cols, rows, sw, tb)) {
+      ViewTerm tb;
+      if (view_term<true>(a, kp, vb, p, Z, tb)) {
         if (per_view) {
 #pragma unroll
           for (int k = 0; k < 6; k++) { u[k] = tb.wp * tb.Jp[k]; v[k] = tb.Jp[k]; }
@@ -285,8 +241,8 @@ __global__ __launch_bounds__(256) void joint_pairs(JointArgs a) {
             for (int k = 0; k < 6; k++) v[k] = cb[k];
             rr = a.gd[(unsigned)i];
           } else {
-            JointTerm tc;
-            if (joint_term(a, g, img, vc, p, i, Z, cols, rows, sw, tc)) {
+            ViewTerm tc;
+            if (view_term<true>(a, kp, vc, p, Z, tc)) {
               const float wJc = tc.wp * tc.Jd;
 #pragma unroll
               for (int k = 0; k < 6; k++) v[k] = wJc * tc.Jp[k];
@@ -322,17 +278,20 @@ __global__ __launch_bounds__(64) void joint_pair_finish(JointArgs a) {
 
 // grid (256-pixel blocks of the level): the evaluation again, the pixel's step from the views' pose steps, the five planes
 __global__ __launch_bounds__(256) void joint_apply_pixels(JointArgs a) {
-  ELLC_JOINT_PIXEL_PROLOGUE;
-  if (i < cols * rows) {
-    float Zout = depth[(unsigned)i], Vout = var[(unsigned)i], dout = 0.0f;   // every pixel that is not stepped keeps K's own bits
+  const KfPixels k = kf_pixels(a.v, a.kf_slot, block_pixel());
+  const int i = k.i;
+  JointCountRec r;
+  rec_zero(r);
+  if (i < k.cols * k.rows) {
+    float Zout = k.depth[(unsigned)i], Vout = k.var[(unsigned)i], dout = 0.0f;   // every pixel that is not stepped keeps K's own bits
     int status = 0, nv = 0;
     MapPixel p;
-    if (map_keep(a.v, depth, var, cols, rows, i, p)) {
+    if (map_keep(a.v, k.depth, k.var, k.cols, k.rows, i, p)) {
       r.n[0]++;
       if (a.prior_weight == 0.0f || p.V > 0.0f) {
         r.n[1]++;
         JointPixel o;
-        joint_pixel<true>(a, g, img, p, i, cols, rows, sw, o);
+        joint_pixel<true>(a, k, p, o);
         status = o.status; nv = o.n; dout = o.d;
         if (status == 1) {
           const float delta = -((o.gd + o.q) * o.ih);
@@ -345,8 +304,7 @@ __global__ __launch_bounds__(256) void joint_apply_pixels(JointArgs a) {
             Vout = o.ih;
           }
         }
-#pragma unroll
-        for (int k = 1; k <= 4; k++) r.n[1 + k] += (status == k) ? 1 : 0;
+        rec_count_status<1, 4>(r.n + 1, status);
       }
     }
     a.inv_depth_out[(unsigned)i] = dout;

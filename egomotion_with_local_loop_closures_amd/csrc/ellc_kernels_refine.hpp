@@ -8,16 +8,9 @@
 // from the level's size alone.
 #pragma once
 #include <float.h>
-#include "ellc_kernels_sim3.hpp"
+#include "ellc_kernels_views.hpp"
 
 namespace ellc {
-
-// one view as the kernel reads it: 64 bytes, staged once per call, read with a wave-uniform index (scalar loads)
-struct RefineView {
-  const uint8_t* img;        // the view's image on the level (stored pitch sw)
-  float T[12];               // K's camera -> the view's
-  float gain, offset;
-};
 
 // the stats as the kernels write them; a block's partial record has the same layout
 struct RefineRec {
@@ -66,54 +59,34 @@ __device__ __forceinline__ void rec_wave_sum(RefineRec& r) {
   }
 }
 
-// Rule 2: H, g, E and n of pixel i = (p.x, p.y) of K at the inverse depth d, the views in ascending b. The photometric lines (A, Bv,
-// Cq, e, wp) are those of sim3_pass, which stays as it is.
-__device__ __forceinline__ void refine_evaluate(const RefineArgs& a, const LevelGeom& g, const ELLC_GLOBAL uint8_t* img, const MapPixel& p, int i,
-                                                float d, int cols, int rows, int sw, float& H, float& gs, float& E, int& n) {
+// Rule 2: H, g, E and n of pixel k.i = (p.x, p.y) of K at the inverse depth d, the views in ascending b
+__device__ __forceinline__ void refine_evaluate(const RefineArgs& a, const KfPixels& k, const MapPixel& p, float d, float& H, float& gs, float& E, int& n) {
   const float Z = 1.0f / d;
-  const float fx = g.fx, fy = g.fy;
   H = 0.0f; gs = 0.0f; E = 0.0f; n = 0;
 #pragma unroll 1
   for (int b = 0; b < a.B; b++) {
-    const RefineView& vw = a.views[b];   // wave-uniform: scalar loads
-    const RenderT T = load_T12(vw.T);
-    RenderCand c;
-    if (!render_candidate(g, T, 0u, i, p.x, p.y, Z, p.V, c)) continue;   // (the request number only enters the key, which is not used here)
-    float Iw, gx, gy, Is;
-    if (!sim3_photo_taps(c, p, img, (const ELLC_GLOBAL uint8_t*)vw.img, cols, rows, sw, Iw, gx, gy, Is)) continue;
-    const float rp = Iw - (vw.gain * Is + vw.offset);
-    const float A = (gx * fx) * c.nid, Bv = (gy * fy) * c.nid;
-    const float Cq = -(((A * c.x) + (Bv * c.y)) * c.nid);
-    const float e = fabsf(rp) * a.sp;
-    float wp = a.w0;
-    if (!(e <= a.huber_k)) wp = a.w0 * (a.huber_k / e);
-    // dP'/dd = -Z (P' - t): the derivative of Iw by the inverse depth
-    const float qx = c.x - T.t[3], qy = c.y - T.t[7], qz = c.z - T.t[11];
-    const float J = -(Z * (((A * qx) + (Bv * qy)) + (Cq * qz)));
-    const float wJ = wp * J;
-    H = H + wJ * J;
-    gs = gs + wJ * rp;
-    E = E + (rp * rp) * wp;
+    ViewTerm t;
+    t.rp = 0.0f; t.wp = 0.0f; t.Jd = 0.0f;   // (set before the call: refine_pixels keeps its 58 registers with it, NOTEBOOK.md)
+    if (!view_term<false>(a, k, a.views[b], p, Z, t)) continue;   // (a.views[b] is wave-uniform: scalar loads)
+    const float wJ = t.wp * t.Jd;
+    H = H + wJ * t.Jd;
+    gs = gs + wJ * t.rp;
+    E = E + (t.rp * t.rp) * t.wp;
     n++;
   }
 }
 
 // grid (256-pixel blocks of the level): thread t of block k owns pixel 256 k + t
 __global__ __launch_bounds__(256) void refine_pixels(RefineArgs a) {
-  const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + a.kf_slot];
-  const LevelGeom& g = a.v.geom[a.v.level];
-  const ELLC_GLOBAL float* depth = gptr(K.depth);
-  const ELLC_GLOBAL float* var = gptr(K.var);
-  const ELLC_GLOBAL uint8_t* img = gptr(K.img);
-  const int cols = g.cols, rows = g.rows, sw = g.sw;
-  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  const KfPixels k = kf_pixels(a.v, a.kf_slot, block_pixel());
+  const int i = k.i;
   RefineRec r;
   rec_zero(r);
-  if (i < cols * rows) {
-    float Zout = depth[(unsigned)i], Vout = var[(unsigned)i];   // every pixel that is not refined keeps K's own bits
+  if (i < k.cols * k.rows) {
+    float Zout = k.depth[(unsigned)i], Vout = k.var[(unsigned)i];   // every pixel that is not refined keeps K's own bits
     int status = 0, nv = 0;
     MapPixel p;
-    if (map_keep(a.v, depth, var, cols, rows, i, p)) {
+    if (map_keep(a.v, k.depth, k.var, k.cols, k.rows, i, p)) {
       r.n[0]++;
       if (a.prior_weight == 0.0f || p.V > 0.0f) {
         r.n[1]++;
@@ -126,7 +99,7 @@ __global__ __launch_bounds__(256) void refine_pixels(RefineArgs a) {
         for (int it = 0; it <= a.n_iter; it++) {
           float H, gs, E;
           int n;
-          refine_evaluate(a, g, img, p, i, d, cols, rows, sw, H, gs, E, n);
+          refine_evaluate(a, k, p, d, H, gs, E, n);
           nv = n;
           if (it == 0) { E0 = E; n0 = n; }
           const float Ht = H + hp;
@@ -152,10 +125,7 @@ __global__ __launch_bounds__(256) void refine_pixels(RefineArgs a) {
           if (!(dn > 0.0f && dn <= FLT_MAX && fabsf(step) <= a.max_step_rel * d)) { status = 4; break; }
           d = dn;
         }
-        // (status is 1..6 here: the loop always ends through a break. Compared, not indexed: an index known at run time only sends
-        // the record from registers into LDS)
-#pragma unroll
-        for (int k = 1; k <= 6; k++) r.n[1 + k] += (status == k) ? 1 : 0;
+        rec_count_status<1, 6>(r.n + 1, status);   // (status is 1..6 here: the loop always ends through a break)
       }
     }
     a.depth[(unsigned)i] = Zout;

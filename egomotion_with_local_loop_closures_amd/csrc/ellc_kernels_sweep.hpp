@@ -7,7 +7,7 @@
 // is carried in eight registers while the samples go by ONCE (sweep_track): no per-thread array, no LDS, no second pass.
 #pragma once
 #include <float.h>
-#include "ellc_kernels_refine.hpp"
+#include "ellc_kernels_views.hpp"
 
 namespace ellc {
 
@@ -59,26 +59,21 @@ __device__ __forceinline__ void rec_wave_sum(SweepRec& r) {
 }
 
 // Rule 3, one pattern pixel (x, y) of K at the depth Z in the view (T, vw): its term c = (rp * rp) * wp, or false where the pattern
-// pixel has no candidate or no four taps there. The photometric lines (rp, e, wp) are those of sim3_pass and refine_evaluate.
-__device__ __forceinline__ bool sweep_term(const SweepArgs& a, const LevelGeom& g, const RenderT& T, const RefineView& vw, const ELLC_GLOBAL uint8_t* img,
-                                           int x, int y, float Z, int cols, int rows, int sw, float& c) {
+// pixel has no candidate or no four taps there.
+__device__ __forceinline__ bool sweep_term(const SweepArgs& a, const KfPixels& k, const RenderT& T, const RefineView& vw, int x, int y, float Z, float& c) {
   MapPixel p;
   p.Z = Z; p.V = 0.0f; p.x = x; p.y = y; p.support = 0;
   RenderCand rc;
-  if (!render_candidate(g, T, 0u, 0, x, y, Z, 0.0f, rc)) return false;   // (request and raster index only enter the key, which is not used here)
+  if (!render_candidate(k.g, T, 0u, 0, x, y, Z, 0.0f, rc)) return false;   // (request and raster index only enter the key, which is not used here)
   float Iw, gx, gy, Is;
-  if (!sim3_photo_taps(rc, p, img, (const ELLC_GLOBAL uint8_t*)vw.img, cols, rows, sw, Iw, gx, gy, Is)) return false;
-  const float rp = Iw - (vw.gain * Is + vw.offset);
-  const float e = fabsf(rp) * a.sp;
-  float wp = a.w0;
-  if (!(e <= a.huber_k)) wp = a.w0 * (a.huber_k / e);
-  c = (rp * rp) * wp;
+  if (!sim3_photo_taps(rc, p, k.img, (const ELLC_GLOBAL uint8_t*)vw.img, k.cols, k.rows, k.sw, Iw, gx, gy, Is)) return false;
+  const PhotoTerm ph = photo_term(Iw, Is, vw.gain, vw.offset, a.w0, a.sp, a.huber_k);
+  c = (ph.rp * ph.rp) * ph.wp;
   return true;
 }
 
 // Rule 3: cost and n of pixel (px, py) of K at the depth Z, the views in ascending b, the pattern in the header's order
-__device__ __forceinline__ void sweep_cost(const SweepArgs& a, const LevelGeom& g, const ELLC_GLOBAL uint8_t* img, int px, int py, float Z, int cols,
-                                           int rows, int sw, float& cost, int& n) {
+__device__ __forceinline__ void sweep_cost(const SweepArgs& a, const KfPixels& k, int px, int py, float Z, float& cost, int& n) {
   float E = 0.0f;
   n = 0;
 #pragma unroll 1
@@ -86,11 +81,11 @@ __device__ __forceinline__ void sweep_cost(const SweepArgs& a, const LevelGeom& 
     const RefineView& vw = a.views[b];   // wave-uniform: scalar loads
     const RenderT T = load_T12(vw.T);
     float c0, c1, c2, c3, c4;
-    if (!sweep_term(a, g, T, vw, img, px, py, Z, cols, rows, sw, c0)) continue;
-    if (!sweep_term(a, g, T, vw, img, px + 1, py, Z, cols, rows, sw, c1)) continue;
-    if (!sweep_term(a, g, T, vw, img, px - 1, py, Z, cols, rows, sw, c2)) continue;
-    if (!sweep_term(a, g, T, vw, img, px, py + 1, Z, cols, rows, sw, c3)) continue;
-    if (!sweep_term(a, g, T, vw, img, px, py - 1, Z, cols, rows, sw, c4)) continue;
+    if (!sweep_term(a, k, T, vw, px, py, Z, c0)) continue;
+    if (!sweep_term(a, k, T, vw, px + 1, py, Z, c1)) continue;
+    if (!sweep_term(a, k, T, vw, px - 1, py, Z, c2)) continue;
+    if (!sweep_term(a, k, T, vw, px, py + 1, Z, c3)) continue;
+    if (!sweep_term(a, k, T, vw, px, py - 1, Z, c4)) continue;
     E = E + ((((c0 + c1) + c2) + c3) + c4);
     n++;
   }
@@ -123,17 +118,13 @@ __device__ __forceinline__ void sweep_track(SweepTrack& t, int k, float cost, in
 
 // grid (256-pixel blocks of the level): thread t of block k owns pixel 256 k + t
 __global__ __launch_bounds__(256) void sweep_pixels(SweepArgs a) {
-  const KfLevelDev& K = a.v.kf_tab[a.v.level * a.v.max_kf + a.kf_slot];
-  const LevelGeom& g = a.v.geom[a.v.level];
-  const ELLC_GLOBAL float* depth = gptr(K.depth);
-  const ELLC_GLOBAL float* var = gptr(K.var);
-  const ELLC_GLOBAL uint8_t* img = gptr(K.img);
-  const int cols = g.cols, rows = g.rows, sw = g.sw;
-  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  const KfPixels kp = kf_pixels(a.v, a.kf_slot, block_pixel());
+  const ELLC_GLOBAL uint8_t* img = kp.img;
+  const int cols = kp.cols, rows = kp.rows, sw = kp.sw, i = kp.i;
   SweepRec r;
   rec_zero(r);
   if (i < cols * rows) {
-    float Zout = depth[(unsigned)i], Vout = var[(unsigned)i];   // every pixel that gets no hypothesis keeps K's own bits
+    float Zout = kp.depth[(unsigned)i], Vout = kp.var[(unsigned)i];   // every pixel that gets no hypothesis keeps K's own bits
     int status = 0, nv = 0;
     const int py = i / cols, px = i - py * cols;
     bool swept = false;
@@ -153,7 +144,7 @@ __global__ __launch_bounds__(256) void sweep_pixels(SweepArgs a) {
         const float d = a.d_min + (float)k * a.dstep;   // rule 2
         float cost;
         int n;
-        sweep_cost(a, g, img, px, py, 1.0f / d, cols, rows, sw, cost, n);
+        sweep_cost(a, kp, px, py, 1.0f / d, cost, n);
         sweep_track(t, k, cost, n, n >= a.min_views && cost <= FLT_MAX);
       }
       // rule 4
@@ -178,9 +169,7 @@ __global__ __launch_bounds__(256) void sweep_pixels(SweepArgs a) {
           }
         }
       }
-      // (compared, not indexed: an index known at run time only sends the record from registers into LDS)
-#pragma unroll
-      for (int k = 1; k <= 6; k++) r.n[1 + k] += (status == k) ? 1 : 0;
+      rec_count_status<1, 6>(r.n + 1, status);
     }
     a.depth[(unsigned)i] = Zout;
     a.var[(unsigned)i] = Vout;

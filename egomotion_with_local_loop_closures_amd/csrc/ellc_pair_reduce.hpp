@@ -1,6 +1,7 @@
 // The reduction tail of the ring's pair calls (ellc_keyframe_depth_consistency, ellc_keyframe_sim3_step, ellc_keyframe_trial_propagate,
 // ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_joint_step's view pairs) and of the stats of ellc_keyframe_refine_depth and
-// its kin (_sweep_depth, _cull_depth, _joint_step / _apply: one request, a partial per 256-pixel block):
+// its kin (_sweep_depth, _cull_depth, _joint_step / _apply: one request, a partial per 256-pixel block; what their pixel kernels share
+// in front of this tail is in ellc_kernels_views.hpp):
 // a pass kernel leaves one partial record per (request, tile), a finish kernel sums a request's tiles. No waiting between blocks, no
 // floating-point atomics. A record type takes part through three plain overloads in namespace ellc:
 //   rec_zero(Rec&)             every field zero

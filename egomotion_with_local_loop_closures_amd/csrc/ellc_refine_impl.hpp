@@ -1,6 +1,7 @@
 // ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert (include/ellc_abi.h): the host side of the per-pixel depth
 // refinement of a keyframe slot against other views. Included at the end of ellc_hip.hip behind ellc_ring_common.hpp: its refusals,
-// view, grow-only buffers and timing window are used here; the views' staging (RefineView) and the four planes are this call's own.
+// view, grow-only buffers and the run of a call of K against views (staging, plane carve, launches, fetches, destination store) are
+// used here; the null-pointer and n_iter refusals, the Args and the copy of the record into the stats are this call's own.
 #pragma once
 #include "ellc_ring_common.hpp"
 #include "ellc_sim3_impl.hpp"
@@ -25,40 +26,21 @@ ellc_status refine_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vi
   // validated first: a refused call leaves the context and every slot as they were and writes nothing
   if (!view_slots || !T12 || !f || !p) return fail(c, ELLC_ERR_BAD_ARG, w + ": null pointer");
   ELLC_TRY(ring_views_check(c, who, B, ELLC_REFINE_MAX_VIEWS, views_are_kf, level, f, T12, light));
-  const LevelGeom& g = c->geom_h[level];
-  if (!std::isfinite(p->sigma_i2) || !std::isfinite(p->huber_k) || !std::isfinite(p->prior_weight) || !std::isfinite(p->max_step_rel) ||
-      !(p->sigma_i2 > 0.0f) || !(p->huber_k > 0.0f) || !(p->prior_weight >= 0.0f) || !(p->max_step_rel > 0.0f) || p->n_iter < 1 || p->n_iter > 8 ||
-      p->min_views < 1 || p->min_views > B)
-    return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
+  ELLC_TRY(ring_views_check_params(c, who, p, B));
+  if (p->n_iter < 1 || p->n_iter > 8) return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
   ELLC_TRY(ring_views_check_slots(c, who, dst, level, kf_slot, B, view_slots, views_are_kf));
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
-  const size_t n = (size_t)g.n;
-  const int blocks = (int)((n + 255) / 256);
-  ELLC_TRY(pair_reserve(c, c->refine, ELLC_REFINE_MAX_VIEWS, sizeof(RefineView), sizeof(RefineRec), (size_t)blocks));
-  ELLC_TRY(dev_grow(c, &c->refine_planes_d, &c->refine_planes_cap, n, 10));   // two f32 planes and two u8 planes
-  RefineView* vw = (RefineView*)c->refine.stage_h;
-  for (int b = 0; b < B; b++) {
-    vw[b].img = ring_view_image(c, level, views_are_kf, view_slots[b]);
-    std::memcpy(vw[b].T, T12 + (size_t)12 * b, 12 * sizeof(float));
-    vw[b].gain = light ? light[2 * b] : 1.0f;
-    vw[b].offset = light ? light[2 * b + 1] : 0.0f;
-  }
-  ELLC_HIP(c, hipMemcpyAsync(c->refine.stage_d, c->refine.stage_h, (size_t)B * sizeof(RefineView), hipMemcpyHostToDevice, c->stream));
+  const size_t n = (size_t)c->geom_h[level].n;
   RefineArgs a{};
   a.v = ring_view(c, level, f);
-  a.views = (const RefineView*)c->refine.stage_d;
-  a.partials = (RefineRec*)c->refine.partials_d;
-  a.out = (RefineRec*)c->refine.out_dev_alias;
-  char* planes = (char*)c->refine_planes_d;
-  const size_t cap = c->refine_planes_cap;
-  a.depth = (float*)planes;
-  a.var = (float*)(planes + 4 * cap);
-  a.nviews = (uint8_t*)(planes + 8 * cap);
-  a.status = (uint8_t*)(planes + 9 * cap);
-  a.kf_slot = kf_slot;
-  a.B = B;
-  a.blocks = blocks;
-  a.first = 0;
+  ELLC_TRY(ring_views_scratch(c, c->refine, ELLC_REFINE_MAX_VIEWS, n, kf_slot, B, a));
+  ELLC_TRY(dev_grow(c, &c->refine_planes_d, &c->refine_planes_cap, n, 10));   // two f32 planes and two u8 planes
+  ELLC_TRY(ring_views_stage<RefineView>(c, c->refine, level, B, views_are_kf, view_slots, T12, light));
+  const PlaneCarve planes{c->refine_planes_d, c->refine_planes_cap};
+  a.depth = planes.at<float>(0);
+  a.var = planes.at<float>(4);
+  a.nviews = planes.at<uint8_t>(8);
+  a.status = planes.at<uint8_t>(9);
   a.w0 = 1.0f / p->sigma_i2;
   a.sp = sqrtf(a.w0);
   a.huber_k = p->huber_k;
@@ -66,20 +48,9 @@ ellc_status refine_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vi
   a.max_step_rel = p->max_step_rel;
   a.n_iter = p->n_iter;
   a.min_views = p->min_views;
-  LaunchTimer t(c, launches_ms);
-  ELLC_TRY(t.begin());
-  hipLaunchKernelGGL(refine_pixels, dim3(blocks), dim3(256), 0, c->stream, a);
-  hipLaunchKernelGGL(refine_finish, dim3(1), dim3(64), 0, c->stream, a);
-  ELLC_HIP(c, hipGetLastError());
-  ELLC_TRY(t.end());
-  ELLC_TRY(ring_views_mark_use(c, B, view_slots, views_are_kf));
-  if (depth) ELLC_HIP(c, hipMemcpyAsync(depth, a.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (var) ELLC_HIP(c, hipMemcpyAsync(var, a.var, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (views) ELLC_HIP(c, hipMemcpyAsync(views, a.nviews, n, hipMemcpyDeviceToHost, c->stream));
-  if (status) ELLC_HIP(c, hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToHost, c->stream));
   const RefineRec* rec = (const RefineRec*)c->refine.out_h;
-  if (dst >= 0) ELLC_TRY(ring_views_store_dst(c, dst, a.depth, a.var, n, &rec->n[8]));
-  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  const RingFetch fetch[4] = {{depth, a.depth, n * 4}, {var, a.var, n * 4}, {views, a.nviews, n}, {status, a.status, n}};
+  ELLC_TRY(ring_views_run(c, a, refine_pixels, refine_finish, view_slots, views_are_kf, fetch, dst, n, &rec->n[8], launches_ms));
   if (out) {
     std::memset(out, 0, sizeof(*out));
     out->n_kept = rec->n[0]; out->n_taking_part = rec->n[1];
@@ -89,7 +60,7 @@ ellc_status refine_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vi
     out->sum_cost_before = rec->s[0];
     out->sum_cost_after = rec->s[1];
   }
-  return t.read();
+  return ELLC_OK;
 }
 
 }  // namespace

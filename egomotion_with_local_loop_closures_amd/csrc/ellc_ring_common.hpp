@@ -1,9 +1,10 @@
 // The host scaffold of the calls over the keyframe ring's semi-dense maps (ellc_keyframe_map_points, _render_depth, _fuse_depth,
 // _depth_consistency, _sim3_step / _align, _light_step, _sim3_step_lit / _align_lit, _trial_propagate, _refine_depth, _sweep_depth, _cull_depth, _joint_step / _apply / _refine, ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes): what they
-// refuse alike, the view map_keep reads, the timing window of the diagnostic hooks, grow-only buffers and the launch loop of the pair
-// reductions. Included at the end of ellc_hip.hip in front of the *_impl.hpp of those calls (the library is one translation unit).
-// A new call of the family supplies a record type with rec_zero / rec_add / rec_wave_sum (ellc_pair_reduce.hpp), a pass kernel and a
-// finish kernel over them, and its own list of refusals in its own order.
+// refuse alike, the view map_keep reads, the timing window of the diagnostic hooks, grow-only buffers, the launch loop of the pair
+// reductions and the run of a call of one keyframe slot against views (ring_views_*: staging, plane carve, scratch, launches, fetches,
+// destination store). Included at the end of ellc_hip.hip in front of the *_impl.hpp of those calls (the library is one translation
+// unit). A new call of the family supplies a record type with rec_zero / rec_add / rec_wave_sum (ellc_pair_reduce.hpp), a pass kernel
+// and a finish kernel over them, and its own list of refusals in its own order.
 #pragma once
 #include "ellc_context.hpp"
 #include "ellc_kernels_map.hpp"
@@ -144,6 +145,15 @@ ellc_status ring_views_store_dst(ellc_ctx* c, int dst, const float* depth_d, con
   });
 }
 
+// what ellc_keyframe_refine_depth and the joint calls refuse of their parameters alike (P: ellc_refine_params, ellc_joint_params)
+template <class P>
+ellc_status ring_views_check_params(ellc_ctx* c, const char* who, const P* p, int B) {
+  if (!std::isfinite(p->sigma_i2) || !std::isfinite(p->huber_k) || !std::isfinite(p->prior_weight) || !std::isfinite(p->max_step_rel) ||
+      !(p->sigma_i2 > 0.0f) || !(p->huber_k > 0.0f) || !(p->prior_weight >= 0.0f) || !(p->max_step_rel > 0.0f) || p->min_views < 1 || p->min_views > B)
+    return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": parameters out of range");
+  return ELLC_OK;
+}
+
 // ---- timing (the diagnostic hooks only): HIP events around a window of launches; read() adds the window's device time to *out, so a
 // call with several windows reports their sum. out == nullptr: nothing is recorded.
 struct LaunchTimer {
@@ -253,6 +263,88 @@ ellc_status pair_run(ellc_ctx* c, PairScratch& s, int B, int per_launch, void (*
   ELLC_TRY(enqueued(B));
   ELLC_HIP(c, hipStreamSynchronize(c->stream));
   std::memcpy(out, s.out_h, (size_t)B * sizeof(*a.out));
+  return t.read();
+}
+
+// ---- the calls of one keyframe slot K against B views, continued: staging, planes, scratch and run of a call. A new call of K against
+// views supplies a staged view type, an Args struct, a pixel kernel, a record and its own refusals.
+
+// The views on their way to the device, View being the call's staged type (RefineView or derived from it): image, transform and light
+// of every view, then what the call adds through more(view, b). (The stream has been waited for since the staging was last read.)
+struct RingViewAsIs {
+  template <class View>
+  void operator()(View&, int) const {}
+};
+
+template <class View, class More = RingViewAsIs>
+ellc_status ring_views_stage(ellc_ctx* c, PairScratch& s, int level, int B, int views_are_kf, const int* view_slots, const float* T12, const float* light,
+                             More more = More()) {
+  View* vw = (View*)s.stage_h;
+  for (int b = 0; b < B; b++) {
+    vw[b] = View{};
+    vw[b].img = ring_view_image(c, level, views_are_kf, view_slots[b]);
+    std::memcpy(vw[b].T, T12 + (size_t)12 * b, 12 * sizeof(float));
+    vw[b].gain = light ? light[2 * b] : 1.0f;
+    vw[b].offset = light ? light[2 * b + 1] : 0.0f;
+    more(vw[b], b);
+  }
+  ELLC_HIP(c, hipMemcpyAsync(s.stage_d, s.stage_h, (size_t)B * sizeof(View), hipMemcpyHostToDevice, c->stream));
+  return ELLC_OK;
+}
+
+// a grow-only buffer of `cap` pixels carved into planes: the plane that starts `bytes_before` bytes a pixel into it
+struct PlaneCarve {
+  void* base;
+  size_t cap;
+  template <class T>
+  T* at(size_t bytes_before) const { return (T*)((char*)base + bytes_before * cap); }
+};
+
+// a device plane to the host; a NULL host pointer: not asked for
+struct RingFetch {
+  void* host;
+  const void* dev;
+  size_t bytes;
+};
+
+template <int N>
+ellc_status ring_fetch(ellc_ctx* c, const RingFetch (&f)[N]) {
+  for (int k = 0; k < N; k++)
+    if (f[k].host) ELLC_HIP(c, hipMemcpyAsync(f[k].host, f[k].dev, f[k].bytes, hipMemcpyDeviceToHost, c->stream));
+  return ELLC_OK;
+}
+
+// The scratch of a one-record call over the n pixels of a level, and what its Args hold of it: the staged views, a partial record
+// per 256-pixel block, the pinned record.
+template <class Args>
+ellc_status ring_views_scratch(ellc_ctx* c, PairScratch& s, int max_B, size_t n, int kf_slot, int B, Args& a) {
+  a.blocks = (int)((n + 255) / 256);
+  ELLC_TRY(pair_reserve(c, s, max_B, sizeof(*a.views), sizeof(*a.out), (size_t)a.blocks));
+  a.views = (decltype(a.views))s.stage_d;
+  a.partials = (decltype(a.partials))s.partials_d;
+  a.out = (decltype(a.out))s.out_dev_alias;
+  a.kf_slot = kf_slot;
+  a.B = B;
+  a.first = 0;
+  return ELLC_OK;
+}
+
+// The run of a one-record call: the pixel kernel over a.blocks blocks and the finish kernel inside the timing window (launches_ms: the
+// diagnostic hook only), the frame slots' reader marks, the planes asked for, a.depth and a.var into slot dst (>= 0; *dense is the
+// record's count of pixels with a depth > 0), the wait. The pinned record may be read when this returns.
+template <class Args, int N>
+ellc_status ring_views_run(ellc_ctx* c, const Args& a, void (*pixels)(Args), void (*finish)(Args), const int* view_slots, int views_are_kf,
+                           const RingFetch (&fetch)[N], int dst, size_t n, const int32_t* dense, float* launches_ms) {
+  LaunchTimer t(c, launches_ms);
+  ELLC_TRY(t.begin());
+  hipLaunchKernelGGL(pixels, dim3(a.blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(finish, dim3(1), dim3(64), 0, c->stream, a);
+  ELLC_HIP(c, hipGetLastError());
+  ELLC_TRY(t.end());
+  ELLC_TRY(ring_views_mark_use(c, a.B, view_slots, views_are_kf));
+  ELLC_TRY(ring_fetch(c, fetch));
+  if (dst >= 0) ELLC_TRY(ring_views_store_dst(c, dst, a.depth, a.var, n, dense));
+  ELLC_HIP(c, hipStreamSynchronize(c->stream));
   return t.read();
 }
 

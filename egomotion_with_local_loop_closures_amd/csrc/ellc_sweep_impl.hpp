@@ -1,6 +1,7 @@
 // ellc_keyframe_sweep_depth, ellc_sweep_default_params (include/ellc_abi.h): the host side of the depth sweep that creates hypotheses in
-// a keyframe slot from other views. Included at the end of ellc_hip.hip behind ellc_refine_impl.hpp: ellc_keyframe_refine_depth's
-// refusals, staging of the views (RefineView) and four planes are used here as they stand; the record and the scratch are this call's own.
+// a keyframe slot from other views. Included at the end of ellc_hip.hip behind ellc_refine_impl.hpp: the refusals and the run of a call
+// of K against views (ellc_ring_common.hpp), the staged view (RefineView) and the four planes of ellc_keyframe_refine_depth are used
+// here as they stand; the parameter refusals, the Args, the record and the scratch are this call's own.
 #pragma once
 #include "ellc_refine_impl.hpp"
 #include "ellc_kernels_sweep.hpp"
@@ -23,7 +24,6 @@ ellc_status sweep_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vie
   // validated first: a refused call leaves the context and every slot as they were and writes nothing
   if (!view_slots || !T12 || !p) return fail(c, ELLC_ERR_BAD_ARG, w + ": null pointer");
   ELLC_TRY(ring_views_check(c, who, B, ELLC_REFINE_MAX_VIEWS, views_are_kf, level, nullptr, T12, light));
-  const LevelGeom& g = c->geom_h[level];
   if (!std::isfinite(p->sigma_i2) || !std::isfinite(p->huber_k) || !std::isfinite(p->d_min) || !std::isfinite(p->d_max) || !std::isfinite(p->min_grad2) ||
       !std::isfinite(p->max_cost) || !std::isfinite(p->distinct_ratio) || !std::isfinite(p->var_scale))
     return fail(c, ELLC_ERR_BAD_ARG, w + ": parameter not finite");
@@ -33,34 +33,18 @@ ellc_status sweep_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vie
     return fail(c, ELLC_ERR_BAD_ARG, w + ": parameters out of range");
   ELLC_TRY(ring_views_check_slots(c, who, dst, level, kf_slot, B, view_slots, views_are_kf));
   ELLC_ENTER(c);   // behind the batches in flight, on the main stream
-  const size_t n = (size_t)g.n;
-  const int blocks = (int)((n + 255) / 256);
-  ELLC_TRY(pair_reserve(c, c->sweep, ELLC_REFINE_MAX_VIEWS, sizeof(RefineView), sizeof(SweepRec), (size_t)blocks));
-  ELLC_TRY(dev_grow(c, &c->refine_planes_d, &c->refine_planes_cap, n, 10));   // two f32 planes and two u8 planes, shared with the refinement
-  RefineView* vw = (RefineView*)c->sweep.stage_h;
-  for (int b = 0; b < B; b++) {
-    vw[b].img = ring_view_image(c, level, views_are_kf, view_slots[b]);
-    std::memcpy(vw[b].T, T12 + (size_t)12 * b, 12 * sizeof(float));
-    vw[b].gain = light ? light[2 * b] : 1.0f;
-    vw[b].offset = light ? light[2 * b + 1] : 0.0f;
-  }
-  ELLC_HIP(c, hipMemcpyAsync(c->sweep.stage_d, c->sweep.stage_h, (size_t)B * sizeof(RefineView), hipMemcpyHostToDevice, c->stream));
+  const size_t n = (size_t)c->geom_h[level].n;
   const ellc_map_filter every = {0.0f, 0, 1.0f, 1};   // (ring_view wants one; no kernel of this call reads it)
   SweepArgs a{};
   a.v = ring_view(c, level, &every);
-  a.views = (const RefineView*)c->sweep.stage_d;
-  a.partials = (SweepRec*)c->sweep.partials_d;
-  a.out = (SweepRec*)c->sweep.out_dev_alias;
-  char* planes = (char*)c->refine_planes_d;
-  const size_t cap = c->refine_planes_cap;
-  a.depth = (float*)planes;
-  a.var = (float*)(planes + 4 * cap);
-  a.nviews = (uint8_t*)(planes + 8 * cap);
-  a.status = (uint8_t*)(planes + 9 * cap);
-  a.kf_slot = kf_slot;
-  a.B = B;
-  a.blocks = blocks;
-  a.first = 0;
+  ELLC_TRY(ring_views_scratch(c, c->sweep, ELLC_REFINE_MAX_VIEWS, n, kf_slot, B, a));
+  ELLC_TRY(dev_grow(c, &c->refine_planes_d, &c->refine_planes_cap, n, 10));   // two f32 planes and two u8 planes, shared with the refinement
+  ELLC_TRY(ring_views_stage<RefineView>(c, c->sweep, level, B, views_are_kf, view_slots, T12, light));
+  const PlaneCarve planes{c->refine_planes_d, c->refine_planes_cap};
+  a.depth = planes.at<float>(0);
+  a.var = planes.at<float>(4);
+  a.nviews = planes.at<uint8_t>(8);
+  a.status = planes.at<uint8_t>(9);
   a.w0 = 1.0f / p->sigma_i2;
   a.sp = sqrtf(a.w0);
   a.huber_k = p->huber_k;
@@ -72,20 +56,9 @@ ellc_status sweep_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vie
   a.var_scale = p->var_scale;
   a.n_samples = p->n_samples;
   a.min_views = p->min_views;
-  LaunchTimer t(c, launches_ms);
-  ELLC_TRY(t.begin());
-  hipLaunchKernelGGL(sweep_pixels, dim3(blocks), dim3(256), 0, c->stream, a);
-  hipLaunchKernelGGL(sweep_finish, dim3(1), dim3(64), 0, c->stream, a);
-  ELLC_HIP(c, hipGetLastError());
-  ELLC_TRY(t.end());
-  ELLC_TRY(ring_views_mark_use(c, B, view_slots, views_are_kf));
-  if (depth) ELLC_HIP(c, hipMemcpyAsync(depth, a.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (var) ELLC_HIP(c, hipMemcpyAsync(var, a.var, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (views) ELLC_HIP(c, hipMemcpyAsync(views, a.nviews, n, hipMemcpyDeviceToHost, c->stream));
-  if (status) ELLC_HIP(c, hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToHost, c->stream));
   const SweepRec* rec = (const SweepRec*)c->sweep.out_h;
-  if (dst >= 0) ELLC_TRY(ring_views_store_dst(c, dst, a.depth, a.var, n, &rec->n[8]));
-  ELLC_HIP(c, hipStreamSynchronize(c->stream));
+  const RingFetch fetch[4] = {{depth, a.depth, n * 4}, {var, a.var, n * 4}, {views, a.nviews, n}, {status, a.status, n}};
+  ELLC_TRY(ring_views_run(c, a, sweep_pixels, sweep_finish, view_slots, views_are_kf, fetch, dst, n, &rec->n[8], launches_ms));
   if (out) {
     std::memset(out, 0, sizeof(*out));
     out->n_ok = rec->n[0]; out->n_swept = rec->n[1];
@@ -94,7 +67,7 @@ ellc_status sweep_depth_impl(ellc_ctx* c, int kf_slot, int level, int B, int vie
     out->sum_views = rec->sum_views;
     out->sum_cost = rec->s[0];
   }
-  return t.read();
+  return ELLC_OK;
 }
 
 }  // namespace
