@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "ellc_keyframe_sweep_depth", "ellc_sweep_default_params",
     "ellc_keyframe_cull_depth", "ellc_cull_default_params",
     "ellc_keyframe_joint_step", "ellc_joint_solve", "ellc_keyframe_joint_apply", "ellc_keyframe_joint_refine", "ellc_joint_default_params",
+    "ellc_depth_absorb_keyframes_lit", "ellc_depth_restart_from_keyframes_lit", "ellc_keyframe_trial_propagate_lit", "ellc_trial_light_solve",
     "ellc_ingest_configure", "ellc_frame_ingest_bgr",
     "ellc_shard_range", "ellc_comm_unique_id", "ellc_comm_init_rccl", "ellc_comm_init_tcp", "ellc_comm_info", "ellc_comm_destroy", "ellc_comm_last_error",
     "ellc_gather_start", "ellc_gather_finish", "ellc_gather_results",
@@ -208,6 +209,13 @@ class EllcTrialPropagation(C.Structure):
     _fields_ = [("sum_r2", C.c_double), ("sum_abs_r", C.c_double),
                 ("n_kept", C.c_int32), ("n_in_view", C.c_int32), ("n_interior", C.c_int32), ("n_low_grad", C.c_int32),
                 ("n_candidates", C.c_int32), ("n_targets", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class EllcTrialPropagationLit(C.Structure):
+    """ellc_trial_propagation_lit: what ellc_keyframe_trial_propagate_lit returns per request (96 bytes): an ellc_trial_propagation at
+    the request's light, then the five sums of the fit of Iw on Is over the interior pixels and their number."""
+    _fields_ = EllcTrialPropagation._fields_ + [("sum_s", C.c_double), ("sum_t", C.c_double), ("sum_ss", C.c_double), ("sum_st", C.c_double),
+                                                ("sum_tt", C.c_double), ("n_fit", C.c_int32), ("reserved2", C.c_int32)]
 
 
 class EllcError(RuntimeError):

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcSweepParams, EllcSweepStats, SWEEP_STATUS, SWEEP_STATS_FIELDS, EllcCullParams, EllcCullStats, CULL_STATUS, CULL_STATS_FIELDS, EllcJointParams, EllcJointNormal, EllcJointApplyStats, JOINT_STATUS, JOINT_MAX_VIEWS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcError, MAX_LEVELS
+from ._lib import EllcConfig, EllcHypotheses, EllcAlignQuality, EllcMapPoint, EllcMapFilter, EllcDepthConsistency, EllcSim3Params, EllcSim3Normal, EllcLightNormal, EllcLightParams, EllcRefineParams, EllcRefineStats, REFINE_STATUS, EllcSweepParams, EllcSweepStats, SWEEP_STATUS, SWEEP_STATS_FIELDS, EllcCullParams, EllcCullStats, CULL_STATUS, CULL_STATS_FIELDS, EllcJointParams, EllcJointNormal, EllcJointApplyStats, JOINT_STATUS, JOINT_MAX_VIEWS, EllcAbsorbParams, EllcAbsorbStats, ABSORB_STATS_FIELDS, EllcTrialPropagation, EllcTrialPropagationLit, EllcError, MAX_LEVELS
 
 MODE_FCA = 0
 MODE_ICA = 1
@@ -11,6 +11,7 @@ ARITH_FAST = 1
 ERR_CAPACITY = -5
 MAP_POINT_DTYPE = np.dtype(EllcMapPoint)   # x y z var (f32), px py (u16), intensity support (u8), source (u16): 24 bytes
 LIGHT_NORMAL_DTYPE = np.dtype(EllcLightNormal)   # sum_w, sum_w_s, sum_w_t, sum_w_ss, sum_w_st, sum_w_tt, chi2_photo (f64), four int32 counts: 72 bytes
+TRIAL_LIT_DTYPE = np.dtype(EllcTrialPropagationLit)   # ellc_trial_propagation's 48 bytes, sum_s, sum_t, sum_ss, sum_st, sum_tt (f64), n_fit, reserved2 (int32): 96 bytes
 SIM3_NORMAL_DTYPE = np.dtype(EllcSim3Normal)   # H (28 f64), b (7 f64), chi2_photo, chi2_depth (f64), six int32 counts: 320 bytes
 JOINT_NORMAL_DTYPE = np.dtype(EllcJointNormal)   # A (8 x 21), a (8 x 6), S (1176), s (48), chi2_photo, chi2_prior (f64), n_terms (i64), six int32 counts and B, n_view_terms (8 int32): 11600 bytes
 HYP_FIELDS = ("invDepth", "invDepthSmoothed", "variance", "varianceSmoothed", "validity", "blacklisted", "valid")
@@ -411,34 +412,42 @@ class Context:
                           max_var, min_support, support_k2, stride, out)
 
     # ---- keyframe maps folded into the live depth map
-    def _absorb(self, fn, name, extra, kf_slots, T12, params, max_var, min_support, support_k2, stride, stats, tail=None):
+    def _absorb(self, fn, name, extra, kf_slots, T12, params, max_var, min_support, support_k2, stride, stats, tail=None, lights=None, head=()):
         kf = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
         B = kf.size
         T = np.ascontiguousarray(T12, np.float32).reshape(B, 12)
+        light = ()
+        if lights is not None:   # the _lit entry point of the same call: the lights go behind the transforms
+            fn, name = getattr(self._l, name + "_lit"), name + "_lit"
+            L = np.ascontiguousarray(lights, np.float32).reshape(B, 2)
+            light = (_p(L),)
         flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
         prm = params if isinstance(params, EllcAbsorbParams) else absorb_params(**(params or {}))
         st = stats if stats is not None else EllcAbsorbStats()
-        # (tail: arguments in front of the stats pointer - ellc_depth_restart_from_keyframes' rescale factor)
-        self._ck(fn(self.h, B, _p(kf), _p(T), C.byref(flt), C.byref(prm), *(tail or ()), C.byref(st), *extra), name)
+        # (head: arguments in front of B - the restart's new keyframe slot; tail: in front of the stats pointer - its rescale factor)
+        self._ck(fn(self.h, *head, B, _p(kf), _p(T), *light, C.byref(flt), C.byref(prm), *(tail or ()), C.byref(st), *extra), name)
         return {k: int(getattr(st, k)) for k in ABSORB_STATS_FIELDS}
 
-    def depth_absorb(self, kf_slots, T12, params=None, max_var=0.0, min_support=0, support_k2=1.0, stride=1, stats=None):
+    def depth_absorb(self, kf_slots, T12, params=None, max_var=0.0, min_support=0, support_k2=1.0, stride=1, stats=None, lights=None):
         """The maps of keyframe slots kf_slots[b] (level 0) folded into the context's live depth map (ellc_depth_absorb_keyframes):
         T12[b] is the row-major 3x4 transform from that slot's camera into the depth map's keyframe's, the filter is map_points'.
         params: dict of agree_k2, max_fold, photo_gate, src_validity, finalise (defaults 1, 64, 1, 20, 1) or an EllcAbsorbParams.
         Returns the sixteen counts of ellc_absorb_stats as a dict (stats: an EllcAbsorbStats to receive them as well). With
-        finalise=0 the caller must regularise (depth_do_regularization) before anything observes or exports the map."""
+        finalise=0 the caller must regularise (depth_do_regularization) before anything observes or exports the map.
+        lights: [B][2] f32 (gain, offset) taking slot kf_slots[b]'s grey values into the keyframe's, the direction of T12[b]; the
+        photometric gate's residual is then taken against gain * Is + offset (ellc_depth_absorb_keyframes_lit). None: the unlit call."""
         return self._absorb(self._l.ellc_depth_absorb_keyframes, "ellc_depth_absorb_keyframes", (), kf_slots, T12, params, max_var, min_support,
-                            support_k2, stride, stats)
+                            support_k2, stride, stats, lights=lights)
 
-    def depth_restart(self, new_kf_slot, kf_slots, T12, params=None, max_var=0.0, min_support=0, support_k2=1.0, stride=1, stats=None):
+    def depth_restart(self, new_kf_slot, kf_slots, T12, params=None, max_var=0.0, min_support=0, support_k2=1.0, stride=1, stats=None, lights=None):
         """The live depth map re-seated on keyframe slot new_kf_slot (which holds an image and is not among kf_slots) from the maps of
         keyframe slots kf_slots[b], starting EMPTY (ellc_depth_restart_from_keyframes): the wipe, depth_absorb's fold with T12[b] the
         transform from slot kf_slots[b]'s camera into new_kf_slot's, and with finalise=1 (the default) createKeyFrame's tail. The
-        context needs no state beforehand. Returns (the sixteen counts of ellc_absorb_stats as a dict, the rescale factor)."""
+        context needs no state beforehand. Returns (the sixteen counts of ellc_absorb_stats as a dict, the rescale factor).
+        lights: as in depth_absorb, into new_kf_slot's grey values (ellc_depth_restart_from_keyframes_lit); None: the unlit call."""
         factor = C.c_float(0.0)
-        out = self._absorb(lambda h, *a: self._l.ellc_depth_restart_from_keyframes(h, int(new_kf_slot), *a), "ellc_depth_restart_from_keyframes",
-                           (), kf_slots, T12, params, max_var, min_support, support_k2, stride, stats, tail=(C.byref(factor),))
+        out = self._absorb(self._l.ellc_depth_restart_from_keyframes, "ellc_depth_restart_from_keyframes", (), kf_slots, T12, params, max_var,
+                           min_support, support_k2, stride, stats, tail=(C.byref(factor),), lights=lights, head=(int(new_kf_slot),))
         return out, float(factor.value)
 
     # ---- trial propagation: what a keyframe's map would seed in an image
@@ -460,6 +469,24 @@ class Context:
         (int32), sum_r2, sum_abs_r (f64). n_targets is the number of hypotheses a restart from that request alone would create."""
         return self._trial(self._l.ellc_keyframe_trial_propagate, "ellc_keyframe_trial_propagate", (), src_slots, dst_slots, Ts, dst_is_keyframe,
                            photo_gate, max_var, min_support, support_k2, stride)
+
+    def trial_propagate_lit(self, src_slots, dst_slots, Ts, lights=None, dst_is_keyframe=False, photo_gate=1, max_var=0.0, min_support=0,
+                            support_k2=1.0, stride=1):
+        """trial_propagate with the residual taken against gain * Is + offset at lights[b] ([B][2] f32, source's grey values into the
+        destination's; None: (1, 0) each) (ellc_keyframe_trial_propagate_lit): a structured array of B ellc_trial_propagation_lit
+        records (TRIAL_LIT_DTYPE) - trial_propagate's fields at that light, then sum_s, sum_t, sum_ss, sum_st, sum_tt (f64) and n_fit
+        over the interior pixels, which trial_light_solve turns into a light."""
+        src = np.ascontiguousarray(src_slots, np.int32).reshape(-1)
+        dst = np.ascontiguousarray(dst_slots, np.int32).reshape(-1)
+        B = src.size
+        assert dst.size == B
+        T = np.ascontiguousarray(Ts, np.float32).reshape(B, 12)
+        L = None if lights is None else np.ascontiguousarray(lights, np.float32).reshape(B, 2)
+        flt = EllcMapFilter(max_var, int(min_support), support_k2, int(stride))
+        out = np.zeros(B, TRIAL_LIT_DTYPE)
+        self._ck(self._l.ellc_keyframe_trial_propagate_lit(self.h, B, _p(src), int(dst_is_keyframe), _p(dst), _p(T), _p(L), C.byref(flt),
+                                                           int(photo_gate), _p(out)), "ellc_keyframe_trial_propagate_lit")
+        return out
 
     # ---- one keyframe's map against another's
     def _consistency(self, fn, name, extra, src_slots, dst_slots, Ts, level, agree_k2, max_var, min_support, support_k2, stride):
@@ -1113,6 +1140,17 @@ def light_solve(rec, light_in=None, params=None):
     li = None if light_in is None else np.ascontiguousarray(light_in, np.float32).reshape(2)
     out = np.zeros(2, np.float32)
     refused = _lib.lib().ellc_light_solve(_p(r), C.byref(p), _p(li), _p(out))
+    return out, bool(refused)
+
+
+def trial_light_solve(rec, light_in=None, params=None):
+    """ellc_trial_light_solve of one ellc_trial_propagation_lit record (a row of trial_propagate_lit's array): the unweighted fit of Iw on
+    Is over its interior pixels, by light_solve's rule: (light f32 [2], refused)."""
+    r = np.ascontiguousarray(np.asarray(rec, TRIAL_LIT_DTYPE).reshape(1))
+    p = _as_light_params(params)
+    li = None if light_in is None else np.ascontiguousarray(light_in, np.float32).reshape(2)
+    out = np.zeros(2, np.float32)
+    refused = _lib.lib().ellc_trial_light_solve(_p(r), C.byref(p), _p(li), _p(out))
     return out, bool(refused)
 
 

@@ -1,4 +1,4 @@
-// ellc_depth_absorb_keyframes (include/ellc_abi.h): the host side of the fold of keyframe slots into the live depth map.
+// ellc_depth_absorb_keyframes, ellc_depth_restart_from_keyframes and their _lit forms (include/ellc_abi.h): the host side of the fold of keyframe slots into the live depth map.
 // Included at the end of ellc_hip.hip, behind ellc_fuse_impl.hpp and ellc_depth_impl.hpp: the render's validation, scratch and staging,
 // the fusion's scratch, scan kernels and list, and the depth map's regularisation and export are used as they are (the fold writes the
 // live map, so the render's enqueue / download / write-back steps do not apply).
@@ -14,16 +14,20 @@ namespace {
 // launches are not inside), HIP events around them. The host's read of the list's size lies inside that window, as in the fusion.
 // restart_slot >= 0: ellc_depth_restart_from_keyframes. That slot takes K's place, the state is wiped in front of the fold (behind
 // everything that can refuse the call) and `finalise` runs createKeyFrame's tail, whose factor goes to *rescale_factor.
-ellc_status absorb_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const ellc_map_filter* f, const ellc_absorb_params* p,
-                        ellc_absorb_stats* out, float* launches_ms, int restart_slot = -1, float* rescale_factor = nullptr) {
+// light: the _lit entry points' [B][2] (gain, offset) of absorb_photo's residual; NULL, the unlit entry points too: (1, 0) each.
+ellc_status absorb_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const float* light, const ellc_map_filter* f, const ellc_absorb_params* p,
+                        ellc_absorb_stats* out, float* launches_ms, int restart_slot = -1, float* rescale_factor = nullptr, bool lit = false) {
   const bool restart = restart_slot >= 0;
-  const char* who = restart ? "ellc_depth_restart_from_keyframes" : "ellc_depth_absorb_keyframes";
+  const char* who = restart ? (lit ? "ellc_depth_restart_from_keyframes_lit" : "ellc_depth_restart_from_keyframes")
+                            : (lit ? "ellc_depth_absorb_keyframes_lit" : "ellc_depth_absorb_keyframes");
   if (!c) return ELLC_ERR_BAD_ARG;
   if (!p) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": null pointer");
   // (the parameters first: a bad argument is reported in front of a slot that is not ready)
   if (p->max_fold < 1 || p->max_fold > ELLC_FUSE_MAX_MERGE) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": max_fold out of range");
   if (p->src_validity < 0 || p->src_validity > 255) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": src_validity out of range");
   if (p->photo_gate < 0 || p->photo_gate > 1 || p->finalise < 0 || p->finalise > 1) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": photo_gate / finalise not 0 or 1");
+  // (a light that is not finite is a bad argument too, in front of the slots; render_validate refuses a B out of range)
+  if (render_B_ok(c, B)) ELLC_TRY(light_check(c, who, B, light));
   ELLC_TRY(render_validate(c, who, B, kf_slots, T12, 0, f, p->agree_k2, restart_slot, !restart));   // (the new keyframe is no source)
   if (restart) {
     if (!c->kf_has_image[restart_slot]) return fail(c, ELLC_ERR_NOT_READY, std::string(who) + ": the new keyframe slot has no image");
@@ -49,7 +53,7 @@ ellc_status absorb_impl(ellc_ctx* c, int B, const int* kf_slots, const float* T1
   a.f.r = render_args(c, B, 0, f, p->agree_k2);
   const size_t mask_words = (size_t)B * (size_t)a.f.r.v.tiles * 32;   // 8 steps x 4 waves per (request, tile)
   ELLC_TRY(fuse_mask_reserve(c, mask_words));
-  ELLC_TRY(render_stage(c, B, kf_slots, T12));
+  ELLC_TRY(render_stage(c, B, kf_slots, T12, light));
   a.f.mask = c->fuse_mask_d;
   a.f.cursor = c->fuse_cursor_d;
   a.f.tile_sums = c->fuse_tile_sums_d;
@@ -132,20 +136,33 @@ void ellc_absorb_default_params(ellc_absorb_params* p) {
 
 ellc_status ellc_depth_absorb_keyframes(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
                                         const ellc_absorb_params* params, ellc_absorb_stats* out) {
-  return absorb_impl(c, B, kf_slots, T12, filter, params, out, nullptr);
+  return absorb_impl(c, B, kf_slots, T12, nullptr, filter, params, out, nullptr);
+}
+
+ellc_status ellc_depth_absorb_keyframes_lit(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const float* light, const ellc_map_filter* filter,
+                                            const ellc_absorb_params* params, ellc_absorb_stats* out) {
+  return absorb_impl(c, B, kf_slots, T12, light, filter, params, out, nullptr, -1, nullptr, true);
 }
 
 ellc_status ellc_depth_restart_from_keyframes(ellc_ctx* c, int new_kf_slot, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
                                               const ellc_absorb_params* params, float* rescale_factor, ellc_absorb_stats* out) {
   if (!c) return ELLC_ERR_BAD_ARG;
   if (!slot_ok(new_kf_slot, c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, "ellc_depth_restart_from_keyframes: new keyframe slot out of range");
-  return absorb_impl(c, B, kf_slots, T12, filter, params, out, nullptr, new_kf_slot, rescale_factor);
+  return absorb_impl(c, B, kf_slots, T12, nullptr, filter, params, out, nullptr, new_kf_slot, rescale_factor);
+}
+
+ellc_status ellc_depth_restart_from_keyframes_lit(ellc_ctx* c, int new_kf_slot, int B, const int* kf_slots, const float* T12, const float* light,
+                                                  const ellc_map_filter* filter, const ellc_absorb_params* params, float* rescale_factor,
+                                                  ellc_absorb_stats* out) {
+  if (!c) return ELLC_ERR_BAD_ARG;
+  if (!slot_ok(new_kf_slot, c->cfg.max_keyframes)) return fail(c, ELLC_ERR_BAD_ARG, "ellc_depth_restart_from_keyframes_lit: new keyframe slot out of range");
+  return absorb_impl(c, B, kf_slots, T12, light, filter, params, out, nullptr, new_kf_slot, rescale_factor, true);
 }
 
 #ifdef ELLC_DIAG_ABI
 ellc_status ellc_profile_depth_absorb(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const ellc_map_filter* filter,
                                       const ellc_absorb_params* params, ellc_absorb_stats* out, float* launches_ms) {
-  return ring_profiled(launches_ms, [&](float* ms) { return absorb_impl(c, B, kf_slots, T12, filter, params, out, ms); });
+  return ring_profiled(launches_ms, [&](float* ms) { return absorb_impl(c, B, kf_slots, T12, nullptr, filter, params, out, ms); });
 }
 #endif   // ELLC_DIAG_ABI
 

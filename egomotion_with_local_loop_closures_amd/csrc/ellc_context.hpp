@@ -250,7 +250,7 @@ struct ellc_ctx {
   void* map_out_d = nullptr;                // device staging of the records: an allocation of its own that grows with the largest call
   size_t map_out_cap = 0;                   //   records it holds
   // ellc_keyframe_render_depth: scratch of its own, allocated by the first call
-  int* render_stage_h = nullptr;            // pinned: [max_keyframes] slot of every request, [max_keyframes][12] f32 transforms
+  int* render_stage_h = nullptr;            // pinned: [max_keyframes] slot of every request, [max_keyframes][12] f32 transforms, [max_keyframes][2] f32 lights
   void* render_block_d = nullptr;           // one device allocation of its own (several MB at 640x480: not carved from the arena) that holds:
   int* render_stage_d = nullptr;            //   the device copy of the record above
   unsigned long long* render_keys_d = nullptr;   // [W*H] smallest candidate key per target
@@ -276,6 +276,7 @@ struct ellc_ctx {
   // ellc_keyframe_depth_consistency, ellc_keyframe_sim3_step / _step_lit / _align / _align_lit, ellc_keyframe_trial_propagate,
   // ellc_keyframe_light_step (through ellc_keyframe_sim3_align_lit too): a PairScratch each, and the trial call's bitmaps
   ellc::PairScratch consist, sim3, trial, light;
+  ellc::PairScratch trial_lit;              // ellc_keyframe_trial_propagate_lit: its records are twice as wide
   unsigned* trial_bits_d = nullptr;         // [requests of one launch][ceil(W*H / 32)] one bit per target pixel
   size_t trial_bits_cap = 0;                //   words it holds
   // ellc_keyframe_refine_depth: a PairScratch (the views' staging, one record, the blocks' partial records) and the four planes it returns

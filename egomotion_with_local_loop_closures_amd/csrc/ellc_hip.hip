@@ -1256,6 +1256,7 @@ ellc_status ellc_ctx_destroy(ellc_ctx* c) {
   ellc::pair_free(c->consist);
   ellc::pair_free(c->sim3);
   ellc::pair_free(c->trial);
+  ellc::pair_free(c->trial_lit);
   ellc::pair_free(c->light);
   ellc::pair_free(c->refine);
   ellc::pair_free(c->sweep);

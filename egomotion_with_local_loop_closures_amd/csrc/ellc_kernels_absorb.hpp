@@ -9,6 +9,8 @@
 //   absorb_scatter                  the walk again over the kept bits: every candidate takes the next entry of its target's segment
 //   absorb_fold + absorb_finish     one thread per target: its candidates in ascending id order, eight at a walk (fuse_merge's selection),
 //                                   folded in registers into the target's own hypothesis, which is written in place
+//   (the _lit entry points hand absorb_mark a light per request, gain and offset beside its T in the staging; the unlit ones stage
+//   (1, 0) and go through the same kernels)
 //   absorb_wipe                     ellc_depth_restart_from_keyframes only, in front of the scatter: every hypothesis empty
 // No waiting between blocks, integer atomics only, no floating-point atomics. render_candidate and map_keep decide every pass.
 // absorb_interior and absorb_photo, the two halves of absorb_mark's gate, also decide ellc_keyframe_trial_propagate's pass (ellc_kernels_trial.hpp).
@@ -37,33 +39,43 @@ __device__ __forceinline__ bool absorb_interior(const LevelGeom& g, const Render
   return c.u > 2.1f && c.v > 2.1f && c.u < (float)g.cols - 3.1f && c.v < (float)g.rows - 3.1f;
 }
 
+// The light of request b in the absorb's staging: [max_kf][2] f32 (gain, offset) behind the slots and the transforms (block-uniform
+// where the request is: scalar loads)
+__device__ __forceinline__ void absorb_light(const int* stage, int max_kf, unsigned b, float& gain, float& offset) {
+  const float* l = (const float*)(stage + 13u * (unsigned)max_kf) + 2u * b;
+  gain = l[0];
+  offset = l[1];
+}
+
 // The photometric gate of :1066-1076 (MAX_DIFF_CONSTANT 1600, MAX_DIFF_GRAD_MULT 0.25, MIN_ABS_GRAD_DECREASE 5) on an INTERIOR candidate of
 // source pixel (x, y) of image `img`, against the destination's level-0 image k_img (pitch g.sw) and maxAbsGradient plane k_maxgrad: does
-// the candidate pass. r = Iw - Is and gr (the gradient at the TARGET) are handed back for ellc_keyframe_trial_propagate's sums.
+// the candidate pass. The source's grey value goes through the request's light first, Ip = gain * Is + offset (two roundings; (1, 0)
+// gives Is bit for bit); gr and both constants stay in the destination's units. r = Iw - Ip and gr (the gradient at the TARGET) are
+// handed back for ellc_keyframe_trial_propagate's sums, Iw and Is for the sums of its fit.
 __device__ __forceinline__ bool absorb_photo(const LevelGeom& g, const uint8_t* k_img, const float* k_maxgrad, const ELLC_GLOBAL uint8_t* img, int x, int y,
-                                             const RenderCand& c, float& r, float& gr) {
+                                             const RenderCand& c, float gain, float offset, float& r, float& gr, float& Iw, float& Is) {
   // 2 < u < cols - 3 and 2 < v < rows - 3: the four taps exist
   const int x0 = (int)c.u, y0 = (int)c.v;
   const unsigned t0 = (unsigned)(y0 * g.sw + x0);
   const float I00 = (float)k_img[t0], I01 = (float)k_img[t0 + 1u], I10 = (float)k_img[t0 + (unsigned)g.sw], I11 = (float)k_img[t0 + (unsigned)g.sw + 1u];
   const float ax = c.u - (float)x0, ay = c.v - (float)y0;
   float gx, gy;
-  const float Iw = sim3_bilinear(I00, I01, I10, I11, ax, ay, gx, gy);
-  const float Is = (float)img[(unsigned)(y * g.sw + x)];
-  r = Iw - Is;
+  Iw = sim3_bilinear(I00, I01, I10, I11, ax, ay, gx, gy);
+  Is = (float)img[(unsigned)(y * g.sw + x)];
+  r = Iw - __fadd_rn(__fmul_rn(gain, Is), offset);
   gr = k_maxgrad[(unsigned)c.target];   // at the TARGET (the reference reads the source's coordinates: dm_prop_project's Q14)
   return !((r * r) / (1600.0f + (0.25f * gr) * gr) > 1.0f || gr < 5.0f);
 }
 
 // THE rule behind render_candidate, for absorb_mark: does the candidate of source pixel (x, y) of image `img` pass the interior bound
-// and, when it is on, the photometric gate against k_img / k_maxgrad
+// and, when it is on, the photometric gate against k_img / k_maxgrad at the request's light
 __device__ __forceinline__ bool absorb_gate(const LevelGeom& g, const uint8_t* k_img, const float* k_maxgrad, int photo_gate, const ELLC_GLOBAL uint8_t* img,
-                                            int x, int y, const RenderCand& c, bool& interior) {
+                                            int x, int y, const RenderCand& c, float gain, float offset, bool& interior) {
   interior = absorb_interior(g, c);
   if (!interior) return false;
   if (!photo_gate) return true;
-  float r, gr;
-  return absorb_photo(g, k_img, k_maxgrad, img, x, y, c, r, gr);
+  float r, gr, Iw, Is;
+  return absorb_photo(g, k_img, k_maxgrad, img, x, y, c, gain, offset, r, gr, Iw, Is);
 }
 
 // fuse_agree's grid (tiles of level 0) x B and walk
@@ -77,6 +89,8 @@ __global__ __launch_bounds__(256) void absorb_mark(AbsorbArgs a) {
   const ELLC_GLOBAL uint8_t* img = gptr(K.img);
   const int cols = g.cols, rows = g.rows;
   const RenderT T = render_T12(ra, b);
+  float gain, offset;
+  absorb_light(ra.stage, ra.v.max_kf, b, gain, offset);
   const int base = (int)blockIdx.x * ELLC_TILE + (int)threadIdx.x;
   int n_kept = 0, n_view = 0, n_int = 0, n_cand = 0;
 #pragma unroll
@@ -90,7 +104,7 @@ __global__ __launch_bounds__(256) void absorb_mark(AbsorbArgs a) {
       if (render_candidate(g, T, b, i, p.x, p.y, p.Z, p.V, c)) {
         n_view++;
         bool interior;
-        ok = absorb_gate(g, a.k_img, a.k_maxgrad, a.photo_gate, img, p.x, p.y, c, interior);
+        ok = absorb_gate(g, a.k_img, a.k_maxgrad, a.photo_gate, img, p.x, p.y, c, gain, offset, interior);
         n_int += interior ? 1 : 0;
         if (ok) {
           n_cand++;

@@ -13,7 +13,7 @@ namespace ellc {
 
 struct RenderArgs {
   MapView v;                     // what map_keep reads
-  const int* stage;              // [max_kf] keyframe slot of every request, then [max_kf][12] f32 transforms (map_slot, map_T12)
+  const int* stage;              // [max_kf] keyframe slot of every request, then [max_kf][12] f32 transforms (map_slot, map_T12), then [max_kf][2] f32 lights (absorb_light)
   unsigned long long* keys;      // [n of the level]: (bits(z') << 32) | (b << 24) | i of the best candidate so far (render_min)
   float* depth;                  // the five planes of the view, [n] each (render_resolve; agree counted up by render_agree)
   float* var;

@@ -77,7 +77,8 @@
 //                    (globalOptimize::absorbMatches: the batch and its Sim(3) refinement run synchronously, the candidates' ring slots are
 //                    copied into tracking-context keyframe slots 2, 3, ..., ellc_depth_absorb_keyframes with the default parameters), so
 //                    the map createKeyFrame propagates next carries it; FILE gets "frameId B" and the fifteen stats per push. The
-//                    tracking context is created with max_keyframes 2 + 43. Without the flag every output file is what it was
+//                    tracking context is created with max_keyframes 2 + 43. Without the flag every output file is what it was.
+//                    Together with --match-light the fold is ellc_depth_absorb_keyframes_lit at every candidate's refined light
 // --restore-connection FILE  (LC mode) FLAG_RESTORE_CONNECTION (main.cpp:252-324): before a frame is tracked the live map is checked
 //                    (globalOptimize::checkConnection); when it has no seeds left the frame is re-localised against the ring
 //                    (globalOptimize::findConnection with restoreConnection on: one batched alignment, one ellc_keyframe_trial_propagate,
@@ -86,6 +87,11 @@
 //                    FILE gets one line per lost frame, "frameId n_candidates chosen_kfId n_targets seeds_after rescale" ("frameId
 //                    n_candidates -1 0 0 0" for a frame without a connection). The tracking context is created with max_keyframes 3
 //                    at least. Without the flag every output file is what it was
+// --restore-light    (LC mode, with --restore-connection only: a usage error otherwise) globalOptimize::restoreAffineLight: the
+//                    candidates are scored by ellc_keyframe_trial_propagate_lit at (1, 0), a light is fitted per candidate
+//                    (ellc_trial_light_solve), they are scored again at it, and the map restarts through
+//                    ellc_depth_restart_from_keyframes_lit at the winner's light; every line of FILE ends in " gain offset" (the
+//                    winner's; "1 0" for a frame without a connection)
 // Input is otherwise a header-less file of W*H u8 grey frames (the decode itself always stays outside).
 // In LC mode finished keyframes go through the loop-closure ring (facade class globalOptimize): matching and the batched
 // alignment of a pushed keyframe run on a second thread and a second context beside tracking, joined at the next push
@@ -102,7 +108,7 @@ using namespace ellc;
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--sweep-matches PATH] [--refine-matches PATH] [--joint-matches PATH] [--cull-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s frames.raw W H num_frames out_dir [LC] [levels] [--save-mats DIR] [--replicate DIR] [--init-poses FILE] [--bgr] [--no-undistort] [--match-quality PATH] [--match-geometry PATH] [--match-sim3 PATH [--match-light] [--sweep-matches PATH] [--refine-matches PATH] [--joint-matches PATH] [--cull-matches PATH]] [--map FILE] [--render FILE] [--fuse FILE [--fuse-inputs DIR]] [--absorb-matches FILE] [--restore-connection FILE] [--restore-light]\n", argv[0]);
     return -1;
   }
   const std::string in = argv[1], outdir = argv[5];
@@ -110,7 +116,7 @@ int main(int argc, char** argv) {
   bool lc = false;
   int levels = 4;
   std::string save_mats, replicate, init_poses;
-  bool bgr = false, undistort = true, no_fused = false, match_light = false;
+  bool bgr = false, undistort = true, no_fused = false, match_light = false, restore_light = false;
   int world = 1, rank = 0, device = 0, comm_port = 0;
   std::string comm_id_file, match_quality, match_geometry, match_sim3, refine_matches, sweep_matches, cull_matches, joint_matches, map_file, render_file, fuse_file, fuse_inputs, absorb_matches, restore_connection;
   for (int i = 6; i < argc; i++) {
@@ -132,6 +138,7 @@ int main(int argc, char** argv) {
     else if (a == "--match-geometry" && i + 1 < argc) match_geometry = argv[++i];
     else if (a == "--match-sim3" && i + 1 < argc) match_sim3 = argv[++i];
     else if (a == "--match-light") match_light = true;
+    else if (a == "--restore-light") restore_light = true;
     else if (a == "--refine-matches" && i + 1 < argc) refine_matches = argv[++i];
     else if (a == "--sweep-matches" && i + 1 < argc) sweep_matches = argv[++i];
     else if (a == "--cull-matches" && i + 1 < argc) cull_matches = argv[++i];
@@ -147,6 +154,10 @@ int main(int argc, char** argv) {
   }
   if (match_light && match_sim3.empty()) {
     std::fprintf(stderr, "--match-light needs --match-sim3 PATH: the light is fitted inside the Sim(3) refinement and reported in its file\n");
+    return -1;
+  }
+  if (restore_light && restore_connection.empty()) {
+    std::fprintf(stderr, "--restore-light needs --restore-connection FILE: the light is fitted inside the search for a new connection and reported in its file\n");
     return -1;
   }
   if (!refine_matches.empty() && match_sim3.empty()) {
@@ -272,6 +283,7 @@ int main(int argc, char** argv) {
       restore_file.open(restore_connection.c_str());
       if (!restore_file) { std::fprintf(stderr, "cannot open %s\n", restore_connection.c_str()); return -1; }
       globalOptimizeLoop->restoreConnection = true;
+      globalOptimizeLoop->restoreAffineLight = restore_light;
     }
     std::vector<std::unique_ptr<frame>> frameptr_vector;
     frame* activeKeyFrame = nullptr;
@@ -307,10 +319,17 @@ int main(int argc, char** argv) {
           const globalOptimize::RestoreRecord& r = g.lastRestore;
           if (!g.connectionLost) {   // a new connection: the frame becomes the active keyframe
             int n_targets = 0;
+            float gain = 1.0f, offset = 0.0f;
             for (size_t b = 0; b < r.ids.size(); b++)
-              if (r.ids[b] == r.chosen) n_targets = r.records[b].n_targets;
+              if (r.ids[b] == r.chosen) {
+                n_targets = r.records[b].n_targets;
+                gain = r.lights[2 * b];
+                offset = r.lights[2 * b + 1];
+              }
             restore_file << (cur->frameId + rt.BATCH_START_ID - 1) << " " << r.ids.size() << " " << (r.chosenFrameId + rt.BATCH_START_ID - 1) << " " << n_targets
-                         << " " << r.seedsAfter << " " << r.rescaleFactor << "\n";
+                         << " " << r.seedsAfter << " " << r.rescaleFactor;
+            if (restore_light) restore_file << " " << gain << " " << offset;
+            restore_file << "\n";
             restore_file.flush();
             currentDepthMap = *g.temp_depthMap;   // :267
             const float seeds_found = currentDepthMap.calculate_no_of_Seeds();
@@ -329,7 +348,7 @@ int main(int argc, char** argv) {
             frameptr_vector.erase(frameptr_vector.begin(), frameptr_vector.end() - 1);   // keep only the new keyframe
             continue;   // :314
           }
-          restore_file << (cur->frameId + rt.BATCH_START_ID - 1) << " " << r.ids.size() << " -1 0 0 0\n";
+          restore_file << (cur->frameId + rt.BATCH_START_ID - 1) << " " << r.ids.size() << " -1 0 0 0" << (restore_light ? " 1 0" : "") << "\n";
           restore_file.flush();
           frameptr_vector.pop_back();   // :319-322: the frame is of no use
           continue;

@@ -17,10 +17,10 @@ ellc_status render_scratch(ellc_ctx* c) {
   const size_t blocks0 = (n0 + 255) / 256;
   if (!c->render_nvalid_h) {
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_stage = 0, o_keys = o_stage + up((size_t)13 * MK * 4), o_depth = o_keys + up(n0 * 8), o_var = o_depth + up(n0 * 4),
+    const size_t o_stage = 0, o_keys = o_stage + up((size_t)15 * MK * 4), o_depth = o_keys + up(n0 * 8), o_var = o_depth + up(n0 * 4),
                  o_source = o_var + up(n0 * 4), o_agree = o_source + up(n0 * 4), o_int = o_agree + up(n0 * 4), o_counts = o_int + up(n0),
                  bytes = o_counts + up(blocks0 * 4);
-    ellc_status s = c->render_stage_h ? ELLC_OK : host_alloc(c, &c->render_stage_h, (size_t)13 * MK);
+    ellc_status s = c->render_stage_h ? ELLC_OK : host_alloc(c, &c->render_stage_h, (size_t)15 * MK);
     if (s != ELLC_OK) return s;
     if (!c->render_block_d) {
       ELLC_HIP(c, hipMalloc(&c->render_block_d, bytes));
@@ -45,12 +45,17 @@ ellc_status render_scratch(ellc_ctx* c) {
   return ELLC_OK;
 }
 
-// the requests' slots and transforms, staged and on their way to the device
-ellc_status render_stage(ellc_ctx* c, int B, const int* kf_slots, const float* T12) {
+// the requests' slots, transforms and lights (NULL: (1, 0) each; the absorb's gate alone reads them), staged and on their way to the device
+ellc_status render_stage(ellc_ctx* c, int B, const int* kf_slots, const float* T12, const float* light = nullptr) {
   const int MK = c->cfg.max_keyframes;
   for (int b = 0; b < B; b++) c->render_stage_h[b] = kf_slots[b];
   std::memcpy(c->render_stage_h + MK, T12, (size_t)B * 12 * sizeof(float));
-  ELLC_HIP(c, hipMemcpyAsync(c->render_stage_d, c->render_stage_h, (size_t)13 * MK * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  float* l = (float*)(c->render_stage_h + (size_t)13 * MK);
+  for (int b = 0; b < B; b++) {
+    l[2 * b] = light ? light[2 * b] : 1.0f;
+    l[2 * b + 1] = light ? light[2 * b + 1] : 0.0f;
+  }
+  ELLC_HIP(c, hipMemcpyAsync(c->render_stage_d, c->render_stage_h, (size_t)15 * MK * sizeof(int), hipMemcpyHostToDevice, c->stream));
   return ELLC_OK;
 }
 
@@ -77,11 +82,14 @@ RenderArgs render_args(ellc_ctx* c, int B, int level, const ellc_map_filter* f, 
 
 // What ellc_keyframe_render_depth and ellc_keyframe_fuse_depth refuse alike (the fusion accepts a destination among its sources).
 // Validated first: a refused call leaves the context and every slot as they were (the message is composed only when a call is refused)
+// the number of requests a call over the render's staging takes
+bool render_B_ok(const ellc_ctx* c, int B) { return B >= 1 && B <= c->cfg.max_keyframes && B <= 256; }
+
 ellc_status render_validate(ellc_ctx* c, const char* who, int B, const int* kf_slots, const float* T12, int level, const ellc_map_filter* f,
                             float agree_k2, int dst, bool dst_may_be_source) {
   if (!c) return ELLC_ERR_BAD_ARG;
   if (!kf_slots || !T12 || !f) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": null pointer");
-  if (B < 1 || B > c->cfg.max_keyframes || B > 256) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": B out of range");
+  if (!render_B_ok(c, B)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": B out of range");
   if (level < 0 || level >= c->L) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": level out of range");
   const LevelGeom& g = c->geom_h[level];
   if (g.n > (1 << 24)) return fail(c, ELLC_ERR_BAD_ARG, std::string(who) + ": more than 2^24 pixels on the level");

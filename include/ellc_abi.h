@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define ELLC_MAX_LEVELS 8
-#define ELLC_ABI_VERSION 23   /* ellc_keyframe_joint_step, ellc_joint_solve, ellc_keyframe_joint_apply, ellc_keyframe_joint_refine, ellc_joint_default_params; 22: ellc_keyframe_cull_depth, ellc_cull_default_params; 21: ellc_keyframe_sweep_depth, ellc_sweep_default_params; 20: ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
+#define ELLC_ABI_VERSION 24   /* ellc_depth_absorb_keyframes_lit, ellc_depth_restart_from_keyframes_lit, ellc_keyframe_trial_propagate_lit, ellc_trial_light_solve; 23: ellc_keyframe_joint_step, ellc_joint_solve, ellc_keyframe_joint_apply, ellc_keyframe_joint_refine, ellc_joint_default_params; 22: ellc_keyframe_cull_depth, ellc_cull_default_params; 21: ellc_keyframe_sweep_depth, ellc_sweep_default_params; 20: ellc_keyframe_refine_depth, ellc_refine_default_params, ellc_sim3_invert; 19: ellc_keyframe_light_step, ellc_keyframe_sim3_step_lit, ellc_keyframe_sim3_align_lit, ellc_light_solve; 18: ellc_keyframe_trial_propagate, ellc_depth_restart_from_keyframes; 17: ellc_depth_absorb_keyframes; 16: ellc_keyframe_fuse_depth; 15: ellc_keyframe_sim3_step, ellc_keyframe_sim3_align; 14: ellc_keyframe_depth_consistency; 13: ellc_keyframe_render_depth; 12: ellc_keyframe_map_points; 11: ellc_align_quality_at; 10 (r06): measurement hooks and self-tests moved out (ellc_abi_diag.h) */
 
 typedef enum {
   ELLC_OK = 0,
@@ -763,6 +763,61 @@ ellc_status ellc_keyframe_sim3_align_lit(ellc_ctx* ctx, int B, const int* src_kf
                                          float* T12_out, float* light_out, ellc_sim3_normal* out, ellc_light_normal* light_rec_out,
                                          int* iters_out, float* trace_T12, ellc_sim3_normal* trace_rec, float* trace_light,
                                          ellc_light_normal* trace_light_rec, int trace_capacity);
+
+/* ---- affine brightness in the absorb, the trial propagation and the restart (v24) ------------------------------------
+ * The light of v19 in the last link of a loop closure: the photometric gate of ellc_depth_absorb_keyframes step 4, which
+ * ellc_keyframe_trial_propagate and ellc_depth_restart_from_keyframes share. light[2 * b] is the gain and light[2 * b + 1] the offset of
+ * request b; they map the SOURCE's grey value into the destination's (K's, the trial's destination, the new keyframe's), the direction
+ * of T = T12 + 12 * b: Ip = gain * Is + offset in f32, the product rounded, then the sum (two roundings, no contraction). ONLY the
+ * residual changes: r = Iw - Ip. g, the constants 1600.0f and 0.25f and the test g < 5.0f stay in the destination's units, so a DARKER
+ * destination still loses its low-gradient candidates to g < 5.0f (MIN_ABS_GRAD_DECREASE, the reference's constant): no light repairs
+ * that. light NULL means (1, 0) for every request; (1, 0) gives Ip == Is bit for bit (Is >= 0). A given light with a value that is not
+ * finite is ELLC_ERR_BAD_ARG.
+ *
+ * ellc_depth_absorb_keyframes_lit / ellc_depth_restart_from_keyframes_lit: everything of the unlit calls applies word for word - rule,
+ * order, stats, refusals, finalise, "a refused call changes nothing" - with step 4's residual taken against Ip at the request's light.
+ * With light NULL, or (1, 0) for a request, that request's candidates are the unlit call's; with that for every request the state
+ * planes, K's planes, the sixteen counts and the factor are the unlit call's bytes. The unlit entry points run the same kernels at (1, 0). */
+ellc_status ellc_depth_absorb_keyframes_lit(ellc_ctx* ctx, int B, const int* kf_slots, const float* T12, const float* light /* may be NULL */,
+                                            const ellc_map_filter* filter, const ellc_absorb_params* params,
+                                            ellc_absorb_stats* out /* may be NULL */);
+ellc_status ellc_depth_restart_from_keyframes_lit(ellc_ctx* ctx, int new_kf_slot, int B, const int* kf_slots, const float* T12,
+                                                  const float* light /* may be NULL */, const ellc_map_filter* filter,
+                                                  const ellc_absorb_params* params, float* rescale_factor /* may be NULL */,
+                                                  ellc_absorb_stats* out /* may be NULL */);
+
+/* ellc_keyframe_trial_propagate_lit: ellc_keyframe_trial_propagate with r = Iw - Ip at the request's light, and the sums a caller needs
+ * to FIT that light. The first 48 bytes of a record are an ellc_trial_propagation evaluated at `light`: sum_r2, sum_abs_r, the gate,
+ * n_candidates and n_targets all use r = Iw - Ip; at light NULL or (1, 0) they are ellc_keyframe_trial_propagate's bytes. The five sums
+ * behind them run over EVERY pixel counted in n_interior (n_fit == n_interior), with Is the source's grey value and Iw the bilinear
+ * value of step 4, both f32: they do not depend on `light` or on photo_gate. Each term of sum_ss, sum_st, sum_tt is the exact double
+ * product of two f32 values; the terms are added in double in the record's own fixed order and partition (no floating-point atomics).
+ * A record is a function of its own request alone, as before. Its scratch and staging are its own. Errors: those of
+ * ellc_keyframe_trial_propagate, and ELLC_ERR_BAD_ARG for a given light with a value that is not finite. */
+typedef struct {            /* 96 bytes, every field naturally aligned */
+  double  sum_r2;           /* as in ellc_trial_propagation, with r = Iw - Ip */
+  double  sum_abs_r;
+  int32_t n_kept, n_in_view, n_interior, n_low_grad, n_candidates, n_targets;
+  int32_t reserved[2];      /* 0 */
+  double  sum_s;            /* sum (double)Is over the pixels counted in n_interior */
+  double  sum_t;            /* sum (double)Iw */
+  double  sum_ss;           /* sum (double)Is * (double)Is   (exact product) */
+  double  sum_st;           /* sum (double)Is * (double)Iw   (exact product) */
+  double  sum_tt;           /* sum (double)Iw * (double)Iw   (exact product) */
+  int32_t n_fit;            /* == n_interior */
+  int32_t reserved2;        /* 0 */
+} ellc_trial_propagation_lit;
+
+ellc_status ellc_keyframe_trial_propagate_lit(ellc_ctx* ctx, int B, const int* src_kf_slots, int dst_is_keyframe, const int* dst_slots,
+                                              const float* T12, const float* light /* may be NULL */, const ellc_map_filter* filter,
+                                              int photo_gate, ellc_trial_propagation_lit* out);
+
+/* Host only, no device work. ellc_light_solve's rule (above) with weight 1 over the record's interior pixels: the ellc_light_normal with
+ * sum_w = n_fit, sum_w_s = sum_s, sum_w_t = sum_t, sum_w_ss = sum_ss, sum_w_st = sum_st, sum_w_tt = sum_tt and n_photo = n_fit is handed
+ * to ellc_light_solve: the same acceptance tests, roundings and return convention (0 accepted, 1 refused: light_in's bits, NULL meaning
+ * (1, 0)); every other field of the normal is zero. An unweighted one-shot fit: no Huber weight, no iteration. A NULL rec, params or
+ * light_out returns 1 and writes nothing (ellc_light_solve itself checks no pointer). */
+int ellc_trial_light_solve(const ellc_trial_propagation_lit* rec, const ellc_light_params* params, const float* light_in, float* light_out);
 
 /* ---- a keyframe's map refined against other views (v20) -------------------------------------------------------------
  * The structure step beside the motion step above: a per-pixel photometric Gauss-Newton on the INVERSE DEPTH of keyframe slot

@@ -518,6 +518,7 @@ class globalOptimize {
   // (finalise on: the map is regularised and exported, so what createKeyFrame propagates next is the absorbed map), and absorb_file
   // (when open) gets "frameId B" and the fifteen stats per push (B 0 and zeros for a push without a match). The tracking runtime
   // needs max_keyframes >= 2 + MAX_LOOP_ARRAY_LENGTH_SCALE_AVG; otherwise pushToArray throws. lastAbsorbStats keeps the record.
+  // With matchAffineLight the fold is ellc_depth_absorb_keyframes_lit at every entry's gain and offset (candidate -> keyframe, T's direction).
   struct AbsorbRecord {
     int frameId = 0, B = 0;
     ellc_absorb_stats stats;
@@ -584,7 +585,8 @@ class globalOptimize {
     std::vector<int> ids, slots;                  // ring array ids / ring keyframe slots of the candidates, in the order findMatch handed them out
     std::vector<float> poses;                     // [candidates][6]: the test frame w.r.t. each candidate, as the batch returned them
     std::vector<float> T;                         // [candidates][12]: candidate camera -> test frame camera, as passed to the library
-    std::vector<ellc_trial_propagation> records;  // per candidate
+    std::vector<ellc_trial_propagation> records;  // per candidate (with restoreAffineLight: of the second trial, at the fitted lights)
+    std::vector<float> lights;                    // [candidates][2]: gain and offset the candidates were scored at ((1, 0) without restoreAffineLight)
     std::vector<int> tried;                       // ring array ids in the order their restart was run
     int chosen = -1;                              // the ring array id the map was restarted from, -1: none
     int chosenFrameId = -1, newKeyframeSlot = -1;
@@ -592,6 +594,12 @@ class globalOptimize {
     float rescaleFactor = 0.0f, seedsAfter = 0.0f;
   };
   bool restoreConnection = false;
+  // restoreAffineLight (off by default: nothing changes; it acts inside restoreConnection's search): the exposure has usually swung when
+  // tracking is lost, so step (c) becomes one ellc_keyframe_trial_propagate_lit at (1, 0), ellc_trial_light_solve of every candidate's
+  // record with the default ellc_light_params (a refused fit keeps (1, 0)), and a second trial at the fitted lights; (d) orders by the
+  // second trial's n_targets, and (e) restarts with ellc_depth_restart_from_keyframes_lit at the winner's light. The alignment of (b)
+  // stays blind to the light.
+  bool restoreAffineLight = false;
   RestoreRecord lastRestore;
   // With restoreConnection off, GlobalOptimize.cpp:717-760 AS SHIPPED: waits for the match thread, pushes the stray test frame (no depth
   // map) into the ring at currentArrayId — histogram, ids, image — and returns: the search that follows in the source sits behind an
@@ -688,7 +696,16 @@ class globalOptimize {
       filter.max_var = 0.0f; filter.min_support = 3; filter.support_k2 = 1.0f; filter.stride = 1;
       ellc_absorb_params params;
       ellc_absorb_default_params(&params);
-      rt->check(ellc_depth_absorb_keyframes(rt->ctx, B, slots.data(), T.data(), &filter, &params, &lastAbsorbStats.stats), "ellc_depth_absorb_keyframes");
+      if (matchAffineLight) {   // the refined light of every candidate, candidate -> keyframe (T's direction), in the fold's photometric gate
+        std::vector<float> light((size_t)B * 2);
+        for (int b = 0; b < B; b++) {
+          light[(size_t)b * 2] = lastMatchSim3[(size_t)b].gain;
+          light[(size_t)b * 2 + 1] = lastMatchSim3[(size_t)b].offset;
+        }
+        rt->check(ellc_depth_absorb_keyframes_lit(rt->ctx, B, slots.data(), T.data(), light.data(), &filter, &params, &lastAbsorbStats.stats),
+                  "ellc_depth_absorb_keyframes_lit");
+      } else
+        rt->check(ellc_depth_absorb_keyframes(rt->ctx, B, slots.data(), T.data(), &filter, &params, &lastAbsorbStats.stats), "ellc_depth_absorb_keyframes");
     }
     if (absorb_file.is_open()) {
       const int32_t* v = &lastAbsorbStats.stats.n_kept;   // sixteen int32 in a row (ellc_abi.h); the reserved word is not written
@@ -856,8 +873,22 @@ class globalOptimize {
       for (int k = 0; k < 12; k++) lastRestore.T[(size_t)b * 12 + k] = M[k];
     }
     lastRestore.records.assign((size_t)B, ellc_trial_propagation());
-    ring.check(ellc_keyframe_trial_propagate(ring.ctx, B, lastRestore.slots.data(), 0, fr.data(), lastRestore.T.data(), &filter, 1, lastRestore.records.data()),
-               "ellc_keyframe_trial_propagate");
+    lastRestore.lights.assign((size_t)B * 2, 0.0f);
+    for (int b = 0; b < B; b++) lastRestore.lights[(size_t)b * 2] = 1.0f;
+    if (restoreAffineLight) {
+      std::vector<ellc_trial_propagation_lit> lit((size_t)B);
+      ring.check(ellc_keyframe_trial_propagate_lit(ring.ctx, B, lastRestore.slots.data(), 0, fr.data(), lastRestore.T.data(), nullptr, &filter, 1, lit.data()),
+                 "ellc_keyframe_trial_propagate_lit");
+      ellc_light_params lp;
+      ellc_light_default_params(&lp);
+      for (int b = 0; b < B; b++) (void)ellc_trial_light_solve(&lit[(size_t)b], &lp, nullptr, &lastRestore.lights[(size_t)b * 2]);
+      ring.check(ellc_keyframe_trial_propagate_lit(ring.ctx, B, lastRestore.slots.data(), 0, fr.data(), lastRestore.T.data(), lastRestore.lights.data(), &filter,
+                                                   1, lit.data()),
+                 "ellc_keyframe_trial_propagate_lit");
+      for (int b = 0; b < B; b++) std::memcpy(&lastRestore.records[(size_t)b], &lit[(size_t)b], sizeof(ellc_trial_propagation));   // its first 48 bytes
+    } else
+      ring.check(ellc_keyframe_trial_propagate(ring.ctx, B, lastRestore.slots.data(), 0, fr.data(), lastRestore.T.data(), &filter, 1, lastRestore.records.data()),
+                 "ellc_keyframe_trial_propagate");
     // (d) descending n_targets, ties to the lower ring index
     std::vector<int> order;
     for (int b = 0; b < B; b++)
@@ -881,8 +912,13 @@ class globalOptimize {
       promoted = true;
       float factor = 1.0f;
       lastRestore.tried.push_back(lastRestore.ids[(size_t)b]);
-      rt->check(ellc_depth_restart_from_keyframes(rt->ctx, ns, 1, &copy_slot, &lastRestore.T[(size_t)b * 12], &filter, &params, &factor, &lastRestore.stats),
-                "ellc_depth_restart_from_keyframes");
+      if (restoreAffineLight)
+        rt->check(ellc_depth_restart_from_keyframes_lit(rt->ctx, ns, 1, &copy_slot, &lastRestore.T[(size_t)b * 12], &lastRestore.lights[(size_t)b * 2], &filter,
+                                                        &params, &factor, &lastRestore.stats),
+                  "ellc_depth_restart_from_keyframes_lit");
+      else
+        rt->check(ellc_depth_restart_from_keyframes(rt->ctx, ns, 1, &copy_slot, &lastRestore.T[(size_t)b * 12], &filter, &params, &factor, &lastRestore.stats),
+                  "ellc_depth_restart_from_keyframes");
       depthMap* dm = new depthMap(*rt);
       dm->keyFrame = testFrame;
       dm->currentFrame = testFrame;
